@@ -3,7 +3,16 @@
 all-reduce] + Keras-Adam) of dl4ds's 4x residual-backbone sub-pixel SR model at 128->512 grids
 (BASELINE.json configs[1]; configs[2] when run on N GPUs).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--config cfg2|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--config cfg2|cfg4|cfg5] [--full]
+                    [--dump-outputs DIR]
+
+A plain run sets up, warms up (W steps), times the K steps and prints the line: `value` = HR samples/s over the K steps,
+`ms_per_step` = milliseconds per timed step.  `--full` adds everything else the line can carry: the library profiler's per-kernel
+figures (`roofline`, `step_roofline`, `hbm_kernels`, DL4DS_BENCH_BREAKDOWN=1's `breakdown`), the >= 2 s `steady_state` window and,
+for cfg2 on one GPU, the unfolded graph, the per-GPU-batch-16 line and the CPU baseline (`--no-*` switch those off one by one).
+`--dump-outputs DIR` writes what the last timed step returned to its caller -- the loss and the updated weights (cfg5: both
+models' weights; `--predict`: the HR fields) -- as DIR/<name>.npy in float32; inputs and initial weights are seeded, so two
+builds can be compared output for output.
 
 `python bench.py --gpus N` (N > 1) starts the N ranks itself -- one process per GPU with RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR / MASTER_PORT set -- and works just as well under a launcher that already did
@@ -83,6 +92,29 @@ def synthetic_batch_cfg5(seed, batch, H=512):
     x = np.repeat(np.repeat(block_mean(f, 8), 8, axis=1), 8, axis=2)
     aux = box_blur_fields(rng, (batch, H, H))
     return x.astype(np.float32), aux.astype(np.float32), y.astype(np.float32)
+
+
+DUMP_MAX_ELEMS = 1 << 22               # --dump-outputs: a larger array is stored as a fixed, seeded sample of this many elements
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: {name: array} -> out_dir/<name>.npy (float32; float64 stays float64), '/' in a name -> '.'.  An array of more
+    than DUMP_MAX_ELEMS elements is replaced by the elements at DUMP_MAX_ELEMS flat indices drawn without replacement by
+    np.random.default_rng(0), in increasing order (the same indices for the same shape in every run).  -> {name: description}."""
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        desc = {'shape': list(a.shape)}
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+            desc['sample'] = f'{DUMP_MAX_ELEMS} elements at seeded flat indices (default_rng(0), sorted)'
+        fname = name.replace('/', '.') + '.npy'
+        np.save(os.path.join(out_dir, fname), a)
+        written[fname] = desc
+    return written
 
 
 def csrc_sha():
@@ -373,8 +405,13 @@ def step_roofline(rep, nprof, ms_step):
 
 
 # ------------------------------------------------------------------------------------------------ workloads
+def supervised_outputs(eng, model):
+    """What a supervised train step returns to its caller: the batch loss and the updated weights (by variable name)."""
+    return dict([('loss', np.asarray([eng.last_loss()], np.float32))] + [('weights/' + k, v) for k, v in model.get_weights().items()])
+
+
 def make_workload(name, B, rank, world):
-    """-> dict(step=callable, describe=str, engine=..., model=..., metric=str, cfg2=bool)."""
+    """-> dict(step=callable, describe=str, engine=..., model=..., metric=str, loss=callable, outputs=callable -> {name: array})."""
     import dl4ds_amd.models as PM
     from dl4ds_amd.device import DeviceArray
     from dl4ds_amd.training import SupervisedEngine, CGANEngine
@@ -387,7 +424,7 @@ def make_workload(name, B, rank, world):
                     metric='HR samples/s (train step) at 4x 128->512 residual SR',
                     describe=('configs[1]: net_postupsampling(resnet, spc, scale=4, lr 128x128 -> hr 512x512, 204405 '
                               'params), MAE, Adam' if world == 1 else 'configs[2]: same model, data-parallel over RCCL'),
-                    loss=lambda: eng.last_loss())
+                    loss=lambda: eng.last_loss(), outputs=lambda: supervised_outputs(eng, model))
     if name == 'cfg4':
         T, h, s = 8, 64, 4
         model = PM.recnet_postupsampling('densenet', 'rc', s, 1, 1, (h, h), time_window=T, attention=True,
@@ -399,7 +436,7 @@ def make_workload(name, B, rank, world):
                     metric='HR samples/s (train step), spatio-temporal dense + attention + LCB, resize-conv 4x, T=8, 64->256',
                     describe=f'configs[3]: recnet_postupsampling(densenet, rc, scale=4, lr 64x64, T=8, attention, LCB, 1 aux; '
                              f'{model.count_params()} params), MAE, Adam',
-                    loss=lambda: eng.last_loss())
+                    loss=lambda: eng.last_loss(), outputs=lambda: supervised_outputs(eng, model))
     if name == 'cfg5':
         H = 512
         gen = PM.unet_pin('unet', 5, 1, hr_size=(H, H), n_filters=8, n_blocks=6, decoder_upsampling='dc', seed=7)
@@ -411,7 +448,9 @@ def make_workload(name, B, rank, world):
                     metric='HR samples/s (CGAN train step), U-Net(deconv) generator + residual discriminator, 8x 64->512',
                     describe=f'configs[4]: unet_pin(unet, dc, 5+1 channels, hr 512x512; G {gen.count_params()} + '
                              f'D {disc.count_params()} params), CGAN step (MAE x100 + BCE), 2 x Adam(2e-4, beta1 0.5)',
-                    loss=lambda: None)
+                    loss=lambda: None,
+                    outputs=lambda: dict([('generator/' + k, v) for k, v in gen.get_weights().items()] +
+                                         [('discriminator/' + k, v) for k, v in disc.get_weights().items()]))
     raise SystemExit(f'unknown --config {name}')
 
 
@@ -449,6 +488,7 @@ def predict_line(args):
         fwd()
     L.check(lib.dl4ds_sync())
     dt = (time.perf_counter() - t0) / args.steps
+    outputs = {'pred': y.numpy()} if args.dump_outputs else None          # the HR fields of the last timed forward pass
     n2 = int(np.ceil(MIN_STEADY_S / dt))
     t0 = time.perf_counter()
     for _ in range(n2):
@@ -493,6 +533,8 @@ def predict_line(args):
            'kernels': top, 'cpu_baseline': None}
     if dom.startswith('conv_split'):
         split_roofs(out['roofline'], achieved)
+    if outputs is not None:
+        out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dump_outputs(args.dump_outputs, outputs)}
     print(json.dumps(out), flush=True)
 
 
@@ -571,6 +613,11 @@ def main():
                          'training/supervised.py:49) and 16 for cfg4 / cfg5 (training/cgan.py:48)')
     ap.add_argument('--config', default='cfg2', choices=['cfg2', 'cfg4', 'cfg5'])
     ap.add_argument('--predict', action='store_true', help='the forward-only line of configs[1] (Predictor API) instead of the train step')
+    ap.add_argument('--full', action='store_true',
+                    help='also the per-kernel profile and rooflines, the steady-state window and (cfg2, one GPU) the unfolded graph, '
+                         'the per-GPU-batch-16 line and the CPU baseline; a plain run times the K steps only')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step returned (loss, updated weights) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-profile', action='store_true')
     ap.add_argument('--no-unfolded', action='store_true', help='skip the 5-step comparison run of the unfolded graph')
@@ -614,7 +661,8 @@ def main():
     if dist_on:
         parallel.broadcast_trainer(eng)
     is_cfg2 = args.config == 'cfg2'
-    w0 = model.get_weights() if (rank == 0 and world == 1 and is_cfg2 and not args.no_cpu_baseline) else None
+    full = args.full
+    w0 = model.get_weights() if (full and rank == 0 and world == 1 and is_cfg2 and not args.no_cpu_baseline) else None
 
     def barrier():
         L.check(lib.dl4ds_sync())
@@ -623,18 +671,18 @@ def main():
 
     # ---- warm-up; on rank 0 its last steps are timed per launch (HIP events on the library stream) to find the kernel
     #      with the largest share of step time and to provide the per-kernel figures
-    prof_on = rank == 0 and not args.no_profile
+    prof_on = full and rank == 0 and not args.no_profile
     nprof = min(3, args.warmup) if prof_on else 0
     if prof_on and nprof == 0:
         nprof = 2            # --warmup 0: two extra (untimed) steps are needed to pick the kernel to instrument
     # every rank runs the SAME number of steps (each step is a sequence of collectives): the ranks that do not profile make up
     # for rank 0's extra steps of a --warmup 0 run
-    extra_other = (2 if (args.warmup == 0 and not args.no_profile) else 0) if (world > 1 and rank != 0) else 0
+    extra_other = (2 if (args.warmup == 0 and full and not args.no_profile) else 0) if (world > 1 and rank != 0) else 0
     for _ in range(max(args.warmup - nprof, 0) + extra_other):
         step()
     breakdown, dom, dom_share, rep_all = None, None, None, None
     executed_gflop_per_step = mfma_gflop_per_step = direct_gflop_per_step = None
-    winograd = False
+    winograd = None           # (known from the profile of a --full run)
     hbm_kernels = None
 
     def report():
@@ -690,6 +738,8 @@ def main():
         dt = parallel.allreduce_host([dt_own], 'max')[0]        # slowest rank
         dt_min = parallel.allreduce_host([dt_own], 'min')[0]
     loss = wl['loss']()
+    # (taken before the steady-state window of --full trains the same model further)
+    outputs = wl['outputs']() if (args.dump_outputs and rank == 0) else None
 
     roofline = None
     if dom is not None:
@@ -761,7 +811,7 @@ def main():
     #      clock is still settling; `value` stays the K-step figure the contract asks for, `steady_state` reports both
     steady = None
     ms_first = 1e3 * dt / args.steps
-    if ms_first * args.steps < 1e3 * MIN_STEADY_S:
+    if full and ms_first * args.steps < 1e3 * MIN_STEADY_S:
         n2 = int(np.ceil(1e3 * MIN_STEADY_S / ms_first))
         barrier()
         t2 = time.perf_counter()
@@ -814,7 +864,7 @@ def main():
         }
         if breakdown is not None and os.environ.get('DL4DS_BENCH_BREAKDOWN'):
             out['breakdown'] = breakdown
-        if world == 1 and is_cfg2 and not os.environ.get('DL4DS_NO_FOLD') and not args.no_unfolded:
+        if full and world == 1 and is_cfg2 and not os.environ.get('DL4DS_NO_FOLD') and not args.no_unfolded:
             # the same step with every layer evaluated separately (the reference's evaluation order, DL4DS_NO_FOLD=1),
             # measured in the same run so that both figures sit side by side; `value` above is the product path
             try:
@@ -835,7 +885,7 @@ def main():
                 out['unfolded_graph'] = {'error': repr(e)}
             finally:
                 os.environ.pop('DL4DS_NO_FOLD', None)
-        if world == 1 and is_cfg2 and not args.no_b16 and B != 16:
+        if full and world == 1 and is_cfg2 and not args.no_b16 and B != 16:
             # "B per GPU in {8,16,32,64}, report best and B=16" -- the same step at per-GPU batch 16, timed the
             # same way (warm-up, K steps fenced by device syncs, then a >= 1 s window) in this run; `value` stays the B = 64 figure
             try:
@@ -866,6 +916,8 @@ def main():
                 out['gpu_over_cpu'] = value / out['cpu_baseline']['value']
             except Exception as e:          # the baseline must never kill the GPU number
                 out['cpu_baseline'] = {'error': repr(e)}
+        if outputs is not None:
+            out['dump_outputs'] = {'dir': args.dump_outputs, 'arrays': dump_outputs(args.dump_outputs, outputs)}
         print(json.dumps(out), flush=True)
     if dist_on:
         parallel.barrier()

@@ -1,18 +1,18 @@
 """The drop-in boundary keeps the reference's call signatures: every builder, trainer and Predictor entry point is
-compared with the reference's own source (AST, no import -- the reference needs TensorFlow) for parameter names,
-POSITIONAL ORDER and default values.  Runs where /root/reference exists (the build container); the GPU box has no copy.
+compared with the reference's own signatures for parameter names, POSITIONAL ORDER and default values.  Those are stored in
+tests/golden/reference_api.json, read from the reference's source by tests/golden/make_reference_api.py (AST, no import -- the
+reference needs TensorFlow).
 
 Arguments the build adds (``seed``, the static-graph sizes ``hr_size`` / ``time_window`` of the discriminator,
 ``checkpoint`` / ``device_data``) must come AFTER every reference parameter, so positional callers are unaffected."""
-import ast
 import importlib
 import inspect
+import json
 import os
 
 import pytest
 
-REF = '/root/reference/dl4ds/'
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present')
+REF_API = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'reference_api.json')
 
 PAIRS = [
     ('models/sp_postups.py', 'net_postupsampling', 'dl4ds_amd.models', 'net_postupsampling'),
@@ -39,33 +39,15 @@ DEFAULT_EXCEPTIONS = {
 }
 
 
-def _ref_functions(path):
-    tree = ast.parse(open(os.path.join(REF, path)).read())
-    out = {}
-    for node in tree.body:
-        if isinstance(node, ast.FunctionDef):
-            out[node.name] = node.args
-        elif isinstance(node, ast.ClassDef):
-            for n in node.body:
-                if isinstance(n, ast.FunctionDef):
-                    out[node.name + '.' + n.name] = n.args
-    return out
-
-
-def _ref_spec(a):
-    pos = [x.arg for x in a.args]
-    defaults = {}
-    for x, d in zip(pos[len(pos) - len(a.defaults):], a.defaults):
-        try:
-            defaults[x] = ast.literal_eval(d)
-        except Exception:
-            defaults[x] = ast.unparse(d)
-    return pos, defaults, a.kwarg.arg if a.kwarg else None
+def _ref_spec(path, name):
+    with open(REF_API) as f:
+        spec = json.load(f)['signatures'][path][name]
+    return spec['positional'], spec['defaults'], spec['kwarg']
 
 
 @pytest.mark.parametrize('ref_path,ref_name,mod,name', PAIRS)
 def test_signature_matches_the_reference(ref_path, ref_name, mod, name):
-    pos, dfl, kwarg = _ref_spec(_ref_functions(ref_path)[ref_name])
+    pos, dfl, kwarg = _ref_spec(ref_path, ref_name)
     obj = importlib.import_module(mod)
     for part in name.split('.'):
         obj = getattr(obj, part)

@@ -26,7 +26,10 @@ def _device_count():
     import ctypes
     import dl4ds_amd._lib as L
     n = ctypes.c_int()
-    L.check(L.load().dl4ds_device_count(ctypes.byref(n)))
+    try:
+        L.check(L.load().dl4ds_device_count(ctypes.byref(n)))
+    except L.Dl4dsHipError:          # no device visible: the skipif below is evaluated on machines without a GPU, too
+        return 0
     return n.value
 
 
@@ -123,7 +126,7 @@ def test_bench_runs_when_invoked_directly_with_gpus_flag():
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     for n in ([1, 2] if _device_count() >= 2 else [1]):
         r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', str(n), '--steps', '2', '--warmup', '1',
-                            '--batch', '4', '--no-cpu-baseline', '--no-unfolded'], capture_output=True, text=True,
+                            '--batch', '4', '--full', '--no-cpu-baseline', '--no-unfolded'], capture_output=True, text=True,
                            timeout=1200, env=env)
         assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
         line = [l for l in r.stdout.splitlines() if l.startswith('{')][-1]
@@ -133,6 +136,30 @@ def test_bench_runs_when_invoked_directly_with_gpus_flag():
         assert out['hbm_kernels'], out
         if n > 1:
             assert out['rccl']['nranks'] == n
+
+
+def test_plain_bench_run_times_the_steps_only_and_dumps_what_the_last_step_returned(tmp_path):
+    """A plain run (no --full): the K timed steps and nothing else on the line; --dump-outputs writes the loss and the updated
+    weights of the last timed step as float32 .npy files."""
+    env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
+    d = tmp_path / 'out'
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--batch', '4', '--dump-outputs', str(d)], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith('{')][-1])
+    assert out['steps'] == 3 and out['warmup'] == 1 and out['ms_per_step'] > 0
+    assert abs(out['value'] - 4 / (out['ms_per_step'] * 1e-3)) < 1e-6 * out['value']
+    assert out['roofline'] is None and out['steady_state'] is None and out['cpu_baseline'] is None and out['hbm_kernels'] is None
+    assert 'b16' not in out and 'unfolded_graph' not in out
+    files = sorted(os.listdir(d))
+    assert set(files) == set(out['dump_outputs']['arrays']) and len(files) == 1 + 56, files
+    assert sum(os.path.getsize(d / f) for f in files) < 64 << 20
+    loss = np.load(d / 'loss.npy')
+    assert loss.dtype == np.float32 and loss.shape == (1,) and loss[0] == np.float32(out['config']['loss_after_run'])
+    for f in files:
+        a = np.load(d / f)
+        assert a.dtype == np.float32 and np.isfinite(a).all(), f
+    assert np.load(d / 'weights.stem.kernel.npy').shape == tuple(out['dump_outputs']['arrays']['weights.stem.kernel.npy']['shape'])
 
 
 TWO_RANK = '''

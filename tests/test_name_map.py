@@ -1,7 +1,7 @@
 """The arena-name <-> Keras-variable map (tests/golden/keras_name_map.py) that lets a maintainer with TensorFlow
 regenerate tests/golden/*.npz from the REAL reference (tests/golden/make_golden_tf.py): it must cover every variable of
 every builder configuration, and its attribute chains must exist in the reference's class definitions."""
-import ast
+import json
 import os
 import sys
 
@@ -99,25 +99,17 @@ def test_unknown_names_are_rejected():
     assert K._snake('RecurrentConvBlock') == 'recurrent_conv_block' and K._snake('TransitionBlock') == 'transition_block'
 
 
-REF_BLOCKS = '/root/reference/dl4ds/models/blocks.py'
+REF_API = os.path.join(HERE, 'golden', 'reference_api.json')
 
 
-@pytest.mark.skipif(not os.path.exists(REF_BLOCKS), reason='reference checkout not present (GPU box)')
 def test_attribute_chains_exist_in_the_reference_classes():
     """Every sub-layer attribute the map walks is a ``self.<attr> = <Layer>(...)`` assignment of that reference class (or
-    of a base class), and every explicit layer name the map selects by is a name the reference builders assign."""
-    tree = ast.parse(open(REF_BLOCKS).read())
-    attrs, bases = {}, {}
-    for node in tree.body:
-        if isinstance(node, ast.ClassDef):
-            bases[node.name] = [b.id for b in node.bases if isinstance(b, ast.Name)]
-            got = set()
-            for sub in ast.walk(node):
-                if isinstance(sub, ast.Assign):
-                    for t in sub.targets:
-                        if isinstance(t, ast.Attribute) and isinstance(t.value, ast.Name) and t.value.id == 'self':
-                            got.add(t.attr)
-            attrs[node.name] = got
+    of a base class), and every explicit layer name the map selects by is a name the reference builders assign.  The
+    reference's classes and names are stored in tests/golden/reference_api.json (tests/golden/make_reference_api.py)."""
+    with open(REF_API) as f:
+        api = json.load(f)
+    attrs = {c: set(v['attrs']) for c, v in api['classes'].items()}
+    bases = {c: v['bases'] for c, v in api['classes'].items()}
 
     def all_attrs(cls):
         out = set(attrs.get(cls, ()))
@@ -129,8 +121,6 @@ def test_attribute_chains_exist_in_the_reference_classes():
         assert cls in attrs, f'reference has no class {cls}'
         missing = want - all_attrs(cls)
         assert not missing, f'{cls}: attributes {missing} are not defined by the reference class'
-    src = ''.join(open(os.path.join('/root/reference/dl4ds/models', f)).read()
-                  for f in ('sp_postups.py', 'sp_preups.py', 'spt_postups.py', 'spt_preups.py', 'discriminator.py', 'blocks.py'))
     for literal in ("'ResidualBlock' + str(i+1)", "'ConvBlock' + str(i+1)", "'DenseBlock' + str(i+1)", "'Transition' + str(i+1)",
                     "'ConvNextBlock' + str(i+1)", "name='TransitionLast'", "name='ConvBlock_aux'", "name='TransitionBackboneLast'",
                     "name='TransitionDC'", "name='Bottleneck'", "'DecoderConvBlock' + str(j+1)", "name='EncoderBlock' + name_suffix",
@@ -138,7 +128,7 @@ def test_attribute_chains_exist_in_the_reference_classes():
                     "name='Deconvolution' + name_suffix", "name='upsampling_' + upsampling", "name='localized_conv_block'",
                     "_branch1'", "_branch2'", "name='deconv_1of2_scale_x2'", "name='deconv_2of2_scale_x2'",
                     "name='deconv_scale_x' + str(self.scale)"):
-        assert literal in src, f'the reference no longer assigns {literal}'
+        assert literal in api['layer_names'], f'the reference no longer assigns {literal}'
 
 
 def test_tf_regeneration_script_imports_and_compares_without_tensorflow():

@@ -1,4 +1,4 @@
-"""Print the per-tag breakdown of a bench.py JSON line (DL4DS_BENCH_BREAKDOWN=1), largest first."""
+"""Print the per-tag breakdown of a `DL4DS_BENCH_BREAKDOWN=1 python bench.py --full` JSON line, largest first."""
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 b = d['breakdown']

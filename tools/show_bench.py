@@ -1,4 +1,4 @@
-"""Pretty-print a bench.py JSON line (with DL4DS_BENCH_BREAKDOWN=1)."""
+"""Pretty-print a bench.py JSON line (`DL4DS_BENCH_BREAKDOWN=1 python bench.py --full`)."""
 import json, sys
 d = json.load(open(sys.argv[1]))
 print('value %.1f %s  ms/step %.3f  cpu %s  gpu/cpu %s' % (d['value'], d['unit'], d['ms_per_step'], d.get('cpu_baseline'), d.get('gpu_over_cpu')))
