@@ -524,6 +524,12 @@ int dl4ds_metrics(const float* yt, const float* yp, int N, int H, int W, int C, 
     image_metrics(S(), yt, yp, N, H, W, C, pair_out_dev, grid_out_dev, range_out_dev, scratch(ws), ws);
     API_END
 }
+int dl4ds_spearman(const float* a, const float* b, size_t n_pairs, size_t L, size_t seg_stride, size_t elem_stride, double* out_dev) {
+    API_BEGIN
+    const size_t ws = spearman_workspace_bytes(n_pairs, L);
+    spearman(S(), a, b, n_pairs, L, seg_stride, elem_stride, out_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

@@ -123,6 +123,11 @@ void dwconv_wgrad(hipStream_t s, const float* x, const float* dy, float* dk, flo
 size_t metrics_workspace_bytes(int N, int H, int W, int C);
 void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int N, int H, int W, int C, float* pair_out_dev,
                    float* grid_out_dev, float* range_out_dev, float* workspace, size_t workspace_bytes);
+// Spearman rank correlation (rank.hip) of S pairs of length-L sequences, element k of pair s at [s*seg_stride + k*elem_stride]:
+// out[s] = scipy.stats.spearmanr(a_s, b_s)[0] in fp64 (average ranks of ties; NaN for a NaN, a constant side or L < 2)
+size_t spearman_workspace_bytes(size_t S, size_t L);
+void spearman(hipStream_t s, const float* a, const float* b, size_t S, size_t L, size_t seg_stride, size_t elem_stride, double* out,
+              void* workspace, size_t workspace_bytes);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

@@ -1,8 +1,6 @@
-"""compute_metrics of dl4ds/metrics.py:102-330 without the plotting: the per-pair and per-grid-point test metrics are
-reduced on the device (`dl4ds_metrics`), the summary statistics the reference prints are assembled here.  Spearman rank
-correlations are not computed (they need a sort per grid point / per pair; scipy on the returned arrays does that)."""
-import ctypes
-
+"""compute_metrics, compute_rmse and compute_correlation of dl4ds/metrics.py:15-330 without the plotting: the per-pair and
+per-grid-point test metrics are reduced on the device (`dl4ds_metrics`), Spearman rank correlations are computed by the
+segmented rank engine (`dl4ds_spearman`, csrc/rank.hip), the summary statistics the reference prints are assembled here."""
 import numpy as np
 
 from . import _lib
@@ -10,15 +8,17 @@ from .device import DeviceArray
 from .dataloader import checkarray_ndim
 
 
-def image_metrics(y_test, y_test_hat):
-    """Raw device reductions -> dict of arrays: per pair ``mae``, ``mse``, ``rmse``, ``psnr``, ``ssim``, ``pearson``; per grid
-    point ``rmse_map``, ``bias_map``, ``pearson_map``; ``drange``."""
+def _upload(y_test, y_test_hat):
+    """-> (y, p, dy, dp): both arrays as contiguous float32 (N, H, W, C) on the host and on the device."""
     y = np.ascontiguousarray(y_test, np.float32)
     p = np.ascontiguousarray(y_test_hat, np.float32)
     if y.shape != p.shape or y.ndim != 4:
         raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y.shape} and {p.shape}')
-    n, h, w, c = y.shape
-    dy, dp = DeviceArray.from_numpy(y), DeviceArray.from_numpy(p)
+    return y, p, DeviceArray.from_numpy(y), DeviceArray.from_numpy(p)
+
+
+def _device_metrics(dy, dp, shape):
+    n, h, w, c = shape
     pair, grid, rng = DeviceArray.zeros((n, 4)), DeviceArray.zeros((3, h, w, c)), DeviceArray.zeros((2,))
     _lib.check(_lib.lib().dl4ds_metrics(dy.ptr, dp.ptr, n, h, w, c, pair.ptr, grid.ptr, rng.ptr))
     pair, grid, rng = pair.numpy().astype(np.float64), grid.numpy(), rng.numpy().astype(np.float64)
@@ -30,11 +30,94 @@ def image_metrics(y_test, y_test_hat):
                 rmse_map=grid[0], bias_map=grid[1], pearson_map=grid[2], drange=drange)
 
 
+def _device_spearman(dy, dp, shape, over):
+    """Spearman rho in fp64 per test pair over all H*W*C values (``over='space'``, shape (N,)) or per grid point of channel 0
+    over the N pairs (``over='time'``, shape (H, W))."""
+    n, h, w, c = shape
+    if over == 'space':
+        segs, length, seg_stride, elem_stride, out_shape = n, h * w * c, h * w * c, 1, (n,)
+    elif over == 'time':
+        segs, length, seg_stride, elem_stride, out_shape = h * w, n, c, h * w * c, (h, w)
+    else:
+        raise ValueError(f"over must be 'time' or 'space', got {over!r}")
+    out = DeviceArray(out_shape, np.float64)
+    _lib.check(_lib.lib().dl4ds_spearman(dy.ptr, dp.ptr, segs, length, seg_stride, elem_stride, out.ptr))
+    return out.numpy()
+
+
+def image_metrics(y_test, y_test_hat):
+    """Raw device reductions -> dict of arrays: per pair ``mae``, ``mse``, ``rmse``, ``psnr``, ``ssim``, ``pearson``; per grid
+    point ``rmse_map``, ``bias_map``, ``pearson_map``; ``drange``."""
+    y, _, dy, dp = _upload(y_test, y_test_hat)
+    return _device_metrics(dy, dp, y.shape)
+
+
+def spearman(y, p, over='space'):
+    """scipy.stats.spearmanr(...)[0] of every test pair over all its H*W*C values (``over='space'``: float64 (N,)) or of every
+    grid point of channel 0 over the N pairs (``over='time'``: float64 (H, W)), on the device.  Ties get average ranks, -0.0
+    ties with +0.0; a NaN, a constant side or fewer than two values give NaN.  Inputs are (N, H, W, C), read as float32."""
+    y, _, dy, dp = _upload(y, p)
+    return _device_spearman(dy, dp, y.shape, over)
+
+
+def _map_dtype(y):
+    return y.dtype if np.issubdtype(y.dtype, np.floating) else np.dtype(np.float64)
+
+
+def _channel0_map(y, values):
+    """The reference's per-grid-point maps (metrics.py:35-45, 75-85): start from NaN and fill only the grid points where
+    ``y[0, :, :, 0]`` is non-zero, in the dtype of ``y``."""
+    out = np.full(y.shape[1:3], np.nan, dtype=_map_dtype(y))
+    sel = y[0, :, :, 0] != 0
+    out[sel] = values[sel]
+    return out
+
+
+def _check_over(over):
+    if over not in ('time', 'space'):
+        raise ValueError(f"over must be 'time' or 'space', got {over!r}")
+
+
+def compute_rmse(y, y_hat, over='time', squared=False, n_jobs=40):
+    """metrics.py:15-48 on the device (``n_jobs`` is accepted and ignored).  ``over='time'``: the per-grid-point MSE map of
+    channel 0, NaN where ``y[0, :, :, 0] == 0`` -- the reference's per-pixel helper calls mean_squared_error without
+    ``squared``, so this map is always the MSE.  ``over='space'``: a list of per-pair RMSE values (MSE if ``squared``)."""
+    _check_over(over)
+    y, y_hat = np.asarray(y), np.asarray(y_hat)
+    _, _, dy, dp = _upload(y, y_hat)
+    m = _device_metrics(dy, dp, y.shape)
+    if over == 'time':
+        return _channel0_map(y, m['rmse_map'][..., 0].astype(np.float64) ** 2)
+    return list(m['mse'] if squared else m['rmse'])
+
+
+def compute_correlation(y, y_hat, over='time', mode='spearman', n_jobs=40):
+    """metrics.py:51-97 on the device (``n_jobs`` is accepted and ignored).  ``over='time'``: the (H, W) map of channel 0 of
+    per-grid-point correlations over the pairs, NaN where ``y[0, :, :, 0] == 0``; ``over='space'``: a list with one
+    correlation per test pair over all its H*W*C values.  ``mode``: 'spearman' (scipy.stats.spearmanr) or 'pearson'
+    (scipy.stats.pearsonr)."""
+    if mode not in ('spearman', 'pearson'):
+        raise ValueError(f"mode must be 'spearman' or 'pearson', got {mode!r}")
+    _check_over(over)
+    y, y_hat = np.asarray(y), np.asarray(y_hat)
+    _, _, dy, dp = _upload(y, y_hat)
+    if mode == 'spearman':
+        vals = _device_spearman(dy, dp, y.shape, over)
+    else:
+        m = _device_metrics(dy, dp, y.shape)
+        vals = m['pearson'] if over == 'space' else m['pearson_map'][..., 0].astype(np.float64)
+    return list(vals) if over == 'space' else _channel0_map(y, vals)
+
+
 def compute_metrics(y_test, y_test_hat, dpi=150, plot_size_px=1000, n_jobs=-1, scaler=None, mask=None, save_path=None,
                     verbose=True):
     """Same preparation as the reference (squeeze 5-D, optional ``scaler.inverse_transform``, optional validity mask) and the
     same printed summary; returns ``(temp_rmse_map, temp_pearson_corrmap, nmeanbias)`` like metrics.py:326, plus the full
-    dictionary of per-pair / per-grid-point arrays as a fourth element."""
+    dictionary of per-pair / per-grid-point arrays as a fourth element (``spearman``: the per-pair Spearman correlations).
+    The arrays go to the device once; the reductions and the Spearman ranks share them.  With ``save_path`` the per-pair
+    RMSE, Spearman and Pearson values are also saved as metrics_{mse,spearcorr,pearcorr}_pergridpair.npy (metrics.py:188-250).
+    As in the reference (metrics.py:316), the 'Per-grid-point Spearman correlation' line reports the SPATIAL (per-pair)
+    Spearman values, the same numbers as 'Spatial Spearman correlation'."""
     y_test, y_test_hat = np.asarray(y_test), np.asarray(y_test_hat)
     if y_test.ndim == 5:
         y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
@@ -48,19 +131,25 @@ def compute_metrics(y_test, y_test_hat, dpi=150, plot_size_px=1000, n_jobs=-1, s
             mask = mask[..., None]
         y_test, y_test_hat = y_test * mask, y_test_hat * mask
         mask_nan = np.where(mask == 0, np.nan, 1.0)
-    m = image_metrics(y_test, y_test_hat)
+    y32, _, dy, dp = _upload(y_test, y_test_hat)
+    m = _device_metrics(dy, dp, y32.shape)
+    m['spearman'] = _device_spearman(dy, dp, y32.shape, 'space')
+    del dy, dp
     rmse_map, corr_map = m['rmse_map'].astype(np.float64), m['pearson_map'].astype(np.float64)
     nmeanbias = m['bias_map'].astype(np.float64) / (np.mean(y_test) * 100)            # metrics.py:219-220
     norm_rmse_map = rmse_map / (np.mean(y_test) * 100)
     if mask_nan is not None:
         rmse_map, corr_map, nmeanbias, norm_rmse_map = (a * mask_nan for a in (rmse_map, corr_map, nmeanbias, norm_rmse_map))
+    spear = (np.mean(m['spearman']), np.std(m['spearman']))
     summary = {
         'PSNR': (np.mean(m['psnr']), np.std(m['psnr'])), 'SSIM': (np.mean(m['ssim']), np.std(m['ssim'])),
         'MAE': (np.mean(m['mae']), np.std(m['mae'])),
         'Per-grid-point RMSE': (np.nanmean(rmse_map), np.nanstd(rmse_map)),
         'Per-grid-point nRMSE': (np.nanmean(norm_rmse_map), np.nanstd(norm_rmse_map)),
+        'Per-grid-point Spearman correlation': spear,                                      # metrics.py:316: the spatial values
         'Per-grid-point Pearson correlation': (np.nanmean(corr_map), np.nanstd(corr_map)),
         'Spatial MSE': (np.mean(m['rmse']), np.std(m['rmse'])),
+        'Spatial Spearman correlation': spear,
         'Spatial Pearson correlation': (np.mean(m['pearson']), np.std(m['pearson'])),
     }
     m['summary'] = summary
@@ -68,6 +157,8 @@ def compute_metrics(y_test, y_test_hat, dpi=150, plot_size_px=1000, n_jobs=-1, s
         lines = ['Metrics on y_test and y_test_hat:\n'] + [f'{k} \tmu = {a} \tsigma = {b}' for k, (a, b) in summary.items()]
         if save_path is not None:
             import os
+            for name, key in (('mse', 'rmse'), ('spearcorr', 'spearman'), ('pearcorr', 'pearson')):
+                np.save(os.path.join(save_path, f'metrics_{name}_pergridpair.npy'), m[key])
             with open(os.path.join(save_path, 'metrics_summary.txt'), 'a') as f:
                 f.write('\n'.join(lines) + '\n')
         elif verbose:

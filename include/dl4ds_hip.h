@@ -147,6 +147,14 @@ int dl4ds_op_loss(int kind, const float* y_true_dev, const float* y_pred_dev, fl
  *   range_out_dev [2]          joint (min, max) of both arrays (metrics.py:166) */
 int dl4ds_metrics(const float* y_true_dev, const float* y_pred_dev, int N, int H, int W, int C, float* pair_out_dev,
                   float* grid_out_dev, float* range_out_dev);
+/* Spearman rank correlation of compute_correlation (metrics.py:51-97), scipy.stats.spearmanr semantics on 1-D inputs: for every
+ * pair s < S, out_dev[s] (fp64) = Pearson correlation of the average ranks (ties share the mean of their positions; -0.0 ties
+ * with +0.0) of the two length-L sequences whose element k lives at a_dev / b_dev [s*seg_stride + k*elem_stride]; NaN when
+ * either sequence holds a NaN (nan_policy='propagate'), is constant, or L < 2.  Per test pair: S = N, L = H*W*C,
+ * seg_stride = L, elem_stride = 1; per grid point of channel 0: S = H*W, L = N, seg_stride = C, elem_stride = H*W*C.
+ * Bitwise reproducible.  L < 2^28. */
+int dl4ds_spearman(const float* a_dev, const float* b_dev, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
+                   double* out_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
