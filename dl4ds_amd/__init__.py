@@ -34,6 +34,7 @@ def __getattr__(name):
     import importlib
     lazy = {'SupervisedTrainer': '.training', 'CGANTrainer': '.training', 'Predictor': '.inference', 'compute_metrics': '.metrics',
             'compute_rmse': '.metrics', 'compute_correlation': '.metrics',
+            'StandardScaler': '.preprocessing', 'MinMaxScaler': '.preprocessing',
             'predict': '.inference', 'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',

@@ -530,6 +530,29 @@ int dl4ds_spearman(const float* a, const float* b, size_t n_pairs, size_t L, siz
     spearman(S(), a, b, n_pairs, L, seg_stride, elem_stride, out_dev, ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_scaler_cells(const size_t* shape, int ndim, const int* reduce, size_t* cells_out) {
+    API_BEGIN
+    *cells_out = scaler_cells(shape, ndim, reduce);
+    API_END
+}
+int dl4ds_scaler_stats_workspace_bytes(const size_t* shape, int ndim, const int* reduce, int is_double, size_t* bytes_out) {
+    API_BEGIN
+    *bytes_out = scaler_stats_workspace_bytes(shape, ndim, reduce, is_double);
+    API_END
+}
+int dl4ds_scaler_stats(const void* x, int is_double, const size_t* shape, int ndim, const int* reduce, double* out_dev,
+                       unsigned* nan_flag_dev, unsigned* mask_bits_dev) {
+    API_BEGIN
+    const size_t ws = scaler_stats_workspace_bytes(shape, ndim, reduce, is_double);
+    scaler_stats(S(), x, is_double, shape, ndim, reduce, out_dev, nan_flag_dev, mask_bits_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_scaler_apply(const void* x, void* out, int is_double, const size_t* shape, int ndim, const int* reduce, int op1,
+                       const void* a_dev, int op2, const void* b_dev, int nan_mode, double fill, const unsigned* mask_bits_dev) {
+    API_BEGIN
+    scaler_apply(S(), x, out, is_double, shape, ndim, reduce, op1, a_dev, op2, b_dev, nan_mode, fill, mask_bits_dev);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

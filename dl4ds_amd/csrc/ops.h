@@ -128,6 +128,20 @@ void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int 
 size_t spearman_workspace_bytes(size_t S, size_t L);
 void spearman(hipStream_t s, const float* a, const float* b, size_t S, size_t L, size_t seg_stride, size_t elem_stride, double* out,
               void* workspace, size_t workspace_bytes);
+// MinMaxScaler / StandardScaler of preprocessing.py (scaler.hip).  shape / reduce describe a C-contiguous array of ndim axes and
+// which of them are reduced (reduce[i] != 0); float or double data.  scaler_stats: out [5][cells] fp64 = count, min, max, mean,
+// population std per kept cell, NaNs skipped (an empty cell: count 0, NaN); *nan_flag = 1 if any NaN was seen; mask_bits (optional)
+// = the NaN mask, bit e%32 of word e/32 for flat element e ((n + 31) / 32 words).  Bitwise reproducible.
+// scaler_apply: out[e] = op2(op1(x[e], a[cell(e)]), b[cell(e)]), each operation rounded on its own in the array's type, then
+// NaN -> fill (SCALER_NAN_FILL) or NaN where the mask bit is set (SCALER_NAN_MASK, mask_bits may be null); out may be x.
+enum ScalerOp { SCALER_OP_NONE = 0, SCALER_OP_MUL = 1, SCALER_OP_ADD = 2, SCALER_OP_SUB = 3, SCALER_OP_DIV = 4 };
+enum ScalerNan { SCALER_NAN_FILL = 0, SCALER_NAN_MASK = 1 };
+size_t scaler_cells(const size_t* shape, int ndim, const int* reduce);
+size_t scaler_stats_workspace_bytes(const size_t* shape, int ndim, const int* reduce, int is_double);
+void scaler_stats(hipStream_t s, const void* x, int is_double, const size_t* shape, int ndim, const int* reduce, double* out,
+                  unsigned* nan_flag, unsigned* mask_bits, void* workspace, size_t workspace_bytes);
+void scaler_apply(hipStream_t s, const void* x, void* out, int is_double, const size_t* shape, int ndim, const int* reduce, int op1,
+                  const void* a, int op2, const void* b, int nan_mode, double fill, const unsigned* mask_bits);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

@@ -155,6 +155,25 @@ int dl4ds_metrics(const float* y_true_dev, const float* y_pred_dev, int N, int H
  * Bitwise reproducible.  L < 2^28. */
 int dl4ds_spearman(const float* a_dev, const float* b_dev, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
                    double* out_dev);
+/* MinMaxScaler / StandardScaler -- preprocessing.py:78-117 (MinMaxScaler.partial_fit: nan mask, np.nanmin / np.nanmax),
+ * :247-283 (StandardScaler.partial_fit: np.nanmean / np.nanstd), :120-167 and :285-334 (transform / inverse_transform).
+ * x_dev: a C-contiguous device array of ndim <= 8 axes (host arrays shape[ndim], reduce[ndim]; reduce[i] != 0: axis i is
+ * reduced), float (is_double = 0) or double; after dropping size-1 axes and merging neighbours of one kind at most five groups.
+ * dl4ds_scaler_stats: ONE read of x.  out_dev [5][cells] fp64, cells = product of the kept extents in C order (keepdims layout):
+ *   count of non-NaN values, min, max, mean, population standard deviation (ddof 0) of every kept cell with NaNs skipped; an
+ *   all-NaN cell gives count 0 and NaN.  nan_flag_dev [1]: 1 if any element was NaN.  mask_bits_dev (or null): the NaN mask,
+ *   bit e%32 of word e/32 for flat element e, (n + 31) / 32 words.  fp64 accumulation, no floating-point atomics: bitwise
+ *   reproducible.
+ * dl4ds_scaler_apply: out[e] = op2(op1(x[e], a[cell(e)]), b[cell(e)]) in the array's own type, every operation rounded on its own
+ *   like numpy's in-place `*=`, `+=`, `-=`, `/=` (op: 0 none, 1 multiply, 2 add, 3 subtract, 4 divide; a_dev / b_dev [cells] in
+ *   the array's type, null for op 0); then nan_mode 0: NaN -> fill (np.nan_to_num(nan=fillnanto)), nan_mode 1: NaN where the bit
+ *   of mask_bits_dev (or null) is set (X[nan_mask] = np.nan).  out_dev may be x_dev. */
+int dl4ds_scaler_cells(const size_t* shape, int ndim, const int* reduce, size_t* cells_out);
+int dl4ds_scaler_stats_workspace_bytes(const size_t* shape, int ndim, const int* reduce, int is_double, size_t* bytes_out);
+int dl4ds_scaler_stats(const void* x_dev, int is_double, const size_t* shape, int ndim, const int* reduce, double* out_dev,
+                       unsigned* nan_flag_dev, unsigned* mask_bits_dev);
+int dl4ds_scaler_apply(const void* x_dev, void* out_dev, int is_double, const size_t* shape, int ndim, const int* reduce, int op1,
+                       const void* a_dev, int op2, const void* b_dev, int nan_mode, double fill, const unsigned* mask_bits_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
