@@ -35,7 +35,8 @@ def __getattr__(name):
     lazy = {'SupervisedTrainer': '.training', 'CGANTrainer': '.training', 'Predictor': '.inference', 'compute_metrics': '.metrics',
             'compute_rmse': '.metrics', 'compute_correlation': '.metrics',
             'StandardScaler': '.preprocessing', 'MinMaxScaler': '.preprocessing',
-            'predict': '.inference', 'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
+            'predict': '.inference', 'predict_ensemble': '.inference', 'EnsemblePredictor': '.inference',
+            'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',
             'crop_array': '.dataloader', 'resize_array': '.dataloader', 'checkarray_ndim': '.dataloader',

@@ -140,7 +140,13 @@ int dl4ds_device_name(char* buf, int buflen) {
 int dl4ds_malloc(void** p, size_t bytes) {
     API_BEGIN
     rt_ensure_init();
-    HIP_CHECK(hipMalloc(p, bytes > 0 ? bytes : 4));
+    const hipError_t e = hipMalloc(p, bytes > 0 ? bytes : 4);
+    if (e != hipSuccess) {
+        // a refused allocation is reported here and nowhere else: the runtime also keeps it as the thread's "last error", where
+        // the hipGetLastError() after the next kernel launch would find it and blame that launch
+        (void)hipGetLastError();
+        throw Dl4dsError(std::string("HIP error: ") + hipGetErrorString(e) + " (hipMalloc of " + std::to_string(bytes) + " bytes)");
+    }
     API_END
 }
 int dl4ds_free(void* p) {
@@ -163,7 +169,11 @@ int dl4ds_memcpy_d2h(void* dst, const void* src, size_t bytes) {
 int dl4ds_host_register(void* p, size_t bytes) {
     API_BEGIN
     DL4DS_REQUIRE(p && bytes, "host_register: empty range");
-    HIP_CHECK(hipHostRegister(p, bytes, hipHostRegisterDefault));
+    const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();           // (callers go on with pageable copies: the refusal must not surface at the next launch)
+        throw Dl4dsError(std::string("HIP error: ") + hipGetErrorString(e) + " (hipHostRegister)");
+    }
     API_END
 }
 int dl4ds_host_unregister(void* p) {
@@ -553,6 +563,12 @@ int dl4ds_scaler_apply(const void* x, void* out, int is_double, const size_t* sh
     scaler_apply(S(), x, out, is_double, shape, ndim, reduce, op1, a_dev, op2, b_dev, nan_mode, fill, mask_bits_dev);
     API_END
 }
+int dl4ds_ensemble_reduce(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
+                          float* mean_dev, float* std_dev, float* min_dev, float* max_dev, float* quant_dev) {
+    API_BEGIN
+    ensemble_reduce(S(), members_dev, K, n, member_stride, q_host, nq, mean_dev, std_dev, min_dev, max_dev, quant_dev);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);
@@ -737,6 +753,24 @@ int dl4ds_graph_dropout_variant(dl4ds_graph* g, int in, float rate, int variant,
 int dl4ds_graph_dropout_count(dl4ds_graph* g, int* n) {
     API_BEGIN
     *n = (int)g->g.dropout_ops.size();
+    API_END
+}
+int dl4ds_graph_dropout_reseed(dl4ds_graph* g, unsigned long long seed) {
+    API_BEGIN
+    for (size_t i = 0; i < g->g.dropout_ops.size(); ++i) {
+        // splitmix64 of (seed, op index): neighbouring seeds and neighbouring ops get unrelated streams
+        unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1);
+        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+        g->g.dropout_ops[i]->reseed(z ^ (z >> 31));
+    }
+    API_END
+}
+int dl4ds_graph_dropout_mc_count(dl4ds_graph* g, int* n) {
+    API_BEGIN
+    int c = 0;
+    for (GOp* op : g->g.dropout_ops) c += op->mc_active() ? 1 : 0;
+    *n = c;
     API_END
 }
 static GOp* dropout_op(dl4ds_graph* g, int index, int B) {

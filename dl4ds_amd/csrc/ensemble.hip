@@ -1,0 +1,286 @@
+// Member statistics of an MC-dropout ensemble (the MCDropout / MCGaussianDropout / MCSpatialDropout layers of blocks.py:658-676 stay
+// active at inference so that K forward passes form an ensemble): ONE read of the member stack members[K][n] gives, per element,
+// mean, population std, min, max and nq linearly interpolated quantiles.  DESIGN.md section 12.
+//
+// A thread owns VEC consecutive elements and holds all K values of each in registers: KP * VEC floats, KP = K rounded up to a power
+// of two (missing rows are +inf, which a sort leaves behind the K real values).  VEC shrinks as K grows so that the live set stays at
+// 64 data registers: K <= 16: 4 elements (16-byte loads per member row), K <= 32: 2, K <= 64: 1, and every load of a thread (up to
+// 64) is issued before the first use.
+// K in 65 ... 256 takes the staged kernel: a wave keeps the K values of 64 elements in LDS (one column per lane: conflict-free),
+// each lane sorts its own column in place with a looped bitonic network.  Only correctness is asked of that path.
+//
+// Arithmetic (what numpy does on the fp64 copy of the stack, np.mean / np.std / np.min / np.max / np.quantile along axis 0):
+//   mean  = (sum_k x_k) / K, std = sqrt((sum_k (x_k - mean)^2) / K): sequential fp64 sums in member order, product and sum rounded
+//           separately, ONE rounding to fp32 at the end.  No state in memory, no atomics: a repeated call gives the same bits.
+//   quantile q: pos = (K - 1) q.  pos >= K - 1: a = b = the largest value, t = pos + 1; else a, b = order statistics floor(pos) and
+//           floor(pos) + 1, t = pos - floor(pos).  d = b - a; result = t >= 0.5 ? b - d (1 - t) : a + d t, in fp64 on the two fp32
+//           values, rounded once.  (numpy's _lerp: the second form is what decides between inf and NaN next to an infinite value.)
+//   A NaN among the K values makes every output of that element NaN; infinities give what the formulas give (std NaN).
+#include "common.h"
+#include "ops.h"
+#include "prof.h"
+#include <cmath>
+#include <cstdint>
+
+// numpy rounds (x - mean)^2 and the running sum separately, and d * t and the sum of the interpolation too
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int ENS_THREADS = 256;
+constexpr int ENS_STAGED_THREADS = 64;      // one wave: a lane's column is private, no barrier anywhere
+
+struct EnsQ {
+    int lo[ENS_MAX_QUANTILES], hi[ENS_MAX_QUANTILES];
+    double t[ENS_MAX_QUANTILES];
+};
+
+struct EnsOut { float *mean, *std, *mn, *mx, *quant; };
+
+__device__ __forceinline__ float ens_nan() { return __builtin_nanf(""); }
+
+__device__ __forceinline__ double ens_lerp(float a, float b, double t) {
+    const double da = (double)a, db = (double)b;
+    const double d = db - da;
+    return t >= 0.5 ? db - d * (1.0 - t) : da + d * t;
+}
+
+// VEC results of one statistic -> p[e0 .. e0 + VEC) as one 4 / 8 / 16-byte store (the host checked alignment and n % VEC == 0)
+template <int VEC>
+__device__ __forceinline__ void ens_store(float* p, const float (&r)[VEC]) {
+    if (!p) return;
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else if constexpr (VEC == 2) *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]);
+    else p[0] = r[0];
+}
+
+// ------------------------------------------------------------------------------------------------ K <= 64: registers
+// n % VEC == 0, member_stride % VEC == 0 and every pointer aligned to VEC floats (else the host takes the VEC = 1 instance).
+// FULL: K == KP (the powers of two): no padding and no predication at all.
+template <int KP, int VEC, bool FULL>
+__global__ void __launch_bounds__(ENS_THREADS) ensemble_reduce_reg(const float* __restrict__ members, int K, size_t n, size_t stride,
+                                                                   EnsQ q, int nq, EnsOut out) {
+    const size_t blk = (size_t)blockIdx.x * (ENS_THREADS * VEC);       // uniform: the row pointers stay scalar,
+    const unsigned off = threadIdx.x * VEC;                             // the lane's part is one 32-bit offset
+    if (blk + off >= n) return;
+    float v[KP][VEC];
+    // Branch-free: every row's load is issued before anything is used.  Rows k >= K re-read row K - 1 (a cache hit, no HBM traffic;
+    // none when K is a power of two) and are then replaced by +inf.
+    const float* row = members + blk;
+#pragma unroll
+    for (int k = 0; k < KP; ++k) {
+        if constexpr (VEC == 4) {
+            const float4 x = *reinterpret_cast<const float4*>(row + off);
+            v[k][0] = x.x; v[k][1] = x.y; v[k][2] = x.z; v[k][3] = x.w;
+        } else if constexpr (VEC == 2) {
+            const float2 x = *reinterpret_cast<const float2*>(row + off);
+            v[k][0] = x.x; v[k][1] = x.y;
+        } else {
+            v[k][0] = row[off];
+        }
+        row += (FULL || k + 1 < K) ? stride : 0;
+    }
+    if constexpr (!FULL) {
+#pragma unroll
+        for (int k = 1; k < KP; ++k) {
+#pragma unroll
+            for (int c = 0; c < VEC; ++c) v[k][c] = k < K ? v[k][c] : __builtin_inff();
+        }
+    }
+
+    float r_mean[VEC], r_std[VEC], r_mn[VEC], r_mx[VEC];
+    bool isnan_[VEC];
+#pragma unroll
+    for (int c = 0; c < VEC; ++c) {
+        double s = 0.0;
+        float mn = v[0][c], mx = v[0][c];
+        bool bad = false;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {          // (uniform selects, no control flow: the values stay in registers)
+            const bool in = FULL || k < K;
+            const float x = v[k][c];
+            const double s1 = s + (double)x;
+            s = in ? s1 : s;
+            mn = (in && x < mn) ? x : mn;
+            mx = (in && x > mx) ? x : mx;
+            bad = bad || (x != x);                // (the padding is +inf, never NaN)
+        }
+        const double mean = s / (double)K;
+        double m2 = 0.0;
+#pragma unroll
+        for (int k = 0; k < KP; ++k) {
+            float x = v[k][c];
+            asm("" : "+v"(x));                    // converted again, not kept: 2 K fp64 registers would halve the occupancy
+            const double d = (double)x - mean;
+            const double m1 = m2 + d * d;
+            m2 = (FULL || k < K) ? m1 : m2;
+        }
+        isnan_[c] = bad;
+        r_mean[c] = bad ? ens_nan() : (float)mean;
+        r_std[c] = bad ? ens_nan() : (float)sqrt(m2 / (double)K);
+        r_mn[c] = bad ? ens_nan() : mn;
+        r_mx[c] = bad ? ens_nan() : mx;
+    }
+    const size_t e0 = blk + off;
+    ens_store<VEC>(out.mean ? out.mean + e0 : nullptr, r_mean);
+    ens_store<VEC>(out.std ? out.std + e0 : nullptr, r_std);
+    ens_store<VEC>(out.mn ? out.mn + e0 : nullptr, r_mn);
+    ens_store<VEC>(out.mx ? out.mx + e0 : nullptr, r_mx);
+
+    if (nq <= 0) return;
+    // bitonic network on the KP register values of each element: every index is a compile-time constant after unrolling
+#pragma unroll
+    for (int size = 2; size <= KP; size <<= 1) {
+#pragma unroll
+        for (int j = size >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int i = 0; i < KP; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const bool up = (i & size) == 0;
+#pragma unroll
+                    for (int c = 0; c < VEC; ++c) {
+                        const float a = v[i][c], b = v[l][c];
+                        const float lo = fminf(a, b), hi = fmaxf(a, b);
+                        v[i][c] = up ? lo : hi;
+                        v[l][c] = up ? hi : lo;
+                    }
+                }
+            }
+        }
+    }
+    for (int j = 0; j < nq; ++j) {
+        const int lo = q.lo[j], hi = q.hi[j];
+        const double t = q.t[j];
+        float r[VEC];
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) {
+            float a = v[0][c], b = v[0][c];
+#pragma unroll
+            for (int k = 1; k < KP; ++k) {        // (lo, hi are uniform: selects on a scalar condition, no indexed register file)
+                a = k == lo ? v[k][c] : a;
+                b = k == hi ? v[k][c] : b;
+            }
+            r[c] = isnan_[c] ? ens_nan() : (float)ens_lerp(a, b, t);
+        }
+        ens_store<VEC>(out.quant + (size_t)j * n + e0, r);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ 64 < K <= 256: LDS columns
+__global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_reduce_staged(const float* __restrict__ members, int K, int KP, size_t n,
+                                                                             size_t stride, EnsQ q, int nq, EnsOut out) {
+    extern __shared__ float col[];            // [KP][64]
+    const int lane = threadIdx.x;
+    const size_t e = (size_t)blockIdx.x * ENS_STAGED_THREADS + lane;
+    if (e >= n) return;                       // (no barrier below: a lane only ever touches its own column)
+    float* s = col + lane;
+    double sum = 0.0;
+    float mn = __builtin_inff(), mx = -__builtin_inff();
+    bool bad = false;
+    for (int k = 0; k < K; ++k) {
+        const float x = members[(size_t)k * stride + e];
+        s[k * ENS_STAGED_THREADS] = x;
+        sum += (double)x;
+        mn = x < mn ? x : mn;
+        mx = x > mx ? x : mx;
+        bad = bad || (x != x);
+    }
+    for (int k = K; k < KP; ++k) s[k * ENS_STAGED_THREADS] = __builtin_inff();
+    const double mean = sum / (double)K;
+    double m2 = 0.0;
+    for (int k = 0; k < K; ++k) {
+        const double d = (double)s[k * ENS_STAGED_THREADS] - mean;
+        m2 += d * d;
+    }
+    if (out.mean) out.mean[e] = bad ? ens_nan() : (float)mean;
+    if (out.std) out.std[e] = bad ? ens_nan() : (float)sqrt(m2 / (double)K);
+    if (out.mn) out.mn[e] = bad ? ens_nan() : mn;
+    if (out.mx) out.mx[e] = bad ? ens_nan() : mx;
+    if (nq <= 0 || !out.quant) return;
+    for (int size = 2; size <= KP; size <<= 1)
+        for (int j = size >> 1; j > 0; j >>= 1)
+            for (int i = 0; i < KP; ++i) {
+                const int l = i ^ j;
+                if (l > i) {
+                    const float a = s[i * ENS_STAGED_THREADS], b = s[l * ENS_STAGED_THREADS];
+                    const float lo = fminf(a, b), hi = fmaxf(a, b);
+                    const bool up = (i & size) == 0;
+                    s[i * ENS_STAGED_THREADS] = up ? lo : hi;
+                    s[l * ENS_STAGED_THREADS] = up ? hi : lo;
+                }
+            }
+    for (int j = 0; j < nq; ++j) {
+        const float a = s[q.lo[j] * ENS_STAGED_THREADS], b = s[q.hi[j] * ENS_STAGED_THREADS];
+        out.quant[(size_t)j * n + e] = bad ? ens_nan() : (float)ens_lerp(a, b, q.t[j]);
+    }
+}
+
+template <int KP, int VEC>
+void launch_reg_v(hipStream_t s, const float* members, int K, size_t n, size_t stride, const EnsQ& q, int nq, const EnsOut& out) {
+    if constexpr (VEC > 1) {
+        // vector loads / stores need whole, aligned groups in every row; otherwise one element per lane (still coalesced)
+        auto aligned = [](const void* p) { return ((uintptr_t)p % (sizeof(float) * VEC)) == 0; };
+        if (n % VEC || stride % VEC || !aligned(members) || !aligned(out.mean) || !aligned(out.std) || !aligned(out.mn) ||
+            !aligned(out.mx) || !aligned(out.quant))
+            return launch_reg_v<KP, 1>(s, members, K, n, stride, q, nq, out);
+    }
+    const size_t blocks = cdivz(n, (size_t)ENS_THREADS * VEC);
+    DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_reduce: too many elements for one launch");
+    if (K == KP)
+        DL4DS_LAUNCH((ensemble_reduce_reg<KP, VEC, true>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, q,
+                     nq, out);
+    else
+        DL4DS_LAUNCH((ensemble_reduce_reg<KP, VEC, false>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, q,
+                     nq, out);
+}
+template <int KP, int VEC>
+void launch_reg(hipStream_t s, const float* members, int K, size_t n, size_t stride, const EnsQ& q, int nq, const EnsOut& out) {
+    launch_reg_v<KP, VEC>(s, members, K, n, stride, q, nq, out);
+}
+
+}  // namespace
+
+void ensemble_reduce(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
+                     float* mean, float* std_, float* mn, float* mx, float* quant) {
+    DL4DS_REQUIRE(K >= 1 && K <= ENS_MAX_MEMBERS, "ensemble_reduce: 1 <= K <= 256 members");
+    DL4DS_REQUIRE(nq >= 0 && nq <= ENS_MAX_QUANTILES, "ensemble_reduce: at most 32 quantiles per call");
+    DL4DS_REQUIRE(nq == 0 || q_host, "ensemble_reduce: nq > 0 without probabilities");
+    if (n == 0) return;
+    DL4DS_REQUIRE(members, "ensemble_reduce: null member stack");
+    DL4DS_REQUIRE(member_stride >= n, "ensemble_reduce: member stride smaller than the member");
+    EnsQ q{};
+    for (int j = 0; j < nq; ++j) {
+        const double p = (double)q_host[j];
+        DL4DS_REQUIRE(p >= 0.0 && p <= 1.0, "ensemble_reduce: quantile probabilities must be in [0, 1]");
+        const double pos = (double)(K - 1) * p;
+        if (pos >= (double)(K - 1)) {
+            q.lo[j] = q.hi[j] = (int)K - 1;
+            q.t[j] = pos + 1.0;                   // numpy: previous index -1 (the last element), gamma = pos - (-1)
+        } else {
+            const double f = std::floor(pos);
+            q.lo[j] = (int)f;
+            q.hi[j] = (int)f + 1;
+            q.t[j] = pos - f;
+        }
+    }
+    if (!quant) nq = 0;
+    const EnsOut out{mean, std_, mn, mx, quant};
+    const int k = (int)K;
+    ProfScope ps(s, "ensemble_reduce", (double)n * (4.0 * K), (double)n * 4.0 * (double)(K + 4 + nq));
+    if (k <= 2) launch_reg<2, 4>(s, members, k, n, member_stride, q, nq, out);
+    else if (k <= 4) launch_reg<4, 4>(s, members, k, n, member_stride, q, nq, out);
+    else if (k <= 8) launch_reg<8, 4>(s, members, k, n, member_stride, q, nq, out);
+    else if (k <= 16) launch_reg<16, 4>(s, members, k, n, member_stride, q, nq, out);
+    else if (k <= 32) launch_reg<32, 2>(s, members, k, n, member_stride, q, nq, out);
+    else if (k <= 64) launch_reg<64, 1>(s, members, k, n, member_stride, q, nq, out);
+    else {
+        const int kp = k <= 128 ? 128 : 256;
+        const size_t blocks = cdivz(n, ENS_STAGED_THREADS);
+        DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_reduce: too many elements for one launch");
+        const size_t lds = (size_t)kp * ENS_STAGED_THREADS * sizeof(float);        // 32 KB / 64 KB
+        DL4DS_LAUNCH(ensemble_reduce_staged, dim3((unsigned)blocks), dim3(ENS_STAGED_THREADS), lds, s, members, k, kp, n,
+                     member_stride, q, nq, out);
+    }
+    HIP_CHECK(hipGetLastError());
+}

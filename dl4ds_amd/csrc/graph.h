@@ -80,6 +80,8 @@ struct GOp {
     virtual void set_batch_groups(int groups) {}
     virtual bool set_mask(Graph& g, const float* host, size_t n) { return false; }   // dropout keep-mask injection
     virtual size_t mask_floats(Graph& g, int B) { return 0; }                         // size of the mask of the last forward
+    virtual void reseed(unsigned long long seed) {}                                   // dropout: new noise seed, draw counter back to 0
+    virtual bool mc_active() const { return false; }                                  // dropout that stays active at inference
     const char* kind = "op";
     virtual std::string describe_fusion(Graph& g) { return ""; }
     // >= 0: the tensor this op writes THROUGH A VIEW (so it may live inside a Concatenate's buffer, GTensor::alias_of)

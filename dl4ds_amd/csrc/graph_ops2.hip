@@ -341,6 +341,8 @@ struct DropoutOp : GOp {
         g.tensors[in].grad_written = true;
     }
     unsigned long long seed = 0x5DEECE66Dull;
+    void reseed(unsigned long long s) override { seed = s; counter = 0; }
+    bool mc_active() const override { return mc && rate > 0.f; }
 };
 
 }  // namespace

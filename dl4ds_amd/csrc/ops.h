@@ -142,6 +142,12 @@ void scaler_stats(hipStream_t s, const void* x, int is_double, const size_t* sha
                   unsigned* nan_flag, unsigned* mask_bits, void* workspace, size_t workspace_bytes);
 void scaler_apply(hipStream_t s, const void* x, void* out, int is_double, const size_t* shape, int ndim, const int* reduce, int op1,
                   const void* a, int op2, const void* b, int nan_mode, double fill, const unsigned* mask_bits);
+// Member statistics of an MC-dropout ensemble (ensemble.hip): one read of members[K][n] (row k at members + k * member_stride) ->
+// per element mean, population std, min, max and quant[j][e] = np.quantile(q[j], method='linear') over the K values, evaluated as
+// numpy does on the fp64 copy of the stack and rounded to fp32 once.  Any output may be null.  Bitwise reproducible.
+constexpr int ENS_MAX_MEMBERS = 256, ENS_MAX_QUANTILES = 32;
+void ensemble_reduce(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
+                     float* mean, float* std_, float* mn, float* mx, float* quant);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

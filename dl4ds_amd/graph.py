@@ -331,6 +331,17 @@ class GraphBuilder:
         _lib.check(self._l.dl4ds_graph_dropout_get_mask(self.h, int(index), int(batch), out.ctypes.data))
         return out
 
+    def dropout_mc_count(self):
+        """Dropout ops that stay active at inference (the MC* variants with rate > 0)."""
+        n = ctypes.c_int()
+        _lib.check(self._l.dl4ds_graph_dropout_mc_count(self.h, ctypes.byref(n)))
+        return n.value
+
+    def reseed_dropout(self, seed):
+        """Every dropout op: seed = mix(seed, op index), draw counter = 0 (include/dl4ds_hip.h)."""
+        seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        _lib.check(self._l.dl4ds_graph_dropout_reseed(self.h, seed - (1 << 64) if seed >> 63 else seed))
+
     def set_dropout_mask(self, index, batch, mask):
         n = ctypes.c_size_t()
         _lib.check(self._l.dl4ds_graph_dropout_mask_size(self.h, int(index), int(batch), ctypes.byref(n)))
@@ -392,6 +403,36 @@ class GraphBuilder:
         fn = self._l.dl4ds_graph_get_grad if grad else self._l.dl4ds_graph_get_param
         _lib.check(fn(self.h, p['pid'], out.ctypes.data))
         return out
+
+
+ENSEMBLE_MAX_MEMBERS = 256        # ENS_MAX_MEMBERS / ENS_MAX_QUANTILES of csrc/ops.h
+ENSEMBLE_MAX_QUANTILES = 32
+
+
+def check_ensemble_args(n_members, quantiles, seed=None, batch_size=None):
+    """Arguments of ``predict_ensemble`` -> (n_members as int, probabilities as a float32 array).  Raises ValueError for anything
+    else; looks at its arguments only (no library, no device)."""
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+    if not is_int(n_members):
+        raise ValueError(f'`n_members` must be an integer, got {n_members!r}')
+    if not 1 <= n_members <= ENSEMBLE_MAX_MEMBERS:
+        raise ValueError(f'`n_members` must be in [1, {ENSEMBLE_MAX_MEMBERS}], got {n_members}')
+    try:
+        q = np.asarray(quantiles, np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'`quantiles` must be a sequence of probabilities, got {quantiles!r}') from None
+    if q.ndim == 0:
+        q = q.reshape(1)
+    if q.ndim != 1 or not np.all((q >= 0.0) & (q <= 1.0)):          # (a NaN fails both comparisons)
+        raise ValueError(f'`quantiles` must be a flat sequence of probabilities in [0, 1], got {quantiles!r}')
+    if q.size > ENSEMBLE_MAX_QUANTILES:
+        raise ValueError(f'at most {ENSEMBLE_MAX_QUANTILES} quantiles per call, got {q.size}')
+    if seed is not None and not is_int(seed):
+        raise ValueError(f'`seed` must be None or an integer, got {seed!r}')
+    if batch_size is not None and (not is_int(batch_size) or batch_size < 1):
+        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    return int(n_members), q.astype(np.float32)
 
 
 class Model:
@@ -486,6 +527,83 @@ class Model:
             if pinned:
                 lib.dl4ds_host_unregister(out.ctypes.data)
         return out
+
+    # --- MC-dropout ensembles (the MC* dropout variants of blocks.py:658-676 stay active at inference)
+    def reseed_dropout(self, seed):
+        """Seed the dropout noise of this model's graph: the masks of the forward passes that follow (at a fixed batch size)
+        are a function of ``seed`` alone.  A model that is never reseeded keeps its built-in seeds."""
+        self.graph.reseed_dropout(seed)
+
+    def predict_ensemble(self, inputs, n_members, batch_size=32, quantiles=(), seed=None, return_members=False):
+        """``n_members`` stochastic forward passes per sample, reduced on the device (csrc/ensemble.hip): a dict with 'mean',
+        'std' (population), 'min', 'max' of shape (N,) + output_shape, 'quantiles' of shape (len(quantiles), N) + output_shape
+        (np.quantile's default 'linear' method; at most 32 probabilities, taken in float32) and, with ``return_members``,
+        'members' (n_members, N) + output_shape.  All float32.
+
+        Per batch the inputs are uploaded once, the members are written into one device stack and only the statistics come
+        back.  The result is a function of (weights, inputs, n_members, batch_size, seed): the masks depend on how the samples
+        are split into batches, so a stack that does not fit raises MemoryError instead of being re-chunked.  ``seed=None``:
+        the graph's noise counters simply continue."""
+        n_members, q = check_ensemble_args(n_members, quantiles, seed, batch_size)
+        if isinstance(inputs, np.ndarray):
+            inputs = [inputs]
+        first = np.asarray(inputs[0])
+        grid = tuple(first.shape[-3:-1])
+        if grid != tuple(self.input_shapes[0][-3:-1]):
+            return self.resized(grid).predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
+                                                       return_members=return_members)
+        from .device import DeviceArray
+        inputs = [np.ascontiguousarray(a, np.float32) for a in inputs]
+        n, K, nq = first.shape[0], n_members, len(q)
+        if self.graph.dropout_mc_count() == 0:
+            import warnings
+            warnings.warn(f'model {self.name} has no MC dropout layer: the {K} ensemble members are identical (build it with '
+                          "dropout_variant 'mcdrop', 'mcgaussiandrop' or 'mcspatialdrop' and a dropout_rate > 0)", UserWarning,
+                          stacklevel=2)
+        if seed is not None:
+            self.reseed_dropout(seed)
+        lib = self.graph._l
+        per = int(np.prod(self.output_shape))
+        bmax = max(min(int(batch_size), n), 1)
+        stride = bmax * per                                    # member stride of the stack, in elements
+        try:
+            stack = DeviceArray((K, stride))
+        except _lib.Dl4dsHipError as e:
+            raise MemoryError(f'predict_ensemble: the member stack of {K} x {bmax} outputs ({K * stride * 4 / 2**30:.2f} GiB) does '
+                              f'not fit on the device; lower batch_size ({e})') from None
+        stats = DeviceArray((4 + nq, stride))
+        dev_in = [DeviceArray((bmax,) + tuple(a.shape[1:])) for a in inputs]
+        in_ptrs = (ctypes.c_void_p * len(dev_in))(*[d.ptr for d in dev_in])
+        qc = (ctypes.c_float * max(nq, 1))(*q.tolist())
+        res = {k: np.empty((n,) + self.output_shape, np.float32) for k in ('mean', 'std', 'min', 'max')}
+        res['quantiles'] = np.empty((nq, n) + self.output_shape, np.float32)
+        if return_members:
+            res['members'] = np.empty((K, n) + self.output_shape, np.float32)
+        pinned = [a for a in res.values() if a.nbytes >= (1 << 22) and lib.dl4ds_host_register(a.ctypes.data, a.nbytes) == 0]
+        try:
+            for i in range(0, n, bmax):
+                part, b = self._prep_inputs([a[i:i + bmax] for a in inputs])
+                m = b * per
+                for d, a in zip(dev_in, part):                                 # the only upload of this batch
+                    _lib.check(lib.dl4ds_memcpy_h2d(d.ptr, a.ctypes.data, a.nbytes))
+                for k in range(K):
+                    _lib.check(lib.dl4ds_graph_forward(self.graph.h, in_ptrs, len(part), b, 0, 0, stack.ptr + k * stride * 4))
+                sp = [stats.ptr + r * stride * 4 for r in range(5)]
+                _lib.check(lib.dl4ds_ensemble_reduce(stack.ptr, K, m, stride, qc, nq, sp[0], sp[1], sp[2], sp[3],
+                                                     sp[4] if nq else None))
+                for r, key in enumerate(('mean', 'std', 'min', 'max')):
+                    _lib.check(lib.dl4ds_memcpy_d2h(res[key][i:i + b].ctypes.data, sp[r], m * 4))
+                for j in range(nq):                                            # quant[j] lies at j * m for this batch's m
+                    _lib.check(lib.dl4ds_memcpy_d2h(res['quantiles'][j, i:i + b].ctypes.data, sp[4] + j * m * 4, m * 4))
+                if return_members:
+                    for k in range(K):
+                        _lib.check(lib.dl4ds_memcpy_d2h(res['members'][k, i:i + b].ctypes.data, stack.ptr + k * stride * 4, m * 4))
+        finally:
+            for a in pinned:
+                lib.dl4ds_host_unregister(a.ctypes.data)
+            for d in [stack, stats] + dev_in:
+                d.free()
+        return res
 
     def resized(self, grid):
         """The same architecture planned for inputs of spatial size ``grid`` (size of the FIRST input: the LR grid of a

@@ -5,12 +5,10 @@ from . import POSTUPSAMPLING_METHODS
 from .dataloader import create_batch_hr_lr
 
 
-def predict(trainer, array, scale, array_in_hr=True, static_vars=None, predictors=None, time_window=None,
-            time_metadata=None, interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
-            save_fname='y_hat.npy', return_lr=False, device='GPU'):
-    """inference.py:109-255, step for step: HR arrays are coarsened by the batch builder, LR arrays are first re-expanded
-    to the HR grid (``resize_array``, :196-199) and handed over as ``array_lr``; one batch of all
-    ``n - (time_window - 1)`` samples (:186-189) goes through ``model.predict``."""
+def _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation):
+    """The part of ``predict`` in front of the network (inference.py:172-236) -> (model, list of input arrays): HR arrays are
+    coarsened by the batch builder, LR arrays are first re-expanded to the HR grid (``resize_array``, :196-199) and handed over as
+    ``array_lr``; one batch of all ``n - (time_window - 1)`` samples (:186-189)."""
     from .dataloader import resize_array, checkarray_ndim
     if hasattr(trainer, 'model'):
         model = trainer.model
@@ -38,7 +36,15 @@ def predict(trainer, array, scale, array_in_hr=True, static_vars=None, predictor
     x, _ = create_batch_hr_lr(np.arange(n_samples), 0, array_hr, array_lr, upsampling=upsampling, scale=scale,
                               batch_size=n_samples, patch_size=None, time_window=time_window, static_vars=static_vars,
                               predictors=preds, interpolation=interpolation)
-    inputs = x
+    return model, x
+
+
+def predict(trainer, array, scale, array_in_hr=True, static_vars=None, predictors=None, time_window=None,
+            time_metadata=None, interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
+            save_fname='y_hat.npy', return_lr=False, device='GPU'):
+    """inference.py:109-255, step for step: the inputs are prepared as the reference does (``_prepare_inputs``) and go through
+    ``model.predict``."""
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
     y = model.predict(inputs, batch_size=batch_size, verbose=0)
     if y.ndim == 5 and time_window is not None:                  # inference.py:241-242
         from .utils import spatiotemporal_to_spatial_samples
@@ -49,6 +55,73 @@ def predict(trainer, array, scale, array_in_hr=True, static_vars=None, predictor
     if save_path is not None and save_fname is not None:
         np.save(save_path + ('' if save_path.endswith('/') else '/') + save_fname, y)
     return (y, np.asarray(inputs[0])) if return_lr else y
+
+
+def _slope(scaler, shape):
+    one = np.asarray(scaler.inverse_transform(np.ones(tuple(shape), np.float64)), np.float64)
+    zero = np.asarray(scaler.inverse_transform(np.zeros(tuple(shape), np.float64)), np.float64)
+    return one - zero
+
+
+def scaler_slope(scaler, sample_shape):
+    """Slope of ``scaler.inverse_transform`` per cell of one sample: inverse_transform(ones) - inverse_transform(zeros) in float64.
+    Exact for MinMaxScaler and StandardScaler of dl4ds_amd.preprocessing, whose inverse transforms are affine per cell.  Evaluated on
+    two samples, of which the first is returned: the scalers drop size-1 axes, a lone sample would lose its sample axis."""
+    return _slope(scaler, (2,) + tuple(sample_shape))[0]
+
+
+def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, array_in_hr=True, static_vars=None,
+                     predictors=None, time_window=None, time_metadata=None, interpolation='inter_area', batch_size=64,
+                     scaler=None, save_path=None, save_fname='y_hat_ensemble.npz', return_lr=False, return_members=False,
+                     device='GPU'):
+    """``predict`` for a model built with one of the MC dropout variants ('mcdrop', 'mcgaussiandrop', 'mcspatialdrop' --
+    blocks.py:658-676, active at inference): ``n_members`` stochastic forward passes per sample, reduced on the device
+    (``Model.predict_ensemble``).  Returns a dict of float32 arrays: 'mean', 'std' (population), 'min', 'max' shaped like the
+    result of ``predict``, 'quantiles' with a leading axis of len(quantiles) (np.quantile's 'linear' method), and 'members' with a
+    leading axis of n_members when ``return_members``; ``(dict, lr)`` with ``return_lr``.  ``seed``: an integer makes the result
+    reproducible -- it is a function of (weights, inputs, n_members, batch_size, seed); None lets the model's noise continue.
+
+    Spatio-temporal outputs: every statistic goes through ``spatiotemporal_to_spatial_samples`` like ``predict``'s result.
+    ``scaler``: 'mean', 'min', 'max', 'quantiles' and 'members' go through ``scaler.inverse_transform``; 'std' is a spread, not a
+    value, and is multiplied by the transform's slope ``inverse_transform(ones) - inverse_transform(zeros)``, evaluated once in
+    float64 on one sample's shape (``scaler_slope``).  That is exact for both scalers of ``dl4ds_amd.preprocessing``, which are
+    affine per cell (for an inverse transform that is not affine it would be meaningless).  ``save_path``: one ``np.savez`` of
+    the dict."""
+    from .graph import check_ensemble_args
+    check_ensemble_args(n_members, quantiles, seed, batch_size)         # before anything touches the device
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    res = model.predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
+                                 return_members=return_members)
+    stacked = ('quantiles', 'members')                 # leading axis in front of the sample axis
+
+    def each(key, fn):
+        a = res[key]
+        if key in stacked:
+            if a.shape[0]:
+                res[key] = np.stack([np.asarray(fn(a[j]), np.float32) for j in range(a.shape[0])])
+        else:
+            res[key] = np.asarray(fn(a), np.float32)
+
+    if res['mean'].ndim == 5 and time_window is not None:        # inference.py:241-242
+        from .utils import spatiotemporal_to_spatial_samples
+        for key in list(res):
+            each(key, lambda a: spatiotemporal_to_spatial_samples(a, time_window))
+    if scaler is not None:
+        try:
+            slope = scaler_slope(scaler, res['mean'].shape[1:])
+        except IndexError:                 # a scaler fitted on data with NaNs carries a mask of the full array's shape
+            slope = _slope(scaler, res['mean'].shape)
+        std64 = res['std'].astype(np.float64)
+        for key in list(res):
+            if key != 'std':
+                each(key, scaler.inverse_transform)
+        # (the scalers drop size-1 axes: the slope then has the trailing axes of the transformed mean and broadcasts over the samples)
+        res['std'] = (np.abs(slope) * std64.reshape(res['mean'].shape)).astype(np.float32)
+    if not len(res['quantiles']):
+        res['quantiles'] = np.empty((0,) + res['mean'].shape, np.float32)
+    if save_path is not None and save_fname is not None:
+        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **res)
+    return (res, np.asarray(inputs[0])) if return_lr else res
 
 
 class Predictor:
@@ -65,3 +138,19 @@ class Predictor:
 
     def run(self):
         return predict(**self.kw)
+
+
+class EnsemblePredictor:
+    """``Predictor`` for MC-dropout ensembles: same constructor-then-``.run()`` shape, runs ``predict_ensemble``."""
+
+    def __init__(self, trainer, array, scale, n_members, quantiles=(), seed=None, array_in_hr=False, static_vars=None,
+                 predictors=None, time_window=None, time_metadata=None, interpolation='inter_area', batch_size=64, scaler=None,
+                 save_path=None, save_fname='y_hat_ensemble.npz', return_lr=False, return_members=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, n_members=n_members, quantiles=quantiles, seed=seed,
+                       array_in_hr=array_in_hr, static_vars=static_vars, predictors=predictors, time_window=time_window,
+                       time_metadata=time_metadata, interpolation=interpolation, batch_size=batch_size, scaler=scaler,
+                       save_path=save_path, save_fname=save_fname, return_lr=return_lr, return_members=return_members,
+                       device=device)
+
+    def run(self):
+        return predict_ensemble(**self.kw)

@@ -174,6 +174,17 @@ int dl4ds_scaler_stats(const void* x_dev, int is_double, const size_t* shape, in
                        unsigned* nan_flag_dev, unsigned* mask_bits_dev);
 int dl4ds_scaler_apply(const void* x_dev, void* out_dev, int is_double, const size_t* shape, int ndim, const int* reduce, int op1,
                        const void* a_dev, int op2, const void* b_dev, int nan_mode, double fill, const unsigned* mask_bits_dev);
+/* Member statistics of an MC-dropout ensemble.  Serves the MCDropout / MCGaussianDropout / MCSpatialDropout layers of
+ * blocks.py:658-676, which stay active at inference so that K forward passes of one input form an ensemble (the reference leaves
+ * the loop and the reduction to the user).  members_dev: K rows of n fp32 values, row k at members_dev + k * member_stride
+ * (member_stride >= n, in elements), 1 <= K <= 256.  ONE read of the stack writes, per element e < n (any output may be null and
+ * is then skipped): mean_dev[e], std_dev[e] (population, ddof 0), min_dev[e], max_dev[e], and quant_dev[j * n + e] for the nq <= 32
+ * probabilities q_host[j] in [0, 1]: np.quantile's default 'linear' method on the sorted K values.  Everything is evaluated as
+ * numpy does on the fp64 copy of the stack (sequential fp64 two-pass mean / std in member order, fp64 interpolation between the two
+ * fp32 order statistics) and rounded to fp32 once; a NaN among the K values makes every output of that element NaN, infinities
+ * give what those formulas give.  No atomics: bitwise reproducible.  Algorithmic traffic (K + 4 + nq) * 4 * n bytes. */
+int dl4ds_ensemble_reduce(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
+                          float* mean_dev, float* std_dev, float* min_dev, float* max_dev, float* quant_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
@@ -253,6 +264,11 @@ int dl4ds_graph_dropout_count(dl4ds_graph* g, int* n);
 int dl4ds_graph_dropout_mask_size(dl4ds_graph* g, int index, int B, size_t* n);
 int dl4ds_graph_dropout_get_mask(dl4ds_graph* g, int index, int B, float* dst_host);
 int dl4ds_graph_dropout_set_mask(dl4ds_graph* g, int index, int B, const float* src_host);
+/* reseed: every dropout op gets the seed mix(seed, op index) and its draw counter goes back to 0, so the masks drawn by the
+ * forward passes that follow (fixed batch size) are a pure function of `seed`: a reproducible MC ensemble (blocks.py:658-676).
+ * A graph that was never reseeded keeps its built-in seeds.  mc_count: dropout ops that are active at inference (mc != 0, rate > 0). */
+int dl4ds_graph_dropout_reseed(dl4ds_graph* g, unsigned long long seed);
+int dl4ds_graph_dropout_mc_count(dl4ds_graph* g, int* n);
 /* LayerNormalization(axis=-1) (batch == 0; mov_* ignored) / BatchNormalization(axis=-1, momentum=0.99) (batch != 0)
  * as instantiated by blocks.py:63-71,151-159,293-296; relu != 0 fuses the activation that follows the layer. */
 int dl4ds_graph_norm(dl4ds_graph* g, int in, int gamma, int beta, int mov_mean, int mov_var, int batch, float eps, int relu,
