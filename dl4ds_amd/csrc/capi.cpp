@@ -569,6 +569,18 @@ int dl4ds_ensemble_reduce(const float* members_dev, size_t K, size_t n, size_t m
     ensemble_reduce(S(), members_dev, K, n, member_stride, q_host, nq, mean_dev, std_dev, min_dev, max_dev, quant_dev);
     API_END
 }
+int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                         unsigned long long elem_offset, const float* scale_dev, int fair, unsigned long long seed,
+                         const float* q_host, int nq, float* crps_dev, float* sqerr_dev, float* var_dev, int* rank_dev,
+                         double* sample_out_dev, double* cell_acc_dev, unsigned long long* rank_hist_dev,
+                         unsigned long long* covered_dev) {
+    API_BEGIN
+    const size_t ws = ensemble_score_workspace_bytes(n, B ? B : 1);
+    ensemble_score(S(), members_dev, K, n, member_stride, obs_dev, B, elem_offset, scale_dev, fair, seed, q_host, nq, crps_dev,
+                   sqerr_dev, var_dev, rank_dev, sample_out_dev, cell_acc_dev, rank_hist_dev, covered_dev, ws ? scratch(ws) : nullptr,
+                   ws);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

@@ -16,43 +16,15 @@
 //           floor(pos) + 1, t = pos - floor(pos).  d = b - a; result = t >= 0.5 ? b - d (1 - t) : a + d t, in fp64 on the two fp32
 //           values, rounded once.  (numpy's _lerp: the second form is what decides between inf and NaN next to an infinite value.)
 //   A NaN among the K values makes every output of that element NaN; infinities give what the formulas give (std NaN).
-#include "common.h"
-#include "ops.h"
+#include "ensemble_common.h"
 #include "prof.h"
-#include <cmath>
-#include <cstdint>
 
 // numpy rounds (x - mean)^2 and the running sum separately, and d * t and the sum of the interpolation too
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int ENS_THREADS = 256;
-constexpr int ENS_STAGED_THREADS = 64;      // one wave: a lane's column is private, no barrier anywhere
-
-struct EnsQ {
-    int lo[ENS_MAX_QUANTILES], hi[ENS_MAX_QUANTILES];
-    double t[ENS_MAX_QUANTILES];
-};
-
 struct EnsOut { float *mean, *std, *mn, *mx, *quant; };
-
-__device__ __forceinline__ float ens_nan() { return __builtin_nanf(""); }
-
-__device__ __forceinline__ double ens_lerp(float a, float b, double t) {
-    const double da = (double)a, db = (double)b;
-    const double d = db - da;
-    return t >= 0.5 ? db - d * (1.0 - t) : da + d * t;
-}
-
-// VEC results of one statistic -> p[e0 .. e0 + VEC) as one 4 / 8 / 16-byte store (the host checked alignment and n % VEC == 0)
-template <int VEC>
-__device__ __forceinline__ void ens_store(float* p, const float (&r)[VEC]) {
-    if (!p) return;
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-    else if constexpr (VEC == 2) *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]);
-    else p[0] = r[0];
-}
 
 // ------------------------------------------------------------------------------------------------ K <= 64: registers
 // n % VEC == 0, member_stride % VEC == 0 and every pointer aligned to VEC floats (else the host takes the VEC = 1 instance).
@@ -64,29 +36,8 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_reduce_reg(const float* 
     const unsigned off = threadIdx.x * VEC;                             // the lane's part is one 32-bit offset
     if (blk + off >= n) return;
     float v[KP][VEC];
-    // Branch-free: every row's load is issued before anything is used.  Rows k >= K re-read row K - 1 (a cache hit, no HBM traffic;
-    // none when K is a power of two) and are then replaced by +inf.
-    const float* row = members + blk;
-#pragma unroll
-    for (int k = 0; k < KP; ++k) {
-        if constexpr (VEC == 4) {
-            const float4 x = *reinterpret_cast<const float4*>(row + off);
-            v[k][0] = x.x; v[k][1] = x.y; v[k][2] = x.z; v[k][3] = x.w;
-        } else if constexpr (VEC == 2) {
-            const float2 x = *reinterpret_cast<const float2*>(row + off);
-            v[k][0] = x.x; v[k][1] = x.y;
-        } else {
-            v[k][0] = row[off];
-        }
-        row += (FULL || k + 1 < K) ? stride : 0;
-    }
-    if constexpr (!FULL) {
-#pragma unroll
-        for (int k = 1; k < KP; ++k) {
-#pragma unroll
-            for (int c = 0; c < VEC; ++c) v[k][c] = k < K ? v[k][c] : __builtin_inff();
-        }
-    }
+    // branch-free: every row's load is issued before anything is used (ens_load)
+    ens_load<KP, VEC, FULL>(members + blk, off, K, stride, v);
 
     float r_mean[VEC], r_std[VEC], r_mn[VEC], r_mx[VEC];
     bool isnan_[VEC];
@@ -122,48 +73,24 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_reduce_reg(const float* 
         r_mx[c] = bad ? ens_nan() : mx;
     }
     const size_t e0 = blk + off;
-    ens_store<VEC>(out.mean ? out.mean + e0 : nullptr, r_mean);
-    ens_store<VEC>(out.std ? out.std + e0 : nullptr, r_std);
-    ens_store<VEC>(out.mn ? out.mn + e0 : nullptr, r_mn);
-    ens_store<VEC>(out.mx ? out.mx + e0 : nullptr, r_mx);
+    ens_store<VEC, float>(out.mean ? out.mean + e0 : nullptr, r_mean);
+    ens_store<VEC, float>(out.std ? out.std + e0 : nullptr, r_std);
+    ens_store<VEC, float>(out.mn ? out.mn + e0 : nullptr, r_mn);
+    ens_store<VEC, float>(out.mx ? out.mx + e0 : nullptr, r_mx);
 
     if (nq <= 0) return;
-    // bitonic network on the KP register values of each element: every index is a compile-time constant after unrolling
-#pragma unroll
-    for (int size = 2; size <= KP; size <<= 1) {
-#pragma unroll
-        for (int j = size >> 1; j > 0; j >>= 1) {
-#pragma unroll
-            for (int i = 0; i < KP; ++i) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const bool up = (i & size) == 0;
-#pragma unroll
-                    for (int c = 0; c < VEC; ++c) {
-                        const float a = v[i][c], b = v[l][c];
-                        const float lo = fminf(a, b), hi = fmaxf(a, b);
-                        v[i][c] = up ? lo : hi;
-                        v[l][c] = up ? hi : lo;
-                    }
-                }
-            }
-        }
-    }
+    ens_sort_reg<KP, VEC>(v);
     for (int j = 0; j < nq; ++j) {
         const int lo = q.lo[j], hi = q.hi[j];
         const double t = q.t[j];
         float r[VEC];
 #pragma unroll
         for (int c = 0; c < VEC; ++c) {
-            float a = v[0][c], b = v[0][c];
-#pragma unroll
-            for (int k = 1; k < KP; ++k) {        // (lo, hi are uniform: selects on a scalar condition, no indexed register file)
-                a = k == lo ? v[k][c] : a;
-                b = k == hi ? v[k][c] : b;
-            }
+            float a, b;
+            ens_pick<KP, VEC>(v, c, lo, hi, a, b);
             r[c] = isnan_[c] ? ens_nan() : (float)ens_lerp(a, b, t);
         }
-        ens_store<VEC>(out.quant + (size_t)j * n + e0, r);
+        ens_store<VEC, float>(out.quant + (size_t)j * n + e0, r);
     }
 }
 
@@ -198,18 +125,7 @@ __global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_reduce_staged(con
     if (out.mn) out.mn[e] = bad ? ens_nan() : mn;
     if (out.mx) out.mx[e] = bad ? ens_nan() : mx;
     if (nq <= 0 || !out.quant) return;
-    for (int size = 2; size <= KP; size <<= 1)
-        for (int j = size >> 1; j > 0; j >>= 1)
-            for (int i = 0; i < KP; ++i) {
-                const int l = i ^ j;
-                if (l > i) {
-                    const float a = s[i * ENS_STAGED_THREADS], b = s[l * ENS_STAGED_THREADS];
-                    const float lo = fminf(a, b), hi = fmaxf(a, b);
-                    const bool up = (i & size) == 0;
-                    s[i * ENS_STAGED_THREADS] = up ? lo : hi;
-                    s[l * ENS_STAGED_THREADS] = up ? hi : lo;
-                }
-            }
+    ens_sort_column(s, KP);
     for (int j = 0; j < nq; ++j) {
         const float a = s[q.lo[j] * ENS_STAGED_THREADS], b = s[q.hi[j] * ENS_STAGED_THREADS];
         out.quant[(size_t)j * n + e] = bad ? ens_nan() : (float)ens_lerp(a, b, q.t[j]);
@@ -249,21 +165,7 @@ void ensemble_reduce(hipStream_t s, const float* members, size_t K, size_t n, si
     if (n == 0) return;
     DL4DS_REQUIRE(members, "ensemble_reduce: null member stack");
     DL4DS_REQUIRE(member_stride >= n, "ensemble_reduce: member stride smaller than the member");
-    EnsQ q{};
-    for (int j = 0; j < nq; ++j) {
-        const double p = (double)q_host[j];
-        DL4DS_REQUIRE(p >= 0.0 && p <= 1.0, "ensemble_reduce: quantile probabilities must be in [0, 1]");
-        const double pos = (double)(K - 1) * p;
-        if (pos >= (double)(K - 1)) {
-            q.lo[j] = q.hi[j] = (int)K - 1;
-            q.t[j] = pos + 1.0;                   // numpy: previous index -1 (the last element), gamma = pos - (-1)
-        } else {
-            const double f = std::floor(pos);
-            q.lo[j] = (int)f;
-            q.hi[j] = (int)f + 1;
-            q.t[j] = pos - f;
-        }
-    }
+    const EnsQ q = ens_positions("ensemble_reduce", K, q_host, nq);
     if (!quant) nq = 0;
     const EnsOut out{mean, std_, mn, mx, quant};
     const int k = (int)K;

@@ -148,6 +148,16 @@ void scaler_apply(hipStream_t s, const void* x, void* out, int is_double, const 
 constexpr int ENS_MAX_MEMBERS = 256, ENS_MAX_QUANTILES = 32;
 void ensemble_reduce(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
                      float* mean, float* std_, float* mn, float* mx, float* quant);
+// Verification of the ensemble members[K][n] against obs[n] (ensemble_score.hip): per element CRPS (fair != 0: the fair form),
+// squared error of the ensemble mean, unbiased variance, rank of the observation with hashed tie-breaking, coverage of nq quantiles;
+// folded per sample (sample_out[B][4]: sums of crps, sqerr, var and the valid count), per cell (cell_acc[4][n / B], +=) and into
+// rank_hist[K + 1] / covered[nq] (+=).  Elements next to a non-finite value or a scale cell that is not finite and > 0 are invalid:
+// NaN / rank -1, in no fold.  Per-element outputs and folds may be null.  No floating-point atomics: bitwise reproducible.
+size_t ensemble_score_workspace_bytes(size_t n, size_t B);
+void ensemble_score(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                    unsigned long long elem_offset, const float* scale, int fair, unsigned long long seed, const float* q_host, int nq,
+                    float* crps, float* sqerr, float* var, int* rank, double* sample_out, double* cell_acc,
+                    unsigned long long* rank_hist, unsigned long long* covered, void* workspace, size_t workspace_bytes);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

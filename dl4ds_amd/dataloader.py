@@ -8,7 +8,7 @@ gathers -- INTER_AREA (integer-ratio block mean; up-scaling through OpenCV's own
 which replicate pixels at integer factors), INTER_NEAREST, INTER_LINEAR (half-pixel centres, edge clamp),
 INTER_CUBIC (A = -0.75, replicated border) and INTER_LANCZOS4 (8 taps, replicated border).  oracle/dataprep.py restates the same
 formulas independently (dense per-pixel form) and tests/test_oracle_dataprep.py compares the two.
-Season/time-metadata channels are not implemented.
+Season channels from the time metadata (``get_season`` / ``get_season_array``: four one-hot channels) are implemented below.
 """
 import numpy as np
 

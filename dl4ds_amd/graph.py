@@ -545,16 +545,52 @@ class Model:
         are split into batches, so a stack that does not fit raises MemoryError instead of being re-chunked.  ``seed=None``:
         the graph's noise counters simply continue."""
         n_members, q = check_ensemble_args(n_members, quantiles, seed, batch_size)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, return_members)
+
+    def score_ensemble(self, inputs, y_true, n_members, batch_size=32, quantiles=(), seed=None, fair=False, scale=None,
+                       return_fields=False):
+        """``predict_ensemble`` plus the verification of the ensemble against the observation ``y_true`` of shape
+        (N,) + output_shape, scored on the device while each batch's member stack is resident (csrc/ensemble_score.hip, DESIGN.md
+        section 13).  Returns ``predict_ensemble``'s dict with one more key, 'scores': a dict with the scalars 'crps', 'spread'
+        (sqrt of the mean ensemble variance, ddof 1), 'rmse' (of the ensemble mean), 'spread_skill' (spread / rmse) over all valid
+        elements; 'crps_per_sample', 'spread_per_sample', 'rmse_per_sample' (N,); 'crps_map', 'spread_map', 'rmse_map' shaped like
+        one sample (NaN where no sample was valid); 'rank_histogram' int64 (n_members + 1,); 'covered' int64 and 'coverage'
+        (= covered / n_valid) per quantile: how often the observation is <= that quantile; 'n_valid' (with '_per_sample' and
+        '_map'), the raw float64 sums 'sample_sums' (N, 4) and 'cell_sums' (4,) + output_shape (crps, squared error, variance,
+        count), 'n_cells_excluded'; and with ``return_fields`` the per-element 'crps_field', 'sqerr_field', 'var_field'
+        (float32, NaN where invalid) and 'rank_field' (int32, -1 where invalid).
+
+        An element is valid iff its observation and all its members are finite: write NaN into ``y_true`` to mask.  ``fair``: the
+        fair CRPS (pair term over K (K - 1) instead of K^2).  ``scale``: a positive factor per cell (broadcast to one sample)
+        that carries CRPS, spread and RMSE into physical units; cells where it is not finite and > 0 are excluded and counted in
+        'n_cells_excluded'.  Ties between the observation and members are broken by a hash of (seed, element index), 0 for
+        ``seed=None``: the ranks do not depend on ``batch_size`` (the members do, as in ``predict_ensemble``).  Scores are per
+        element and "sample" is the leading axis, whatever the output's rank; the stack is read twice (statistics, then scores)."""
+        n_members, q = check_ensemble_args(n_members, quantiles, seed, batch_size)
+        from .ensemble_score import check_score_args
+        check_score_args(fair)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False,
+                                  score=dict(y_true=y_true, fair=fair, scale=scale, return_fields=return_fields), who='score_ensemble')
+
+    def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, score=None, who='predict_ensemble'):
+        """The per-batch loop of ``predict_ensemble`` / ``score_ensemble``: inputs (and the observation) uploaded once per batch,
+        the members written into one device stack, reduced (and scored) there."""
         if isinstance(inputs, np.ndarray):
             inputs = [inputs]
         first = np.asarray(inputs[0])
         grid = tuple(first.shape[-3:-1])
         if grid != tuple(self.input_shapes[0][-3:-1]):
-            return self.resized(grid).predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
-                                                       return_members=return_members)
+            return self.resized(grid)._run_ensemble(inputs, n_members, q, batch_size, seed, return_members, score=score, who=who)
         from .device import DeviceArray
         inputs = [np.ascontiguousarray(a, np.float32) for a in inputs]
         n, K, nq = first.shape[0], n_members, len(q)
+        y_true = None
+        if score is not None:
+            from .ensemble_score import check_score_args
+            y_true = np.ascontiguousarray(score['y_true'], np.float32)
+            if y_true.shape != (n,) + self.output_shape:
+                raise ValueError(f'`y_true` must have the shape of the prediction {(n,) + self.output_shape}, got {y_true.shape}')
+            scale = check_score_args(score['fair'], score['scale'], self.output_shape)
         if self.graph.dropout_mc_count() == 0:
             import warnings
             warnings.warn(f'model {self.name} has no MC dropout layer: the {K} ensemble members are identical (build it with '
@@ -569,9 +605,10 @@ class Model:
         try:
             stack = DeviceArray((K, stride))
         except _lib.Dl4dsHipError as e:
-            raise MemoryError(f'predict_ensemble: the member stack of {K} x {bmax} outputs ({K * stride * 4 / 2**30:.2f} GiB) does '
+            raise MemoryError(f'{who}: the member stack of {K} x {bmax} outputs ({K * stride * 4 / 2**30:.2f} GiB) does '
                               f'not fit on the device; lower batch_size ({e})') from None
         stats = DeviceArray((4 + nq, stride))
+        scorer = dev_obs = None
         dev_in = [DeviceArray((bmax,) + tuple(a.shape[1:])) for a in inputs]
         in_ptrs = (ctypes.c_void_p * len(dev_in))(*[d.ptr for d in dev_in])
         qc = (ctypes.c_float * max(nq, 1))(*q.tolist())
@@ -581,6 +618,10 @@ class Model:
             res['members'] = np.empty((K, n) + self.output_shape, np.float32)
         pinned = [a for a in res.values() if a.nbytes >= (1 << 22) and lib.dl4ds_host_register(a.ctypes.data, a.nbytes) == 0]
         try:
+            if score is not None:                      # (inside the try: a refused allocation here still frees the stack)
+                from .ensemble_score import Scorer
+                dev_obs = DeviceArray((stride,))
+                scorer = Scorer(K, n, self.output_shape, q, score['fair'], seed, scale, score['return_fields'], bmax)
             for i in range(0, n, bmax):
                 part, b = self._prep_inputs([a[i:i + bmax] for a in inputs])
                 m = b * per
@@ -595,12 +636,20 @@ class Model:
                     _lib.check(lib.dl4ds_memcpy_d2h(res[key][i:i + b].ctypes.data, sp[r], m * 4))
                 for j in range(nq):                                            # quant[j] lies at j * m for this batch's m
                     _lib.check(lib.dl4ds_memcpy_d2h(res['quantiles'][j, i:i + b].ctypes.data, sp[4] + j * m * 4, m * 4))
+                if scorer is not None:                                         # the stack is still resident: second read
+                    _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, y_true[i:i + b].ctypes.data, m * 4))
+                    scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
                 if return_members:
                     for k in range(K):
                         _lib.check(lib.dl4ds_memcpy_d2h(res['members'][k, i:i + b].ctypes.data, stack.ptr + k * stride * 4, m * 4))
+            if scorer is not None:
+                res['scores'] = scorer.result()
         finally:
             for a in pinned:
                 lib.dl4ds_host_unregister(a.ctypes.data)
+            for d in (scorer, dev_obs):
+                if d is not None:
+                    d.free()
             for d in [stack, stats] + dev_in:
                 d.free()
         return res

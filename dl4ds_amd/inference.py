@@ -70,28 +70,9 @@ def scaler_slope(scaler, sample_shape):
     return _slope(scaler, (2,) + tuple(sample_shape))[0]
 
 
-def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, array_in_hr=True, static_vars=None,
-                     predictors=None, time_window=None, time_metadata=None, interpolation='inter_area', batch_size=64,
-                     scaler=None, save_path=None, save_fname='y_hat_ensemble.npz', return_lr=False, return_members=False,
-                     device='GPU'):
-    """``predict`` for a model built with one of the MC dropout variants ('mcdrop', 'mcgaussiandrop', 'mcspatialdrop' --
-    blocks.py:658-676, active at inference): ``n_members`` stochastic forward passes per sample, reduced on the device
-    (``Model.predict_ensemble``).  Returns a dict of float32 arrays: 'mean', 'std' (population), 'min', 'max' shaped like the
-    result of ``predict``, 'quantiles' with a leading axis of len(quantiles) (np.quantile's 'linear' method), and 'members' with a
-    leading axis of n_members when ``return_members``; ``(dict, lr)`` with ``return_lr``.  ``seed``: an integer makes the result
-    reproducible -- it is a function of (weights, inputs, n_members, batch_size, seed); None lets the model's noise continue.
-
-    Spatio-temporal outputs: every statistic goes through ``spatiotemporal_to_spatial_samples`` like ``predict``'s result.
-    ``scaler``: 'mean', 'min', 'max', 'quantiles' and 'members' go through ``scaler.inverse_transform``; 'std' is a spread, not a
-    value, and is multiplied by the transform's slope ``inverse_transform(ones) - inverse_transform(zeros)``, evaluated once in
-    float64 on one sample's shape (``scaler_slope``).  That is exact for both scalers of ``dl4ds_amd.preprocessing``, which are
-    affine per cell (for an inverse transform that is not affine it would be meaningless).  ``save_path``: one ``np.savez`` of
-    the dict."""
-    from .graph import check_ensemble_args
-    check_ensemble_args(n_members, quantiles, seed, batch_size)         # before anything touches the device
-    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
-    res = model.predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
-                                 return_members=return_members)
+def _finish_ensemble(res, scaler, time_window):
+    """What ``predict_ensemble`` does to the raw statistics of ``Model.predict_ensemble``: spatio-temporal flattening, the scaler's
+    inverse transform of the values and its slope on the spread; in place."""
     stacked = ('quantiles', 'members')                 # leading axis in front of the sample axis
 
     def each(key, fn):
@@ -119,8 +100,112 @@ def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, 
         res['std'] = (np.abs(slope) * std64.reshape(res['mean'].shape)).astype(np.float32)
     if not len(res['quantiles']):
         res['quantiles'] = np.empty((0,) + res['mean'].shape, np.float32)
+
+
+def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, array_in_hr=True, static_vars=None,
+                     predictors=None, time_window=None, time_metadata=None, interpolation='inter_area', batch_size=64,
+                     scaler=None, save_path=None, save_fname='y_hat_ensemble.npz', return_lr=False, return_members=False,
+                     device='GPU'):
+    """``predict`` for a model built with one of the MC dropout variants ('mcdrop', 'mcgaussiandrop', 'mcspatialdrop' --
+    blocks.py:658-676, active at inference): ``n_members`` stochastic forward passes per sample, reduced on the device
+    (``Model.predict_ensemble``).  Returns a dict of float32 arrays: 'mean', 'std' (population), 'min', 'max' shaped like the
+    result of ``predict``, 'quantiles' with a leading axis of len(quantiles) (np.quantile's 'linear' method), and 'members' with a
+    leading axis of n_members when ``return_members``; ``(dict, lr)`` with ``return_lr``.  ``seed``: an integer makes the result
+    reproducible -- it is a function of (weights, inputs, n_members, batch_size, seed); None lets the model's noise continue.
+
+    Spatio-temporal outputs: every statistic goes through ``spatiotemporal_to_spatial_samples`` like ``predict``'s result.
+    ``scaler``: 'mean', 'min', 'max', 'quantiles' and 'members' go through ``scaler.inverse_transform``; 'std' is a spread, not a
+    value, and is multiplied by the transform's slope ``inverse_transform(ones) - inverse_transform(zeros)``, evaluated once in
+    float64 on one sample's shape (``scaler_slope``).  That is exact for both scalers of ``dl4ds_amd.preprocessing``, which are
+    affine per cell (for an inverse transform that is not affine it would be meaningless).  ``save_path``: one ``np.savez`` of
+    the dict."""
+    from .graph import check_ensemble_args
+    check_ensemble_args(n_members, quantiles, seed, batch_size)         # before anything touches the device
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    res = model.predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
+                                 return_members=return_members)
+    _finish_ensemble(res, scaler, time_window)
     if save_path is not None and save_fname is not None:
         np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **res)
+    return (res, np.asarray(inputs[0])) if return_lr else res
+
+
+def _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, array_in_hr, time_window, batch_size, scaler=None):
+    """Everything ``verify_ensemble`` can refuse from its arguments alone (no library, no device) -> the observation as an array
+    with a channel axis."""
+    from .graph import check_ensemble_args
+    from .ensemble_score import check_score_args
+    check_ensemble_args(n_members, quantiles, seed, batch_size)
+    check_score_args(fair)
+    if time_window is not None:
+        raise ValueError('verify_ensemble: `time_window` is not supported: how scores of overlapping windows flatten to spatial '
+                         'samples is not defined yet (score the 5-D output with Model.score_ensemble)')
+    array = np.asarray(getattr(array, 'values', array))
+    if y_true is None:
+        if not array_in_hr:
+            raise ValueError('`y_true` is required when `array_in_hr` is False (there is no HR field to verify against)')
+        if scaler is not None:
+            raise ValueError('`y_true` is required with a `scaler`: the observation is taken in physical units, while the HR '
+                             '`array` that feeds the model is in the model\'s units then')
+        y_true = array
+    y_true = np.asarray(getattr(y_true, 'values', y_true))
+    if y_true.ndim == 3:
+        y_true = y_true[..., None]
+    grid = tuple(array.shape[1:3]) if array_in_hr else (array.shape[1] * scale, array.shape[2] * scale)
+    if y_true.ndim != 4 or tuple(y_true.shape[:3]) != (array.shape[0],) + grid:
+        raise ValueError(f"`y_true` must have the shape of predict's result {(array.shape[0],) + grid + ('C',)}, got {y_true.shape}")
+    return y_true
+
+
+def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(), seed=None, fair=False, mask=None,
+                    array_in_hr=True, static_vars=None, predictors=None, time_window=None, time_metadata=None,
+                    interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
+                    save_fname='y_hat_ensemble_scores.npz', return_lr=False, device='GPU'):
+    """``predict_ensemble`` plus the verification of the ensemble against the observation, scored on the device while the member
+    stack is resident (``Model.score_ensemble``, csrc/ensemble_score.hip): returns ``predict_ensemble``'s dict of statistics with
+    one more key, 'scores' -- CRPS (``fair``: the fair form), spread, RMSE of the ensemble mean, spread / RMSE, each over all valid
+    elements, per sample and as a map; the rank histogram; the coverage of ``quantiles``; see ``Model.score_ensemble`` for every key.
+
+    ``y_true``: the observation in physical units, shaped like ``predict``'s result; None means the HR ``array`` itself and is
+    allowed only with ``array_in_hr=True`` and without a ``scaler`` (with one, ``array`` is in the model's units).  ``mask``: as in ``compute_metrics`` (2-D or with a channel axis, 0 = excluded); NaN
+    and infinite observations or members exclude their element too.  ``scaler``: the observation goes through
+    ``scaler.transform`` (the members live in the model's units, scoring happens there) and the slope of
+    ``scaler.inverse_transform`` per cell (``scaler_slope``) carries CRPS, spread and RMSE back into physical units; the ranks do
+    not change.  Cells whose slope is not finite and positive are excluded and counted in ``scores['n_cells_excluded']``.  NaN in ``y_true``
+    stays NaN through the transform (which would otherwise fill it); a scaler fitted on data with NaNs, whose inverse transform has
+    no per-cell slope for one sample, raises ValueError.
+    ``save_path``: one ``np.savez`` of the statistics and the scores (flattened with a ``scores_`` prefix).
+
+    Out of scope: recurrent models.  ``time_window is not None`` raises ValueError, because how the scores of overlapping windows
+    flatten to spatial samples is not defined yet."""
+    y_true = _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, array_in_hr, time_window, batch_size,
+                                scaler)
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    from .metrics import _masked_observation
+    obs, slope = y_true, None
+    if scaler is not None:
+        # the scalers' transform replaces NaN by a fill value and, built with copy=False, writes into its argument: the positions
+        # that are not finite are recorded first and the transform gets a copy
+        bad = ~np.isfinite(np.asarray(y_true, np.float64))
+        obs = np.array(scaler.transform(np.array(y_true, copy=True)), np.float32).reshape(y_true.shape)
+        obs[bad] = np.nan
+        try:
+            slope = np.asarray(scaler_slope(scaler, y_true.shape[1:]), np.float64)
+        except IndexError:
+            raise ValueError('verify_ensemble: `scaler` has no per-cell slope for one sample (a scaler fitted on data with NaNs '
+                             'carries a mask of the full array\'s shape); that is not supported') from None
+        if slope.size == int(np.prod(y_true.shape[1:])):       # (the scalers drop size-1 axes)
+            slope = slope.reshape(y_true.shape[1:])
+    obs = _masked_observation(obs, mask)
+    res = model.score_ensemble(inputs, obs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed, fair=fair,
+                               scale=slope)
+    scores = res.pop('scores')
+    _finish_ensemble(res, scaler, time_window)
+    res['scores'] = scores
+    if save_path is not None and save_fname is not None:
+        flat = {k: v for k, v in res.items() if k != 'scores'}
+        flat.update({'scores_' + k: np.asarray(v) for k, v in scores.items()})
+        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **flat)
     return (res, np.asarray(inputs[0])) if return_lr else res
 
 
@@ -154,3 +239,19 @@ class EnsemblePredictor:
 
     def run(self):
         return predict_ensemble(**self.kw)
+
+
+class EnsembleVerifier:
+    """``EnsemblePredictor`` for the verification: same constructor-then-``.run()`` shape, runs ``verify_ensemble``."""
+
+    def __init__(self, trainer, array, scale, n_members, y_true=None, quantiles=(), seed=None, fair=False, mask=None,
+                 array_in_hr=False, static_vars=None, predictors=None, time_window=None, time_metadata=None,
+                 interpolation='inter_area', batch_size=64, scaler=None, save_path=None, save_fname='y_hat_ensemble_scores.npz',
+                 return_lr=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, n_members=n_members, y_true=y_true, quantiles=quantiles,
+                       seed=seed, fair=fair, mask=mask, array_in_hr=array_in_hr, static_vars=static_vars, predictors=predictors,
+                       time_window=time_window, time_metadata=time_metadata, interpolation=interpolation, batch_size=batch_size,
+                       scaler=scaler, save_path=save_path, save_fname=save_fname, return_lr=return_lr, device=device)
+
+    def run(self):
+        return verify_ensemble(**self.kw)

@@ -167,3 +167,63 @@ def compute_metrics(y_test, y_test_hat, dpi=150, plot_size_px=1000, n_jobs=-1, s
         for a in (rmse_map, corr_map, nmeanbias):
             a[np.where(np.broadcast_to(mask, a.shape) == 0)] = 0
     return rmse_map, corr_map, nmeanbias, m
+
+
+def _masked_observation(y, mask):
+    """``y`` as float32 with NaN where ``mask`` (2-D, or with a channel axis; 0 = excluded) is 0, as ``compute_metrics`` reads it."""
+    y = np.array(y, np.float32)                    # (a copy: the caller's array is not written)
+    if mask is not None:
+        mask = np.asarray(getattr(mask, 'values', mask))
+        if mask.ndim == 2 and y.ndim >= 4:
+            mask = mask[..., None]
+        try:
+            excluded = np.broadcast_to(mask == 0, y.shape)
+        except ValueError:
+            raise ValueError(f'`mask` of shape {mask.shape} does not broadcast to the observation {y.shape}') from None
+        y[excluded] = np.nan
+    return y
+
+
+def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None, batch_size=None, scale=None,
+                    return_fields=False):
+    """Verification scores of an ensemble the caller already has on the host: ``members`` shaped (K,) + y_true.shape against the
+    observation ``y_true`` (samples on the leading axis), uploaded in chunks of ``batch_size`` samples (default: chunks of at most
+    256 MiB of members) and scored on the device by the entry ``Model.score_ensemble`` uses (csrc/ensemble_score.hip).  Returns the
+    'scores' dict described there: CRPS (``fair``: the fair form), spread, RMSE of the ensemble mean and their ratio, per sample and
+    per cell, the rank histogram with ties broken by a hash of (``seed``, element index), the coverage of ``quantiles``.  The result
+    does not depend on ``batch_size``.  ``mask``: 2-D or with a channel axis, 0 = excluded (NaN is written into the observation;
+    elements next to a non-finite value are excluded anyway).  The folds run one lane per cell and walk a chunk's samples in
+    turn: made for fields; samples of very few cells (a 1-D ``y_true`` has one) are slow.  ``scale``: a positive factor per cell, see ``Model.score_ensemble``."""
+    from .graph import check_ensemble_args
+    from .ensemble_score import Scorer, check_score_args
+    members = np.asarray(members)
+    if members.ndim < 2:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape, got {members.shape}')
+    K, q = check_ensemble_args(int(members.shape[0]), quantiles, seed, batch_size)
+    y_true = np.asarray(getattr(y_true, 'values', y_true))
+    if y_true.ndim < 1 or members.shape[1:] != y_true.shape:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape = (K,) + {y_true.shape}, got {members.shape}')
+    N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
+    scale = check_score_args(fair, scale, sample_shape)
+    obs = _masked_observation(y_true, mask)
+    per = int(np.prod(sample_shape, dtype=np.int64))
+    if batch_size is None:
+        batch_size = max(1, (1 << 26) // max(K * per, 1))
+    bmax = max(min(int(batch_size), N), 1)
+    stride = bmax * per
+    scorer = Scorer(K, N, sample_shape, q, fair, seed, scale, return_fields, bmax)
+    stack, dev_obs = DeviceArray((K, stride)), DeviceArray((stride,))
+    lib = _lib.lib()
+    try:
+        for i in range(0, N, bmax):
+            b = min(bmax, N - i)
+            for k in range(K):
+                part = np.ascontiguousarray(members[k, i:i + b], np.float32)
+                _lib.check(lib.dl4ds_memcpy_h2d(stack.ptr + k * stride * 4, part.ctypes.data, part.nbytes))
+            _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, obs[i:i + b].ctypes.data, b * per * 4))
+            scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
+        return scorer.result()
+    finally:
+        scorer.free()
+        stack.free()
+        dev_obs.free()

@@ -185,6 +185,40 @@ int dl4ds_scaler_apply(const void* x_dev, void* out_dev, int is_double, const si
  * give what those formulas give.  No atomics: bitwise reproducible.  Algorithmic traffic (K + 4 + nq) * 4 * n bytes. */
 int dl4ds_ensemble_reduce(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* q_host, int nq,
                           float* mean_dev, float* std_dev, float* min_dev, float* max_dev, float* quant_dev);
+/* Verification of an MC-dropout ensemble against an observation.  Serves the same MC* layers of blocks.py:658-676: the reference
+ * defines them and leaves both the ensemble loop and its verification to the user.  members_dev as for dl4ds_ensemble_reduce
+ * (K rows of n fp32 values, row k at members_dev + k * member_stride, 1 <= K <= 256); obs_dev [n]: the observation; the n
+ * elements are B whole samples of per = n / B cells (n % B == 0), the first of them element elem_offset of the whole data set
+ * (elem_offset % per == 0); scale_dev (or null) [per]: a positive factor per cell that carries the scores into physical units.
+ * An element e is VALID iff obs[e] and its K members are finite (no NaN, no infinity) and, with a scale, scale[e % per] is finite
+ * and > 0.  An invalid element gets NaN (rank -1) in the per-element outputs and takes no part in any sum, count or histogram: NaN
+ * in obs_dev is the masking mechanism.  ONE read of the stack computes per element, each value in fp64 on the fp32 inputs, rounded
+ * to fp32 once:
+ *   crps_dev[e]  = (1/K) sum_k |x_k - y| - c sum_{i<j} |x_i - x_j|, c = 1/K^2 (CRPS of the empirical distribution) or, fair != 0,
+ *                  c = 1/(K (K - 1)) (fair CRPS); K = 1: |x_0 - y|.  The pair term is evaluated from the sorted differences
+ *                  d_k = x_k - y as sum_i (2 i - K + 1) d_(i), so cancellation scales with the ensemble's distance from the
+ *                  observation, not with the field's magnitude.  Times scale.
+ *   sqerr_dev[e] = (mean_k x_k - y)^2, var_dev[e] = sum_k (x_k - mean)^2 / (K - 1) (K = 1: 0); times scale^2.
+ *   rank_dev[e]  = #{k : x_k < y} + tie(seed, g, m), m = #{k : x_k == y} (-0.0 == +0.0), g = elem_offset + e, and with all
+ *                  arithmetic on unsigned 64-bit integers (mod 2^64):
+ *                    z = seed + 0x9E3779B97F4A7C15 * (g + 1);  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                    z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z = z ^ (z >> 31);  tie = ((z >> 32) * (m + 1)) >> 32
+ *                  (splitmix64 of (seed, g); one of 0 ... m, 0 when m = 0): random tie-breaking that is a pure function of
+ *                  (seed, g, m) and so does not depend on how the samples were split into calls.
+ *   covered_j[e] = [y <= Q_j] for the nq <= 32 probabilities q_host[j] in [0, 1], Q_j the fp32 'linear' quantile that
+ *                  dl4ds_ensemble_reduce writes.
+ * Folds over the valid elements (each may be null; the per-element outputs too):
+ *   sample_out_dev [B][4]: fp64 sums of crps, sqerr, var over sample b and its valid count, overwritten;
+ *   cell_acc_dev [4][per]: the same four per cell, ADDED ONTO the accumulators, samples in ascending order, so that the result
+ *                  after all calls does not depend on the number of samples per call;
+ *   rank_hist_dev [K + 1], covered_dev [nq] (required when nq > 0): 64-bit counts, ADDED (integer atomics).
+ * The accumulators are zeroed by the caller (dl4ds_memset).  No floating-point atomics: a repeated call gives the same bits.
+ * Algorithmic traffic (K + 1) * 4 * n bytes read plus a hand-over of five 4-byte words per element written and read once. */
+int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                         unsigned long long elem_offset, const float* scale_dev, int fair, unsigned long long seed,
+                         const float* q_host, int nq, float* crps_dev, float* sqerr_dev, float* var_dev, int* rank_dev,
+                         double* sample_out_dev, double* cell_acc_dev, unsigned long long* rank_hist_dev,
+                         unsigned long long* covered_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
