@@ -581,6 +581,15 @@ int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t me
                    ws);
     API_END
 }
+int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
+              const int* windows_host, int n_windows, long long* sums_dev, long long* cont_dev, long long* valid_dev) {
+    API_BEGIN
+    fss_check_args(N, H, W, C, thresholds_host, T, windows_host, n_windows);        // before the workspace is sized
+    const size_t ws = fss_workspace_bytes(N, H, W, C, T);
+    fss(S(), y_dev, p_dev, N, H, W, C, thresholds_host, T, windows_host, n_windows, sums_dev, cont_dev, valid_dev,
+        ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

@@ -158,6 +158,14 @@ void ensemble_score(hipStream_t s, const float* members, size_t K, size_t n, siz
                     unsigned long long elem_offset, const float* scale, int fair, unsigned long long seed, const float* q_host, int nq,
                     float* crps, float* sqerr, float* var, int* rank, double* sample_out, double* cell_acc,
                     unsigned long long* rank_hist, unsigned long long* covered, void* workspace, size_t workspace_bytes);
+// Neighbourhood verification (fss.hip) of the N*C fields of y, p (N, H, W, C) at T thresholds and S window sizes (host arrays):
+// sums [N][C][T][S][3] = the exact integer sums D, F, O of the Fractions Skill Score, cont [N][C][T][4] = hits, misses, false
+// alarms, correct negatives over the valid (both finite) cells, valid [N][C] their count.  Outputs are overwritten.  Integer
+// arithmetic only: equal to a reference, whatever the order of the atomics.  fss_check_args throws on a bad or overflowing request.
+size_t fss_workspace_bytes(int N, int H, int W, int C, int T);
+void fss_check_args(int N, int H, int W, int C, const float* thresholds, int T, const int* windows, int S);
+void fss(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T,
+         const int* windows, int S, long long* sums, long long* cont, long long* valid, void* workspace, size_t workspace_bytes);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

@@ -1,6 +1,8 @@
 """compute_metrics, compute_rmse and compute_correlation of dl4ds/metrics.py:15-330 without the plotting: the per-pair and
 per-grid-point test metrics are reduced on the device (`dl4ds_metrics`), Spearman rank correlations are computed by the
-segmented rank engine (`dl4ds_spearman`, csrc/rank.hip), the summary statistics the reference prints are assembled here."""
+segmented rank engine (`dl4ds_spearman`, csrc/rank.hip), the summary statistics the reference prints are assembled here.
+`neighbourhood_scores` / `fss` (no counterpart in the reference): Fractions Skill Score and contingency scores per threshold and
+neighbourhood size from the exact integer sums of `dl4ds_fss` (csrc/fss.hip)."""
 import numpy as np
 
 from . import _lib
@@ -227,3 +229,165 @@ def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None
         scorer.free()
         stack.free()
         dev_obs.free()
+
+
+FSS_DEFAULT_WINDOWS = (1, 3, 5, 9, 17, 33, 65)
+FSS_SUM_BOUND = 1 << 62                            # H*W*m^2 must stay below it: the 64-bit sums of dl4ds_fss are exact
+FSS_CELL_BOUND = 1 << 31
+
+
+def check_neighbourhood_args(shape, thresholds, windows, batch_size=None):
+    """Validation of `neighbourhood_scores` (no library call) -> (thresholds as float32 (T,), windows as int32 (S,))."""
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f'expected non-empty (N, H, W, C) arrays, got shape {tuple(shape)}')
+    _, h, w, _ = (int(v) for v in shape)
+    t64 = np.atleast_1d(np.asarray(thresholds, np.float64))
+    if t64.ndim != 1 or t64.size == 0:
+        raise ValueError('`thresholds` must be a non-empty 1-D sequence')
+    with np.errstate(over='ignore'):
+        thr = t64.astype(np.float32)
+    if not np.isfinite(t64).all() or not np.isfinite(thr).all():
+        raise ValueError('`thresholds` must be finite (as float32)')
+    if not (np.diff(thr) > 0).all():
+        raise ValueError('`thresholds` must be strictly increasing as float32 values')
+    win = np.atleast_1d(np.asarray(windows))
+    if win.ndim != 1 or win.size == 0:
+        raise ValueError('`windows` must be a non-empty 1-D sequence')
+    if win.dtype == bool or not np.issubdtype(win.dtype, np.integer):
+        raise ValueError('`windows` must be integers')
+    wl = [int(v) for v in win]
+    if min(wl) < 1 or max(wl) >= 1 << 31:
+        raise ValueError('`windows` must be positive (and below 2^31)')
+    if any(b <= a for a, b in zip(wl, wl[1:])):
+        raise ValueError('`windows` must be strictly increasing')
+    if h * w >= FSS_CELL_BOUND:
+        raise ValueError(f'fields of H*W = {h * w} cells are not supported: H*W must stay below 2^31')
+    for n in wl:
+        m = min(n, h) * min(n, w)
+        if h * w * m * m >= FSS_SUM_BOUND:
+            raise ValueError(f'window {n} on a {h} x {w} field: H*W*m^2 = {h * w * m * m} with m = min(n, H)*min(n, W) = {m} '
+                             'must stay below 2^62 for the exact 64-bit sums')
+    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
+        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    return thr, np.asarray(wl, np.int32)
+
+
+def _ratio(num, den):
+    """num / den in fp64, NaN where den == 0 (arrays of integers, or Python integers)."""
+    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return np.where(den == 0, np.nan, num / np.where(den == 0, 1.0, den))
+
+
+def _contingency_scores(hits, misses, fa, nvalid):
+    """POD, FAR, CSI, ETS, frequency bias from integer counts (int64 arrays, or object arrays of Python integers)."""
+    to = lambda a: np.asarray(a, np.float64)
+    obs, fc = hits + misses, hits + fa
+    hr = _ratio(to(obs) * to(fc), nvalid)                              # hits expected by chance
+    ets_den = to(hits + misses + fa) - hr
+    with np.errstate(invalid='ignore'):
+        ets = np.where(np.isnan(hr) | (ets_den == 0), np.nan, (to(hits) - hr) / np.where(ets_den == 0, 1.0, ets_den))
+    return dict(pod=_ratio(hits, obs), far=_ratio(fa, fc), csi=_ratio(hits, hits + misses + fa), ets=ets, bias=_ratio(fc, obs))
+
+
+def _pysum(a, axis):
+    """Sum of an int64 array over `axis` as Python integers (object array): cannot overflow."""
+    return np.sum(a.astype(object), axis=axis)
+
+
+def neighbourhood_scores(y_test, y_test_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=None, batch_size=None):
+    """Scale- and threshold-dependent verification of (N, H, W, C) predictions on the device (csrc/fss.hip): the Fractions Skill
+    Score (Roberts & Lean 2008) per field, exceedance threshold and neighbourhood size, and the categorical contingency scores at
+    the same thresholds.  Every one of the N*C planes is one field.  Inputs are prepared as in `compute_metrics` (5-D squeezed,
+    optional ``scaler.inverse_transform``) and read as float32; ``thresholds`` are cast to float32.  A cell is valid when both
+    arrays are finite there and ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it; an event is ``value >= threshold``
+    on a valid cell.  The window of size n at (i, j) is rows [i - n//2, i - n//2 + n), columns likewise, clipped to the field
+    (``scipy.ndimage.uniform_filter(mode='constant')`` times n^2, even n included).  The device returns exact int64 sums, so the
+    result equals an integer reference and does not depend on ``batch_size`` (samples per upload; default: chunks of at most 256 MiB
+    per array).  Returns a dict:
+
+    * ``sums`` (N, C, T, S, 3) int64: D = sum (cf - co)^2, F = sum cf^2, O = sum co^2 of the window counts over all cells;
+      ``fss`` (N, C, T, S) = 1 - D / (F + O) (NaN when F + O = 0), ``fss_pooled`` (T, S) and ``fss_pooled_per_channel``
+      (C, T, S) = 1 - sum D / sum (F + O) over the fields;
+    * ``hits``, ``misses``, ``false_alarms``, ``correct_negatives`` (N, C, T) int64 and ``n_valid`` (N, C);
+    * ``pod``, ``far``, ``csi``, ``ets``, ``bias`` (N, C, T) and pooled over all fields as ``pod_pooled`` ... (T,), NaN on a zero
+      denominator;
+    * ``base_rate`` = ``fss_random`` (T,): the pooled observed event frequency, ``fss_useful`` = 0.5 + base_rate / 2 and
+      ``useful_window`` (T,): the smallest requested window whose pooled FSS reaches it, or -1;
+    * ``thresholds`` (float32) and ``windows`` as used."""
+    y_test, y_test_hat = np.asarray(getattr(y_test, 'values', y_test)), np.asarray(getattr(y_test_hat, 'values', y_test_hat))
+    if y_test.ndim == 5:
+        y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
+    y_test, y_test_hat = checkarray_ndim(y_test, 4, -1), checkarray_ndim(y_test_hat, 4, -1)
+    if y_test.shape != y_test_hat.shape or y_test.ndim != 4:
+        raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y_test.shape} and {y_test_hat.shape}')
+    thr, win = check_neighbourhood_args(y_test.shape, thresholds, windows, batch_size)
+    if scaler is not None and hasattr(scaler, 'inverse_transform'):
+        y_test, y_test_hat = scaler.inverse_transform(y_test), scaler.inverse_transform(y_test_hat)
+    obs = _masked_observation(y_test, mask)
+    N, H, W, C = obs.shape
+    T, S = len(thr), len(win)
+    per = H * W * C
+    if batch_size is None:
+        batch_size = max(1, (1 << 26) // per)
+    bmax = max(min(int(batch_size), N), 1)
+    sums = np.empty((N, C, T, S, 3), np.int64)
+    cont = np.empty((N, C, T, 4), np.int64)
+    nvalid = np.empty((N, C), np.int64)
+    lib = _lib.lib()
+    dy, dp = DeviceArray((bmax * per,)), DeviceArray((bmax * per,))
+    dsums, dcont, dvalid = (DeviceArray((bmax,) + a.shape[1:], np.int64) for a in (sums, cont, nvalid))
+    try:
+        for i in range(0, N, bmax):
+            b = min(bmax, N - i)
+            part = np.ascontiguousarray(y_test_hat[i:i + b], np.float32)
+            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, obs[i:i + b].ctypes.data, b * per * 4))
+            _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part.ctypes.data, b * per * 4))
+            _lib.check(lib.dl4ds_fss(dy.ptr, dp.ptr, b, H, W, C, thr.ctypes.data, T, win.ctypes.data, S, dsums.ptr, dcont.ptr,
+                                     dvalid.ptr))
+            for host, dev in ((sums, dsums), (cont, dcont), (nvalid, dvalid)):
+                _lib.check(lib.dl4ds_memcpy_d2h(host[i:i + b].ctypes.data, dev.ptr, host[i:i + b].nbytes))
+    finally:
+        for d in (dy, dp, dsums, dcont, dvalid):
+            d.free()
+    return scores_from_counts(sums, cont, nvalid, thr, win)
+
+
+def scores_from_counts(sums, cont, nvalid, thresholds, windows):
+    """The result dict of `neighbourhood_scores` from the integer outputs of `dl4ds_fss` (host arithmetic only)."""
+    sums, cont, nvalid = np.asarray(sums, np.int64), np.asarray(cont, np.int64), np.asarray(nvalid, np.int64)
+    D, FO = sums[..., 0], sums[..., 1] + sums[..., 2]                  # F + O < 2^63 by the overflow rule
+    res = dict(sums=sums, fss=1.0 - _ratio(D, FO), n_valid=nvalid, thresholds=np.asarray(thresholds, np.float32),
+               windows=np.asarray(windows, np.int64))
+    so = sums.astype(object)
+    res['fss_pooled'] = 1.0 - _ratio_exact(np.sum(so[..., 0], axis=(0, 1)), np.sum(so[..., 1] + so[..., 2], axis=(0, 1)))
+    res['fss_pooled_per_channel'] = 1.0 - _ratio_exact(np.sum(so[..., 0], axis=0), np.sum(so[..., 1] + so[..., 2], axis=0))
+    hits, misses, fa, cn = (cont[..., k] for k in range(4))
+    res.update(hits=hits, misses=misses, false_alarms=fa, correct_negatives=cn)
+    res.update(_contingency_scores(hits, misses, fa, nvalid[..., None]))
+    ph, pm, pf = (_pysum(a, (0, 1)) for a in (hits, misses, fa))
+    pn = int(_pysum(nvalid, (0, 1)))
+    for k, v in _contingency_scores(ph, pm, pf, np.full(ph.shape, pn, object)).items():
+        res[k + '_pooled'] = v
+    base = _ratio_exact(ph + pm, np.full(ph.shape, pn, object))
+    res.update(base_rate=base, fss_random=base.copy(), fss_useful=0.5 + base / 2.0)
+    with np.errstate(invalid='ignore'):
+        reach = res['fss_pooled'] >= res['fss_useful'][:, None]       # NaN compares false
+    res['useful_window'] = np.where(reach.any(1), res['windows'][np.argmax(reach, 1)], -1).astype(np.int64)
+    return res
+
+
+def _ratio_exact(num, den):
+    """Element-wise num / den of object arrays of Python integers, each quotient correctly rounded to fp64; NaN where den == 0."""
+    num, den = np.asarray(num, object), np.asarray(den, object)
+    out = np.full(num.shape, np.nan)
+    for idx in np.ndindex(num.shape):
+        if den[idx] != 0:
+            out[idx] = int(num[idx]) / int(den[idx])
+    return out
+
+
+def fss(y, y_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=None, batch_size=None):
+    """``(fss, fss_pooled)`` of `neighbourhood_scores`: the Fractions Skill Score per field (N, C, T, S) and pooled (T, S)."""
+    r = neighbourhood_scores(y, y_hat, thresholds, windows, scaler=scaler, mask=mask, batch_size=batch_size)
+    return r['fss'], r['fss_pooled']

@@ -219,6 +219,22 @@ int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t me
                          const float* q_host, int nq, float* crps_dev, float* sqerr_dev, float* var_dev, int* rank_dev,
                          double* sample_out_dev, double* cell_acc_dev, unsigned long long* rank_hist_dev,
                          unsigned long long* covered_dev);
+/* Neighbourhood (scale- and threshold-dependent) verification of a prediction against an observation: the Fractions Skill Score
+ * of Roberts & Lean (2008) and the 2 x 2 contingency table.  The reference has no such metric; the definitions are DESIGN.md
+ * section 14.  y_dev / p_dev: observation and prediction, (N, H, W, C) fp32; each of the N*C planes is one field.
+ * thresholds_host [T] (finite), windows_host [S] (>= 1): HOST arrays.  A cell is VALID iff y and p are both finite there: NaN in
+ * y_dev is the masking mechanism.  bo = valid & (y >= t), bf = valid & (p >= t).  The window of size n at cell (i, j) is rows
+ * [i - n/2, i - n/2 + n), columns likewise, clipped to the field (scipy.ndimage.uniform_filter(mode='constant') * n^2, even n
+ * included; windows larger than the field are legal); co, cf are the counts of bo, bf in it.  All outputs are overwritten:
+ *   sums_dev  [N][C][T][S][3]  D = sum (cf - co)^2, F = sum cf^2, O = sum co^2 over all H*W cells; FSS = 1 - D / (F + O)
+ *   cont_dev  [N][C][T][4]     hits, misses, false alarms, correct negatives over the valid cells
+ *   valid_dev [N][C]           number of valid cells
+ * Integer arithmetic only (64-bit sums, integer atomics): the result equals an integer reference and a repeated call gives the
+ * same bits.  Refused (non-zero return, dl4ds_last_error) unless H*W < 2^31 and, for every window, H*W*m^2 < 2^62 with
+ * m = min(n, H) * min(n, W).  Algorithmic traffic: 8 B per cell read once, then 2-byte row prefixes (4-byte when W > 65535):
+ * 4 T per cell written once, 16 T per cell and window read, mostly from cache. */
+int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
+              const int* windows_host, int S, long long* sums_dev, long long* cont_dev, long long* valid_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
