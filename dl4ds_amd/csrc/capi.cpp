@@ -590,6 +590,16 @@ int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C
         ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, size_t L, size_t seg_stride, size_t elem_stride,
+                       const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
+                       long long* ks_dev, long long* hist_dev, long long* valid_dev) {
+    API_BEGIN
+    distribution_check_args(n_seg, L, q_host, Q, edges_host, E);                     // before the workspace is sized
+    const size_t ws = distribution_workspace_bytes(n_seg, L, seg_stride, elem_stride);
+    distribution(S(), y_dev, p_dev, n_seg, L, seg_stride, elem_stride, q_host, Q, edges_host, E, quant_dev, w1_dev, ks_dev, hist_dev,
+                 valid_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

@@ -166,6 +166,15 @@ size_t fss_workspace_bytes(int N, int H, int W, int C, int T);
 void fss_check_args(int N, int H, int W, int C, const float* thresholds, int T, const int* windows, int S);
 void fss(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T,
          const int* windows, int S, long long* sums, long long* cont, long long* valid, void* workspace, size_t workspace_bytes);
+// Distribution verification (distribution.hip) of S pairs of length-L segments, element k of segment s at [s*seg_stride +
+// k*elem_stride]: per segment quant [S][2][Q] (numpy 'linear' quantiles of the valid values of y, p), w1 [S] (1-Wasserstein), ks [S]
+// (n times the two-sample KS statistic), hist [S][2][E-1] (np.histogram over the E edges; may be null when E == 0), valid [S] (n).
+// q / edges are host arrays.  Outputs are overwritten.  distribution_check_args throws on a request the entry refuses.
+size_t distribution_workspace_bytes(size_t S, size_t L, size_t seg_stride, size_t elem_stride);
+void distribution_check_args(size_t S, size_t L, const double* q, int Q, const float* edges, int E);
+void distribution(hipStream_t s, const float* y, const float* p, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
+                  const double* q, int Q, const float* edges, int E, double* quant, double* w1, long long* ks, long long* hist,
+                  long long* valid, void* workspace, size_t workspace_bytes);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "ops.h"
 #include "prof.h"
+#include "sort_keys.h"
 #include <algorithm>
 
 namespace {
@@ -33,26 +34,7 @@ constexpr int RK_THREADS = 256;                        // global engine: threads
 constexpr int RK_TILE = 4096;                          // global engine: elements per tile
 constexpr int RK_WAVES = RK_THREADS / 64;
 constexpr int RK_WAVE_SPAN = RK_TILE / RK_WAVES;       // 1024 consecutive elements per wave, 16 chunks of 64
-constexpr int RK_RADIX = 256;
 constexpr size_t RK_WS_BUDGET = size_t(128) << 20;     // workspace of the global engine (one chunk of pairs)
-
-__device__ __forceinline__ uint32_t rank_key(float v) {
-    uint32_t u = __float_as_uint(v);
-    if (u == 0x80000000u) u = 0u;                      // -0.0 == +0.0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// first position in sorted k[0, n) whose key is >= x (LB) or > x (!LB)
-template <bool LB, typename P>
-__device__ __forceinline__ uint32_t bound(P k, uint32_t n, uint32_t x) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        const uint32_t v = k[mid];
-        if (LB ? (v < x) : (v <= x)) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ double rho_from(double sab, double saa, double sbb, bool nan, size_t L) {
     if (nan || L < 2) return __builtin_nan("");
@@ -146,17 +128,6 @@ __global__ void __launch_bounds__(lds_threads<P>()) spearman_lds_kernel(const fl
 // Chunk-local layout: pair i of the chunk owns elements [i*L, (i+1)*L) of every per-element buffer and tiles
 // [i*ntiles, (i+1)*ntiles) of every per-tile buffer.  blockIdx.x = tile, blockIdx.y = pair of the chunk.
 
-// the 64-bit mask of the lanes of this wave that are valid and carry the same 8-bit digit as this one
-__device__ __forceinline__ uint64_t match_digit(uint32_t d, bool valid) {
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-        const uint64_t bl = __ballot((d >> bit) & 1u);
-        m &= ((d >> bit) & 1u) ? bl : ~bl;
-    }
-    return m;
-}
-
 template <bool FROM_INPUT>
 __device__ __forceinline__ uint32_t load_key(const float* __restrict__ src, const uint32_t* __restrict__ kin, size_t seg, size_t L,
                                              size_t ss, size_t es, size_t pos, int& nan) {
@@ -197,29 +168,6 @@ __global__ void __launch_bounds__(RK_THREADS) spearman_hist_kernel(const float* 
         if (!side_b) nanflag[seg * ntiles + tile] = (uint32_t)nan_any;
         else if (nan_any) nanflag[seg * ntiles + tile] = 1u;
     }
-}
-
-// per pair: hist -> exclusive scatter offsets, digit-major then tile: off[t][d] = sum_{d' < d} total[d'] + sum_{t' < t} hist[t'][d]
-__global__ void __launch_bounds__(RK_THREADS) spearman_scan_kernel(uint32_t* __restrict__ hist, int ntiles) {
-    __shared__ uint32_t tot[RK_RADIX];
-    const int d = threadIdx.x;
-    uint32_t* h = hist + (size_t)blockIdx.x * ntiles * RK_RADIX + d;
-    uint32_t run = 0;
-    for (int t = 0; t < ntiles; ++t) {
-        const uint32_t v = h[(size_t)t * RK_RADIX];
-        h[(size_t)t * RK_RADIX] = run;
-        run += v;
-    }
-    tot[d] = run;
-    __syncthreads();
-    for (int s = 1; s < RK_RADIX; s <<= 1) {           // inclusive Hillis-Steele scan of the digit totals
-        const uint32_t x = d >= s ? tot[d - s] : 0u;
-        __syncthreads();
-        tot[d] += x;
-        __syncthreads();
-    }
-    const uint32_t base = tot[d] - run;
-    for (int t = 0; t < ntiles; ++t) h[(size_t)t * RK_RADIX] += base;
 }
 
 // stable scatter of one pass: wave w ranks its 1024 consecutive elements per digit in order (chunks of 64, lanes in order by the
@@ -332,8 +280,6 @@ __global__ void spearman_finish_kernel(const double* __restrict__ part, const ui
     out[seg] = rho_from(sab, saa, sbb, nan, L);
 }
 
-inline size_t al256(size_t b) { return (b + 255) & ~size_t(255); }
-
 struct Chunk {
     size_t pairs, ntiles, elems;                       // pairs per chunk, tiles per pair, elements per pair
     size_t bytes_per_pair() const {
@@ -400,7 +346,7 @@ void spearman(hipStream_t s, const float* a, const float* b, size_t S, size_t L,
             // pass 0 reads the floats (keys made on the fly, index = position) -> (k1, i1); then k1 -> k0 -> k1 -> k0
             DL4DS_LAUNCH(spearman_hist_kernel<true>, grid, dim3(RK_THREADS), 0, s, src, nullptr, L, seg_stride, elem_stride, 0, side,
                          hist, nanflag);
-            DL4DS_LAUNCH(spearman_scan_kernel, dim3((unsigned)np), dim3(RK_THREADS), 0, s, hist, nt);
+            DL4DS_LAUNCH(radix_scan_kernel, dim3((unsigned)np), dim3(RK_THREADS), 0, s, hist, nt);
             DL4DS_LAUNCH(spearman_scatter_kernel<true>, grid, dim3(RK_THREADS), 0, s, src, nullptr, nullptr, L, seg_stride, elem_stride,
                          0, hist, k1, i1);
             for (int pass = 1; pass < 4; ++pass) {
@@ -410,7 +356,7 @@ void spearman(hipStream_t s, const float* a, const float* b, size_t S, size_t L,
                 uint32_t* iout = (pass & 1) ? i0 : i1;
                 DL4DS_LAUNCH(spearman_hist_kernel<false>, grid, dim3(RK_THREADS), 0, s, nullptr, kin, L, size_t(0), size_t(0),
                              8 * pass, side, hist, nanflag);
-                DL4DS_LAUNCH(spearman_scan_kernel, dim3((unsigned)np), dim3(RK_THREADS), 0, s, hist, nt);
+                DL4DS_LAUNCH(radix_scan_kernel, dim3((unsigned)np), dim3(RK_THREADS), 0, s, hist, nt);
                 DL4DS_LAUNCH(spearman_scatter_kernel<false>, grid, dim3(RK_THREADS), 0, s, nullptr, kin, iin, L, size_t(0), size_t(0),
                              8 * pass, hist, kout, iout);
             }

@@ -2,7 +2,9 @@
 per-grid-point test metrics are reduced on the device (`dl4ds_metrics`), Spearman rank correlations are computed by the
 segmented rank engine (`dl4ds_spearman`, csrc/rank.hip), the summary statistics the reference prints are assembled here.
 `neighbourhood_scores` / `fss` (no counterpart in the reference): Fractions Skill Score and contingency scores per threshold and
-neighbourhood size from the exact integer sums of `dl4ds_fss` (csrc/fss.hip)."""
+neighbourhood size from the exact integer sums of `dl4ds_fss` (csrc/fss.hip).
+`distribution_scores` / `quantile_maps` (no counterpart either): sample quantiles, 1-Wasserstein distance, Kolmogorov-Smirnov
+statistic, histograms and Perkins skill score per grid cell or per sample from `dl4ds_distribution` (csrc/distribution.hip)."""
 import numpy as np
 
 from . import _lib
@@ -391,3 +393,150 @@ def fss(y, y_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=Non
     """``(fss, fss_pooled)`` of `neighbourhood_scores`: the Fractions Skill Score per field (N, C, T, S) and pooled (T, S)."""
     r = neighbourhood_scores(y, y_hat, thresholds, windows, scaler=scaler, mask=mask, batch_size=batch_size)
     return r['fss'], r['fss_pooled']
+
+
+DIST_DEFAULT_QUANTILES = (0.01, 0.05, 0.25, 0.5, 0.75, 0.95, 0.99)
+DIST_MAX_QUANTILES = 64                            # caps of dl4ds_distribution: q and the edges travel as kernel arguments
+DIST_MAX_EDGES = 257
+DIST_LENGTH_BOUND = 1 << 31
+
+
+def check_distribution_args(shape, quantiles, bins=None, over='time', batch_size=None):
+    """Validation of `distribution_scores` (no library call) -> (quantiles as float64 (Q,), bin edges as float32 (E,) or None)."""
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f'expected non-empty (N, H, W, C) arrays, got shape {tuple(shape)}')
+    _check_over(over)
+    n, h, w, c = (int(v) for v in shape)
+    length = n if over == 'time' else h * w * c
+    if length >= DIST_LENGTH_BOUND:
+        raise ValueError(f'segments of {length} elements are not supported: the length must stay below 2^31')
+    q = np.asarray(quantiles, np.float64)
+    if q.ndim == 0:
+        q = q.reshape(1)
+    if q.ndim != 1:
+        raise ValueError('`quantiles` must be a 1-D sequence')
+    if q.size > DIST_MAX_QUANTILES:
+        raise ValueError(f'at most {DIST_MAX_QUANTILES} quantiles are supported, got {q.size}')
+    if not ((q >= 0.0) & (q <= 1.0)).all():                            # NaN compares false
+        raise ValueError('`quantiles` must lie in [0, 1]')
+    edges = None
+    if bins is not None:
+        b64 = np.asarray(bins, np.float64)
+        if b64.ndim != 1 or b64.size < 2:
+            raise ValueError('`bins` must be a 1-D sequence of at least two bin edges')
+        if b64.size > DIST_MAX_EDGES:
+            raise ValueError(f'at most {DIST_MAX_EDGES} bin edges are supported, got {b64.size}')
+        with np.errstate(over='ignore'):
+            edges = b64.astype(np.float32)
+        if not np.isfinite(b64).all() or not np.isfinite(edges).all():
+            raise ValueError('`bins` must be finite (as float32)')
+        if not (np.diff(edges) > 0).all():
+            raise ValueError('`bins` must be strictly increasing as float32 values')
+    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
+        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    return np.ascontiguousarray(q), edges
+
+
+def distribution_from_counts(quant, w1, ks_count, hist, nvalid, quantiles, bins):
+    """The result dict of `distribution_scores` from the outputs of `dl4ds_distribution` (host arithmetic only): ``quant``
+    (..., 2, Q), ``w1``, ``ks_count``, ``nvalid`` (...), ``hist`` (..., 2, B) or None."""
+    quant, nvalid = np.asarray(quant, np.float64), np.asarray(nvalid, np.int64)
+    ks_count = np.asarray(ks_count, np.int64)
+    res = dict(n_valid=nvalid, q_obs=quant[..., 0, :], q_pred=quant[..., 1, :], q_bias=quant[..., 1, :] - quant[..., 0, :],
+               wasserstein=np.asarray(w1, np.float64), ks_count=ks_count, ks=_ratio(ks_count, nvalid),
+               quantiles=np.asarray(quantiles, np.float64), bins=None)
+    if hist is not None:
+        hist = np.asarray(hist, np.int64)
+        ho, hp = hist[..., 0, :], hist[..., 1, :]
+        lead = tuple(range(nvalid.ndim))
+        po, pp = np.atleast_1d(_pysum(ho, lead)), np.atleast_1d(_pysum(hp, lead))
+        common = sum(min(int(a), int(b)) for a, b in zip(po, pp))
+        total = sum(int(v) for v in nvalid.ravel())
+        res.update(hist_obs=ho, hist_pred=hp, perkins=_ratio(np.minimum(ho, hp).sum(-1), nvalid),
+                   hist_obs_pooled=po.astype(np.int64), hist_pred_pooled=pp.astype(np.int64),
+                   perkins_pooled=_ratio_exact(common, total)[()], bins=np.asarray(bins, np.float32))
+    return res
+
+
+def distribution_scores(y_test, y_test_hat, quantiles=DIST_DEFAULT_QUANTILES, bins=None, over='time', scaler=None, mask=None,
+                        batch_size=None):
+    """Does the prediction have the observation's distribution?  Per segment, on the device (csrc/distribution.hip): the sample
+    quantiles of both (N, H, W, C) arrays, their 1-Wasserstein distance, the two-sample Kolmogorov-Smirnov statistic and, with
+    ``bins`` (bin edges, cast to float32), both histograms and the Perkins skill score.  ``over='time'``: one segment per grid cell
+    and channel over the N samples, results shaped (H, W, C) + ...; ``over='space'``: one segment per sample over its H*W*C values,
+    results shaped (N,) + ... (the convention of `spearman`).  Inputs are prepared as in `neighbourhood_scores` (5-D squeezed,
+    optional ``scaler.inverse_transform``) and read as float32.  An element is valid when both arrays are finite there and
+    ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it; invalid elements leave both samples, so both have ``n_valid``
+    values.  Quantiles are numpy's ``method='linear'`` in fp64; histogram bins are [e_b, e_b+1), the last one closed on the right
+    (``np.histogram``), values outside the edges are counted nowhere.  The arrays are uploaded in chunks of at most 256 MiB each
+    (``batch_size``: grid rows per upload for 'time', samples for 'space'); the result does not depend on it.  Returns a dict:
+
+    * ``n_valid`` int64; ``q_obs``, ``q_pred``, ``q_bias`` = q_pred - q_obs (..., Q); ``wasserstein``;
+    * ``ks_count`` int64 = n_valid times the KS statistic, ``ks`` = ks_count / n_valid;
+    * with ``bins``: ``hist_obs``, ``hist_pred`` (..., B) int64, ``perkins`` = sum_b min(hist_obs, hist_pred) / n_valid, and
+      pooled over all segments ``hist_obs_pooled``, ``hist_pred_pooled`` (B,), ``perkins_pooled``;
+    * ``quantiles`` (float64) and ``bins`` (float32, or None) as used.  Every ratio is NaN where ``n_valid == 0``."""
+    y_test, y_test_hat = np.asarray(getattr(y_test, 'values', y_test)), np.asarray(getattr(y_test_hat, 'values', y_test_hat))
+    if y_test.ndim == 5:
+        y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
+    y_test, y_test_hat = checkarray_ndim(y_test, 4, -1), checkarray_ndim(y_test_hat, 4, -1)
+    if y_test.shape != y_test_hat.shape or y_test.ndim != 4:
+        raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y_test.shape} and {y_test_hat.shape}')
+    q, edges = check_distribution_args(y_test.shape, quantiles, bins, over, batch_size)
+    if scaler is not None and hasattr(scaler, 'inverse_transform'):
+        y_test, y_test_hat = scaler.inverse_transform(y_test), scaler.inverse_transform(y_test_hat)
+    obs = _masked_observation(y_test, mask)
+    N, H, W, C = obs.shape
+    Q, E = len(q), 0 if edges is None else len(edges)
+    if over == 'time':
+        lead, units, unit = (H, W, C), H, W * C                            # uploaded in bands of rows: `unit` segments per row
+        per_unit = N * W * C
+    else:
+        lead, units, unit = (N,), N, 1                                     # uploaded in blocks of samples: one segment each
+        per_unit = H * W * C
+    if batch_size is None:
+        batch_size = max(1, (1 << 26) // per_unit)
+    bmax = max(min(int(batch_size), units), 1)
+    segs = units * unit
+    quant = np.empty((segs, 2, Q), np.float64)
+    w1 = np.empty((segs,), np.float64)
+    ks, nvalid = np.empty((segs,), np.int64), np.empty((segs,), np.int64)
+    hist = np.empty((segs, 2, E - 1), np.int64) if E else None
+    lib = _lib.lib()
+    dy, dp = DeviceArray((bmax * per_unit,)), DeviceArray((bmax * per_unit,))
+    dquant, dw1 = DeviceArray((bmax * unit, 2, max(Q, 1)), np.float64), DeviceArray((bmax * unit,), np.float64)
+    dks, dvalid = DeviceArray((bmax * unit,), np.int64), DeviceArray((bmax * unit,), np.int64)
+    dhist = DeviceArray((bmax * unit, 2, E - 1), np.int64) if E else None
+    try:
+        for i in range(0, units, bmax):
+            b = min(bmax, units - i)
+            if over == 'time':
+                part_y = np.ascontiguousarray(obs[:, i:i + b])
+                part_p = np.ascontiguousarray(y_test_hat[:, i:i + b], np.float32)
+                s, length, seg_stride, elem_stride = b * unit, N, 1, b * unit
+            else:
+                part_y = obs[i:i + b]
+                part_p = np.ascontiguousarray(y_test_hat[i:i + b], np.float32)
+                s, length, seg_stride, elem_stride = b, per_unit, per_unit, 1
+            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, part_y.ctypes.data, part_y.nbytes))
+            _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part_p.ctypes.data, part_p.nbytes))
+            _lib.check(lib.dl4ds_distribution(dy.ptr, dp.ptr, s, length, seg_stride, elem_stride, q.ctypes.data, Q,
+                                              edges.ctypes.data if E else None, E, dquant.ptr, dw1.ptr, dks.ptr,
+                                              dhist.ptr if E else None, dvalid.ptr))
+            s0 = i * unit
+            outs = [(quant, dquant), (w1, dw1), (ks, dks), (nvalid, dvalid)] + ([(hist, dhist)] if E else [])
+            for host, dev in outs:
+                if host[s0:s0 + s].nbytes:
+                    _lib.check(lib.dl4ds_memcpy_d2h(host[s0:s0 + s].ctypes.data, dev.ptr, host[s0:s0 + s].nbytes))
+    finally:
+        for d in (dy, dp, dquant, dw1, dks, dvalid, dhist):
+            if d is not None:
+                d.free()
+    return distribution_from_counts(quant.reshape(lead + (2, Q)), w1.reshape(lead), ks.reshape(lead),
+                                    None if hist is None else hist.reshape(lead + (2, E - 1)), nvalid.reshape(lead), q, edges)
+
+
+def quantile_maps(y, y_hat, quantiles, over='time', scaler=None, mask=None):
+    """``(q_obs, q_pred)`` of `distribution_scores`: the sample quantiles of observation and prediction per segment, (..., Q)."""
+    r = distribution_scores(y, y_hat, quantiles, over=over, scaler=scaler, mask=mask)
+    return r['q_obs'], r['q_pred']

@@ -235,6 +235,31 @@ int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t me
  * 4 T per cell written once, 16 T per cell and window read, mostly from cache. */
 int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
               const int* windows_host, int S, long long* sums_dev, long long* cont_dev, long long* valid_dev);
+/* Distribution verification of a prediction against an observation: per segment the sample quantiles of either side, the
+ * 1-Wasserstein distance, the two-sample Kolmogorov-Smirnov statistic, a histogram of either side and the valid count.  The
+ * reference has no such metric; the definitions are DESIGN.md section 15.  Element k of segment s of either array lives at
+ * base[s*seg_stride + k*elem_stride] (as dl4ds_spearman): per sample over its values (S = N, L = H*W*C, contiguous) or per grid
+ * cell over the samples (S = H*W*C, L = N, seg_stride 1, elem_stride H*W*C).  q_host [Q] (0 <= Q <= 64, each in [0, 1]) and
+ * edges_host [E] (E = 0, or 2 <= E <= 257 finite, strictly increasing) are HOST arrays.  Per segment:
+ *   an element is VALID iff y and p are both finite there (NaN in y_dev is the masking mechanism); invalid elements are dropped
+ *   from both sides, so both samples have n <= L values; -0.0 counts as +0.0.  With a, b the ascending valid values of y, p:
+ *   quant_dev [S][2][Q]   (obs, pred) numpy method='linear': h = q*(n-1), j = floor(h), x[j] + (x[min(j+1, n-1)] - x[j]) * (h - j)
+ *                         in fp64 on the float32 values, multiply and add not fused; NaN when n = 0
+ *   w1_dev    [S]         (1/n) sum |a[i] - b[i]| in fp64: the 1-Wasserstein distance of two equal-size samples; NaN when n = 0
+ *   ks_dev    [S]         max over every valid value v of either side of |#{a <= v} - #{b <= v}|: n times the two-sample
+ *                         Kolmogorov-Smirnov statistic, an exact integer; 0 when n = 0
+ *   hist_dev  [S][2][E-1] number of valid values in [e_b, e_b+1), the last bin closed on the right (np.histogram); values outside
+ *                         the edges are counted nowhere; may be null when E == 0
+ *   valid_dev [S]         n
+ * All outputs are overwritten.  No float atomics, reductions in a fixed order: a repeated call gives the same bits.  Refused
+ * (non-zero return, dl4ds_last_error): L >= 2^31, S >= 2^31, Q < 0 or Q > 64, a q outside [0, 1], E = 1 or E > 257, edges that
+ * are not finite or not strictly increasing.  Segments of up to 8192 contiguous elements, and of up to 512 elements when
+ * seg_stride == 1, are sorted in LDS (8 B read per element, nothing else); longer ones by a key-only radix sort in a
+ * workspace of at most 128 MiB per chunk of segments: 8 B read and 8 B written per element, then per side four passes of
+ * 8 B read (twice) and 4 B written per element. */
+int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
+                       const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
+                       long long* ks_dev, long long* hist_dev, long long* valid_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
