@@ -21,7 +21,7 @@
 //    a lane's store goes to bank (g*(P+1) + k) % 32, conflict-free), then the same network sorts the 2*G rows independently.
 //    Both are one kernel template <P, G> (P = padded length, G = 1 for the first).
 //  * global (everything else): a gather kernel writes both sides' keys into the contiguous workspace (strided input through a
-//    64 x 64 LDS transpose, so reads and writes are both coalesced), four key-only 8-bit LSD radix passes per side, a kernel
+//    64 x 64 LDS transpose, so reads and writes are both coalesced), the key-only radix sort of sort_keys.h per side, a kernel
 //    with the W1 / KS partials per tile of sorted positions and a finish kernel per segment.  Segments go through in chunks
 //    sized by a fixed workspace budget.
 #include "common.h"
@@ -39,13 +39,7 @@ constexpr int DS_ROW = 16;                             // fewest segments per st
 constexpr size_t DS_LDS_BUDGET = size_t(72) << 10;     // LDS of a workgroup, keys + reduction buffers: two workgroups per 160 KiB CU
 constexpr int DS_MAX_Q = 64, DS_MAX_E = 257;           // (the C header states both)
 constexpr uint32_t DS_INVALID = 0xFFFFFFFFu;           // key of an invalid element and of the padding
-constexpr int DS_THREADS = 256;                        // global engine: threads per workgroup (4 waves)
-constexpr int DS_TILE = 4096;                          // global engine: elements per tile
-constexpr int DS_WAVES = DS_THREADS / 64;
-constexpr int DS_WAVE_SPAN = DS_TILE / DS_WAVES;
 constexpr int DS_TR = 64;                              // gather kernel: 64 segments x 64 elements per transposed tile
-constexpr size_t DS_WS_BUDGET = size_t(128) << 20;     // workspace of the global engine (one chunk of segments)
-constexpr size_t DS_MAX_GRID = size_t(1) << 30;
 
 struct DistParams {
     double q[DS_MAX_Q];
@@ -109,20 +103,11 @@ __device__ __forceinline__ void segment_tables(const DistParams& prm, P ka, P kb
     }
 }
 
-// fixed-order tree over groups of R consecutive threads; the results land in the group's first slot
+// fixed-order tree (sum, maximum) over groups of R consecutive threads; the results land in the group's first slot
 template <int R>
 __device__ __forceinline__ void group_reduce(double* redd, uint32_t* redu, int t, double w, uint32_t ks) {
-    const int r = t % R;
     redd[t] = w; redu[t] = ks;
-    __syncthreads();
-#pragma unroll
-    for (int s = R / 2; s > 0; s >>= 1) {
-        if (r < s) {
-            redd[t] += redd[t + s];
-            redu[t] = max(redu[t], redu[t + s]);
-        }
-        __syncthreads();
-    }
+    group_tree<R>(t, [&](int i, int j) { redd[i] += redd[j]; redu[i] = max(redu[i], redu[j]); });
 }
 
 __device__ __forceinline__ void write_scalars(const DistOut& out, size_t seg, uint32_t n, double w1sum, uint32_t ks) {
@@ -146,7 +131,6 @@ __global__ void __launch_bounds__((lds_threads<P, G>())) dist_lds_kernel(const f
     constexpr int T = lds_threads<P, G>(), PITCH = lds_pitch<P, G>();
     constexpr int R = G == 1 ? T : (P < T ? P : T);    // threads that share a segment in the results phase
     constexpr int GROUPS = T / R;                      // segments worked on at a time
-    constexpr int LOGP = __builtin_ctz(P), HALF = G * P / 2;
     static_assert(G % GROUPS == 0 && (P & (P - 1)) == 0 && (G & (G - 1)) == 0, "dist_lds_kernel: shape");
     static_assert(lds_bytes<P, G>() <= DS_LDS_BUDGET, "dist_lds_kernel: LDS budget");
     extern __shared__ __attribute__((aligned(16))) unsigned char dist_lds[];
@@ -175,21 +159,7 @@ __global__ void __launch_bounds__((lds_threads<P, G>())) dist_lds_kernel(const f
         }
     }
     __syncthreads();
-    // one bitonic network over the 2*G rows: compare-exchange c works on side c / HALF, row (c % HALF) / (P/2)
-    for (int lk = 1; lk <= LOGP; ++lk) {
-        for (int lj = lk - 1; lj >= 0; --lj) {
-            for (int c = t; c < 2 * HALF; c += T) {
-                const int rem = c < HALF ? c : c - HALF;
-                const int g = rem >> (LOGP - 1), q = rem & (P / 2 - 1);
-                const int i = ((q >> lj) << (lj + 1)) | (q & ((1 << lj) - 1)), o = i + (1 << lj);
-                const bool up = ((i >> lk) & 1) == 0;
-                uint32_t* row = (c < HALF ? ka : kb) + g * PITCH;
-                const uint32_t a = row[i], b = row[o];
-                if ((a > b) == up) { row[i] = b; row[o] = a; }
-            }
-            __syncthreads();
-        }
-    }
+    bitonic_rows<P, 2 * G, PITCH, T, false>(ka, nullptr);              // ka and kb are contiguous: 2*G rows
     for (int g0 = 0; g0 < G; g0 += GROUPS) {
         const int g = g0 + t / R, r = t % R;
         const size_t seg = s0 + g;
@@ -209,16 +179,16 @@ __global__ void __launch_bounds__((lds_threads<P, G>())) dist_lds_kernel(const f
 }
 
 // ------------------------------------------------------------------------------------------------------------- global engine
-// Chunk-local layout: segment i of the chunk owns elements [i*L, (i+1)*L) of every key buffer and tiles [i*ntiles, (i+1)*ntiles)
-// of every per-tile buffer.  blockIdx.x = i*ntiles + tile.
+// Chunk-local layout and grid convention: sort_keys.h (blockIdx.x = segment of the chunk * ntiles + tile).
 
 // both sides' keys of a chunk, contiguous per segment; lanes run along the elements
-__global__ void __launch_bounds__(DS_THREADS) dist_gather_kernel(const float* __restrict__ y, const float* __restrict__ p, size_t L,
-                                                                 size_t ss, size_t es, unsigned ntiles, uint32_t* __restrict__ ka,
+__global__ void __launch_bounds__(SORT_THREADS) dist_gather_kernel(const float* __restrict__ y, const float* __restrict__ p, size_t L,
+                                                                 size_t ss, size_t es, const TileGrid grid, uint32_t* __restrict__ ka,
                                                                  uint32_t* __restrict__ kb) {
-    const size_t seg = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
-    for (int i = threadIdx.x; i < DS_TILE; i += DS_THREADS) {
-        const size_t pos = tile * DS_TILE + i;
+    size_t seg, tile;
+    grid.split(seg, tile);
+    for (int i = threadIdx.x; i < SORT_TILE; i += SORT_THREADS) {
+        const size_t pos = tile * SORT_TILE + i;
         if (pos < L) {
             const size_t o = seg * ss + pos * es;
             uint32_t a, b;
@@ -230,20 +200,20 @@ __global__ void __launch_bounds__(DS_THREADS) dist_gather_kernel(const float* __
 
 // the same for seg_stride == 1: a tile of 64 segments x 64 elements is read with lanes along the segments and written with lanes
 // along the elements, transposed through LDS.  blockIdx.x = segment block * etiles + element block.
-__global__ void __launch_bounds__(DS_THREADS) dist_gather_tr_kernel(const float* __restrict__ y, const float* __restrict__ p,
+__global__ void __launch_bounds__(SORT_THREADS) dist_gather_tr_kernel(const float* __restrict__ y, const float* __restrict__ p,
                                                                     size_t nseg, size_t L, size_t es, unsigned etiles,
                                                                     uint32_t* __restrict__ ka, uint32_t* __restrict__ kb) {
     __shared__ uint32_t ta[DS_TR][DS_TR + 1], tb[DS_TR][DS_TR + 1];
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
     const size_t sg0 = (size_t)(blockIdx.x / etiles) * DS_TR, p0 = (size_t)(blockIdx.x % etiles) * DS_TR;
-    for (int e = ty; e < DS_TR; e += DS_WAVES) {
+    for (int e = ty; e < DS_TR; e += SORT_WAVES) {
         const size_t seg = sg0 + tx, pos = p0 + e;
         uint32_t a = DS_INVALID, b = DS_INVALID;
         if (seg < nseg && pos < L) make_keys(y[seg + pos * es], p[seg + pos * es], a, b);
         ta[e][tx] = a; tb[e][tx] = b;
     }
     __syncthreads();
-    for (int g = ty; g < DS_TR; g += DS_WAVES) {
+    for (int g = ty; g < DS_TR; g += SORT_WAVES) {
         const size_t seg = sg0 + g, pos = p0 + tx;
         if (seg < nseg && pos < L) {
             ka[seg * L + pos] = ta[tx][g]; kb[seg * L + pos] = tb[tx][g];
@@ -251,80 +221,16 @@ __global__ void __launch_bounds__(DS_THREADS) dist_gather_tr_kernel(const float*
     }
 }
 
-// per-(segment, tile) digit counts -> hist[(segment*ntiles + tile)*256 + digit]
-__global__ void __launch_bounds__(DS_THREADS) dist_hist_kernel(const uint32_t* __restrict__ kin, size_t L, unsigned ntiles, int shift,
-                                                               uint32_t* __restrict__ hist) {
-    __shared__ uint32_t cnt[RK_RADIX];
-    const int t = threadIdx.x, lane = t & 63;
-    const size_t seg = blockIdx.x / ntiles, t0 = (size_t)(blockIdx.x % ntiles) * DS_TILE;
-    cnt[t] = 0u;
-    __syncthreads();
-    for (int i = t; i < DS_TILE; i += DS_THREADS) {
-        const size_t pos = t0 + i;
-        const bool valid = pos < L;
-        const uint32_t d = valid ? (kin[seg * L + pos] >> shift) & 255u : 0u;
-        const uint64_t m = match_digit(d, valid);
-        if (valid && (m & ((1ull << lane) - 1ull)) == 0ull) atomicAdd(&cnt[d], (uint32_t)__popcll(m));
-    }
-    __syncthreads();
-    hist[(size_t)blockIdx.x * RK_RADIX + t] = cnt[t];
-}
-
-// stable scatter of one pass, keys only: wave w ranks its DS_WAVE_SPAN consecutive elements per digit in order (chunks of 64, lanes in
-// order by the match mask), the waves' counts are scanned in wave order, the segment's offsets of this tile come from the scan
-__global__ void __launch_bounds__(DS_THREADS) dist_scatter_kernel(const uint32_t* __restrict__ kin, size_t L, unsigned ntiles, int shift,
-                                                                  const uint32_t* __restrict__ off, uint32_t* __restrict__ kout) {
-    constexpr int CH = DS_WAVE_SPAN / 64;
-    __shared__ uint32_t wcnt[DS_WAVES][RK_RADIX];
-    __shared__ uint32_t gofs[RK_RADIX];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const size_t seg = blockIdx.x / ntiles, tile = blockIdx.x % ntiles;
-    for (int i = t; i < DS_WAVES * RK_RADIX; i += DS_THREADS) wcnt[i / RK_RADIX][i % RK_RADIX] = 0u;
-    gofs[t] = off[(size_t)blockIdx.x * RK_RADIX + t];
-    __syncthreads();
-    const uint64_t lt = (1ull << lane) - 1ull;
-    const size_t p0 = tile * DS_TILE + (size_t)w * DS_WAVE_SPAN + lane;
-    uint32_t key[CH], r[CH];
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const size_t pos = p0 + (size_t)c * 64;
-        const bool valid = pos < L;
-        key[c] = valid ? kin[seg * L + pos] : 0u;
-        const uint32_t d = (key[c] >> shift) & 255u;
-        const uint64_t m = match_digit(d, valid);
-        const uint32_t before = valid ? wcnt[w][d] : 0u;
-        r[c] = before + (uint32_t)__popcll(m & lt);
-        if (valid && (m & lt) == 0ull) wcnt[w][d] = before + (uint32_t)__popcll(m);
-    }
-    __syncthreads();
-    {                                                  // exclusive scan of the four waves' counts, per digit
-        uint32_t run = 0;
-#pragma unroll
-        for (int v = 0; v < DS_WAVES; ++v) {
-            const uint32_t x = wcnt[v][t];
-            wcnt[v][t] = run;
-            run += x;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-        const size_t pos = p0 + (size_t)c * 64;
-        if (pos < L) {
-            const uint32_t d = (key[c] >> shift) & 255u;
-            kout[seg * L + gofs[d] + wcnt[w][d] + r[c]] = key[c];
-        }
-    }
-}
-
 // W1 sum and KS maximum of one tile of sorted positions -> pw / pk[segment*ntiles + tile]
-__global__ void __launch_bounds__(DS_THREADS) dist_terms_kernel(const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, size_t L,
-                                                                unsigned ntiles, double* __restrict__ pw, uint32_t* __restrict__ pk) {
-    __shared__ double redd[DS_THREADS];
-    __shared__ uint32_t redu[DS_THREADS];
+__global__ void __launch_bounds__(SORT_THREADS) dist_terms_kernel(const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, size_t L,
+                                                                const TileGrid grid, double* __restrict__ pw, uint32_t* __restrict__ pk) {
+    __shared__ double redd[SORT_THREADS];
+    __shared__ uint32_t redu[SORT_THREADS];
     __shared__ uint32_t n_sh;
     const int t = threadIdx.x;
-    const size_t seg = blockIdx.x / ntiles, t0 = (size_t)(blockIdx.x % ntiles) * DS_TILE;
+    size_t seg, tile;
+    grid.split(seg, tile);
+    const size_t t0 = tile * SORT_TILE;
     const uint32_t* a = ka + seg * L;
     const uint32_t* b = kb + seg * L;
     if (t == 0) n_sh = bound<true>(a, (uint32_t)L, DS_INVALID);
@@ -332,21 +238,21 @@ __global__ void __launch_bounds__(DS_THREADS) dist_terms_kernel(const uint32_t* 
     const uint32_t n = n_sh;
     double w = 0.0;
     uint32_t ks = 0;
-    for (int i = t; i < DS_TILE; i += DS_THREADS) {
+    for (int i = t; i < SORT_TILE; i += SORT_THREADS) {
         const size_t j = t0 + i;
         if (j < n) position_terms(a, b, n, (uint32_t)j, w, ks);
     }
-    group_reduce<DS_THREADS>(redd, redu, t, w, ks);
+    group_reduce<SORT_THREADS>(redd, redu, t, w, ks);
     if (t == 0) { pw[blockIdx.x] = redd[0]; pk[blockIdx.x] = redu[0]; }
 }
 
 // per segment of the chunk: the tiles' partials in a fixed order, then the quantiles and the histogram from the sorted keys
-__global__ void __launch_bounds__(DS_THREADS) dist_finish_kernel(const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, size_t L,
+__global__ void __launch_bounds__(SORT_THREADS) dist_finish_kernel(const uint32_t* __restrict__ ka, const uint32_t* __restrict__ kb, size_t L,
                                                                  unsigned ntiles, const double* __restrict__ pw,
                                                                  const uint32_t* __restrict__ pk, size_t seg0, const DistParams prm,
                                                                  const DistOut out) {
-    __shared__ double redd[DS_THREADS];
-    __shared__ uint32_t redu[DS_THREADS];
+    __shared__ double redd[SORT_THREADS];
+    __shared__ uint32_t redu[SORT_THREADS];
     __shared__ uint32_t n_sh;
     const int t = threadIdx.x;
     const size_t seg = blockIdx.x;
@@ -357,27 +263,24 @@ __global__ void __launch_bounds__(DS_THREADS) dist_finish_kernel(const uint32_t*
     const uint32_t n = n_sh;
     double w = 0.0;
     uint32_t ks = 0;
-    for (size_t i = t; i < ntiles; i += DS_THREADS) {
+    for (size_t i = t; i < ntiles; i += SORT_THREADS) {
         w += pw[seg * ntiles + i];
         ks = max(ks, pk[seg * ntiles + i]);
     }
-    group_reduce<DS_THREADS>(redd, redu, t, w, ks);
+    group_reduce<SORT_THREADS>(redd, redu, t, w, ks);
     if (t == 0) write_scalars(out, seg0 + seg, n, redd[0], redu[0]);
-    segment_tables(prm, a, b, n, seg0 + seg, t, DS_THREADS, out);
+    segment_tables(prm, a, b, n, seg0 + seg, t, SORT_THREADS, out);
 }
 
-struct Chunk {
-    size_t segs, ntiles, elems;                        // segments per chunk, tiles per segment, elements per segment
-    size_t bytes_per_seg() const {
-        return 3 * al256(elems * 4) + al256(ntiles * RK_RADIX * 4) + al256(ntiles * 8) + al256(ntiles * 4);
-    }
+// workspace of `segs` segments: both sides' keys and the sort's second buffer; per tile the digit counts and the W1 / KS partials
+struct Workspace {
+    uint32_t *ka, *kb, *tmp, *hist;
+    double* pw;
+    uint32_t* pk;
+    Workspace(Carver& w, size_t segs, size_t ntiles, size_t L)
+        : ka(w.take<uint32_t>(segs * L)), kb(w.take<uint32_t>(segs * L)), tmp(w.take<uint32_t>(segs * L)),
+          hist(w.take<uint32_t>(segs * ntiles * SORT_RADIX)), pw(w.take<double>(segs * ntiles)), pk(w.take<uint32_t>(segs * ntiles)) {}
 };
-
-Chunk plan(size_t S, size_t L) {
-    Chunk c{0, std::max<size_t>(1, cdivz(L, DS_TILE)), L};
-    c.segs = std::max<size_t>(1, std::min({S, DS_WS_BUDGET / c.bytes_per_seg(), DS_MAX_GRID / c.ntiles}));
-    return c;
-}
 
 enum Engine { ENGINE_LDS, ENGINE_STRIDED, ENGINE_GLOBAL };
 
@@ -442,8 +345,7 @@ void distribution_check_args(size_t S, size_t L, const double* q, int Q, const f
 
 size_t distribution_workspace_bytes(size_t S, size_t L, size_t seg_stride, size_t elem_stride) {
     if (S == 0 || engine_of(L, seg_stride, elem_stride) != ENGINE_GLOBAL) return 0;
-    const Chunk c = plan(S, L);
-    return c.segs * c.bytes_per_seg();
+    return plan_chunks<Workspace>(S, L).bytes();
 }
 
 void distribution(hipStream_t s, const float* y, const float* p, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
@@ -463,44 +365,27 @@ void distribution(hipStream_t s, const float* y, const float* p, size_t S, size_
     if (e == ENGINE_LDS) return launch_one(s, y, p, S, L, seg_stride, elem_stride, prm, out);
     if (e == ENGINE_STRIDED) return launch_strided(s, y, p, S, L, seg_stride, elem_stride, prm, out);
     DL4DS_REQUIRE(workspace_bytes >= distribution_workspace_bytes(S, L, seg_stride, elem_stride), "distribution workspace too small");
-    const Chunk c = plan(S, L);
-    char* ws = static_cast<char*>(workspace);
-    const size_t eb = al256(c.segs * c.elems * 4);
-    uint32_t* ka = reinterpret_cast<uint32_t*>(ws);
-    uint32_t* kb = reinterpret_cast<uint32_t*>(ws + eb);
-    uint32_t* tmp = reinterpret_cast<uint32_t*>(ws + 2 * eb);
-    char* w = ws + 3 * eb;
-    uint32_t* hbuf = reinterpret_cast<uint32_t*>(w);
-    w += al256(c.segs * c.ntiles * RK_RADIX * 4);
-    double* pw = reinterpret_cast<double*>(w);
-    w += al256(c.segs * c.ntiles * 8);
-    uint32_t* pk = reinterpret_cast<uint32_t*>(w);
+    const Chunk c = plan_chunks<Workspace>(S, L);
+    Carver carver{static_cast<char*>(workspace)};
+    const Workspace w(carver, c.segs, c.ntiles, L);
     const unsigned nt = (unsigned)c.ntiles;
     const bool transposed = seg_stride == 1 && elem_stride != 1;
     for (size_t s0 = 0; s0 < S; s0 += c.segs) {
         const size_t ns = std::min(c.segs, S - s0);
-        const dim3 grid((unsigned)(ns * nt)), block(DS_THREADS);
+        const dim3 grid((unsigned)(ns * nt)), block(SORT_THREADS);
         const float* ys = y + s0 * seg_stride;
         const float* psrc = p + s0 * seg_stride;
         if (transposed) {
             const unsigned etiles = (unsigned)cdivz(L, DS_TR);
             DL4DS_LAUNCH(dist_gather_tr_kernel, dim3((unsigned)(cdivz(ns, DS_TR) * etiles)), block, 0, s, ys, psrc, ns, L, elem_stride,
-                         etiles, ka, kb);
+                         etiles, w.ka, w.kb);
         } else {
-            DL4DS_LAUNCH(dist_gather_kernel, grid, block, 0, s, ys, psrc, L, seg_stride, elem_stride, nt, ka, kb);
+            DL4DS_LAUNCH(dist_gather_kernel, grid, block, 0, s, ys, psrc, L, seg_stride, elem_stride, tile_grid(nt), w.ka, w.kb);
         }
-        for (uint32_t* k : {ka, kb}) {                 // k -> tmp -> k -> tmp -> k
-            for (int pass = 0; pass < 4; ++pass) {
-                const uint32_t* kin = (pass & 1) ? tmp : k;
-                uint32_t* kout = (pass & 1) ? k : tmp;
-                DL4DS_LAUNCH(dist_hist_kernel, grid, block, 0, s, kin, L, nt, 8 * pass, hbuf);
-                DL4DS_LAUNCH(radix_scan_kernel, dim3((unsigned)ns), dim3(RK_RADIX), 0, s, hbuf, (int)nt);
-                DL4DS_LAUNCH(dist_scatter_kernel, grid, block, 0, s, kin, L, nt, 8 * pass, (const uint32_t*)hbuf, kout);
-            }
-        }
-        DL4DS_LAUNCH(dist_terms_kernel, grid, block, 0, s, (const uint32_t*)ka, (const uint32_t*)kb, L, nt, pw, pk);
-        DL4DS_LAUNCH(dist_finish_kernel, dim3((unsigned)ns), block, 0, s, (const uint32_t*)ka, (const uint32_t*)kb, L, nt,
-                     (const double*)pw, (const uint32_t*)pk, s0, prm, out);
+        for (uint32_t* k : {w.ka, w.kb}) segmented_sort<false>(s, KeyBuffer{k}, k, nullptr, w.tmp, nullptr, ns, L, nt, w.hist);
+        DL4DS_LAUNCH(dist_terms_kernel, grid, block, 0, s, (const uint32_t*)w.ka, (const uint32_t*)w.kb, L, tile_grid(nt), w.pw, w.pk);
+        DL4DS_LAUNCH(dist_finish_kernel, dim3((unsigned)ns), block, 0, s, (const uint32_t*)w.ka, (const uint32_t*)w.kb, L, nt,
+                     (const double*)w.pw, (const uint32_t*)w.pk, s0, prm, out);
     }
     HIP_CHECK(hipGetLastError());
 }

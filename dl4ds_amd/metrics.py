@@ -38,12 +38,11 @@ def _device_spearman(dy, dp, shape, over):
     """Spearman rho in fp64 per test pair over all H*W*C values (``over='space'``, shape (N,)) or per grid point of channel 0
     over the N pairs (``over='time'``, shape (H, W))."""
     n, h, w, c = shape
+    _check_over(over)
     if over == 'space':
         segs, length, seg_stride, elem_stride, out_shape = n, h * w * c, h * w * c, 1, (n,)
-    elif over == 'time':
-        segs, length, seg_stride, elem_stride, out_shape = h * w, n, c, h * w * c, (h, w)
     else:
-        raise ValueError(f"over must be 'time' or 'space', got {over!r}")
+        segs, length, seg_stride, elem_stride, out_shape = h * w, n, c, h * w * c, (h, w)
     out = DeviceArray(out_shape, np.float64)
     _lib.check(_lib.lib().dl4ds_spearman(dy.ptr, dp.ptr, segs, length, seg_stride, elem_stride, out.ptr))
     return out.numpy()
@@ -188,6 +187,30 @@ def _masked_observation(y, mask):
     return y
 
 
+def _prepared(y_test, y_test_hat, scaler, mask, check):
+    """Both arrays as `compute_metrics` prepares them -> (masked float32 observation, prediction, ``check(shape)``'s result)."""
+    y_test, y_test_hat = np.asarray(getattr(y_test, 'values', y_test)), np.asarray(getattr(y_test_hat, 'values', y_test_hat))
+    if y_test.ndim == 5:
+        y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
+    y_test, y_test_hat = checkarray_ndim(y_test, 4, -1), checkarray_ndim(y_test_hat, 4, -1)
+    if y_test.shape != y_test_hat.shape or y_test.ndim != 4:
+        raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y_test.shape} and {y_test_hat.shape}')
+    checked = check(y_test.shape)                  # every ValueError comes before inverse_transform and before any library call
+    if scaler is not None and hasattr(scaler, 'inverse_transform'):
+        y_test, y_test_hat = scaler.inverse_transform(y_test), scaler.inverse_transform(y_test_hat)
+    return _masked_observation(y_test, mask), y_test_hat, checked
+
+
+def _check_batch_size(batch_size):
+    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
+        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+
+
+def _upload_batch(batch_size, per, count):
+    """Units per upload out of `count`, `per` floats each: ``batch_size``, by default chunks of at most 256 MiB per array."""
+    return max(min(int(max(1, (1 << 26) // per) if batch_size is None else batch_size), count), 1)
+
+
 def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None, batch_size=None, scale=None,
                     return_fields=False):
     """Verification scores of an ensemble the caller already has on the host: ``members`` shaped (K,) + y_true.shape against the
@@ -211,9 +234,7 @@ def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None
     scale = check_score_args(fair, scale, sample_shape)
     obs = _masked_observation(y_true, mask)
     per = int(np.prod(sample_shape, dtype=np.int64))
-    if batch_size is None:
-        batch_size = max(1, (1 << 26) // max(K * per, 1))
-    bmax = max(min(int(batch_size), N), 1)
+    bmax = _upload_batch(batch_size, max(K * per, 1), N)
     stride = bmax * per
     scorer = Scorer(K, N, sample_shape, q, fair, seed, scale, return_fields, bmax)
     stack, dev_obs = DeviceArray((K, stride)), DeviceArray((stride,))
@@ -269,8 +290,7 @@ def check_neighbourhood_args(shape, thresholds, windows, batch_size=None):
         if h * w * m * m >= FSS_SUM_BOUND:
             raise ValueError(f'window {n} on a {h} x {w} field: H*W*m^2 = {h * w * m * m} with m = min(n, H)*min(n, W) = {m} '
                              'must stay below 2^62 for the exact 64-bit sums')
-    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
-        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    _check_batch_size(batch_size)
     return thr, np.asarray(wl, np.int32)
 
 
@@ -317,22 +337,12 @@ def neighbourhood_scores(y_test, y_test_hat, thresholds, windows=FSS_DEFAULT_WIN
     * ``base_rate`` = ``fss_random`` (T,): the pooled observed event frequency, ``fss_useful`` = 0.5 + base_rate / 2 and
       ``useful_window`` (T,): the smallest requested window whose pooled FSS reaches it, or -1;
     * ``thresholds`` (float32) and ``windows`` as used."""
-    y_test, y_test_hat = np.asarray(getattr(y_test, 'values', y_test)), np.asarray(getattr(y_test_hat, 'values', y_test_hat))
-    if y_test.ndim == 5:
-        y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
-    y_test, y_test_hat = checkarray_ndim(y_test, 4, -1), checkarray_ndim(y_test_hat, 4, -1)
-    if y_test.shape != y_test_hat.shape or y_test.ndim != 4:
-        raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y_test.shape} and {y_test_hat.shape}')
-    thr, win = check_neighbourhood_args(y_test.shape, thresholds, windows, batch_size)
-    if scaler is not None and hasattr(scaler, 'inverse_transform'):
-        y_test, y_test_hat = scaler.inverse_transform(y_test), scaler.inverse_transform(y_test_hat)
-    obs = _masked_observation(y_test, mask)
+    obs, y_test_hat, (thr, win) = _prepared(y_test, y_test_hat, scaler, mask,
+                                            lambda shape: check_neighbourhood_args(shape, thresholds, windows, batch_size))
     N, H, W, C = obs.shape
     T, S = len(thr), len(win)
     per = H * W * C
-    if batch_size is None:
-        batch_size = max(1, (1 << 26) // per)
-    bmax = max(min(int(batch_size), N), 1)
+    bmax = _upload_batch(batch_size, per, N)
     sums = np.empty((N, C, T, S, 3), np.int64)
     cont = np.empty((N, C, T, 4), np.int64)
     nvalid = np.empty((N, C), np.int64)
@@ -432,8 +442,7 @@ def check_distribution_args(shape, quantiles, bins=None, over='time', batch_size
             raise ValueError('`bins` must be finite (as float32)')
         if not (np.diff(edges) > 0).all():
             raise ValueError('`bins` must be strictly increasing as float32 values')
-    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
-        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    _check_batch_size(batch_size)
     return np.ascontiguousarray(q), edges
 
 
@@ -476,16 +485,8 @@ def distribution_scores(y_test, y_test_hat, quantiles=DIST_DEFAULT_QUANTILES, bi
     * with ``bins``: ``hist_obs``, ``hist_pred`` (..., B) int64, ``perkins`` = sum_b min(hist_obs, hist_pred) / n_valid, and
       pooled over all segments ``hist_obs_pooled``, ``hist_pred_pooled`` (B,), ``perkins_pooled``;
     * ``quantiles`` (float64) and ``bins`` (float32, or None) as used.  Every ratio is NaN where ``n_valid == 0``."""
-    y_test, y_test_hat = np.asarray(getattr(y_test, 'values', y_test)), np.asarray(getattr(y_test_hat, 'values', y_test_hat))
-    if y_test.ndim == 5:
-        y_test, y_test_hat = np.squeeze(y_test, -1), np.squeeze(y_test_hat, -1)
-    y_test, y_test_hat = checkarray_ndim(y_test, 4, -1), checkarray_ndim(y_test_hat, 4, -1)
-    if y_test.shape != y_test_hat.shape or y_test.ndim != 4:
-        raise ValueError(f'expected two (N, H, W, C) arrays of one shape, got {y_test.shape} and {y_test_hat.shape}')
-    q, edges = check_distribution_args(y_test.shape, quantiles, bins, over, batch_size)
-    if scaler is not None and hasattr(scaler, 'inverse_transform'):
-        y_test, y_test_hat = scaler.inverse_transform(y_test), scaler.inverse_transform(y_test_hat)
-    obs = _masked_observation(y_test, mask)
+    obs, y_test_hat, (q, edges) = _prepared(y_test, y_test_hat, scaler, mask,
+                                            lambda shape: check_distribution_args(shape, quantiles, bins, over, batch_size))
     N, H, W, C = obs.shape
     Q, E = len(q), 0 if edges is None else len(edges)
     if over == 'time':
@@ -494,9 +495,7 @@ def distribution_scores(y_test, y_test_hat, quantiles=DIST_DEFAULT_QUANTILES, bi
     else:
         lead, units, unit = (N,), N, 1                                     # uploaded in blocks of samples: one segment each
         per_unit = H * W * C
-    if batch_size is None:
-        batch_size = max(1, (1 << 26) // per_unit)
-    bmax = max(min(int(batch_size), units), 1)
+    bmax = _upload_batch(batch_size, per_unit, units)
     segs = units * unit
     quant = np.empty((segs, 2, Q), np.float64)
     w1 = np.empty((segs,), np.float64)

@@ -6,11 +6,11 @@ Every case is ``dict(y, p, quantiles, bins, over, mask, empty)``: ``empty`` is t
 construction (their quantiles, W1, KS and Perkins score are NaN); everywhere else the expected arrays are finite."""
 import numpy as np
 
-# constants of csrc/distribution.hip the shapes below are built around
+# constants of csrc/distribution.hip and csrc/sort_keys.h the shapes below are built around
 LDS_MAX = 8192                # DS_LDS_MAX: longest contiguous segment sorted in LDS
 STRIDED_MAX = 512             # DS_STRIDED_MAX: longest segment of the strided LDS engine
-TILE = 4096                   # DS_TILE: elements per tile of the global engine
-WS_BUDGET = 128 << 20         # DS_WS_BUDGET: workspace of one chunk of segments of the global engine
+TILE = 4096                   # SORT_TILE: elements per tile of the global engine
+WS_BUDGET = 128 << 20         # SORT_WS_BUDGET: workspace of one chunk of segments of the global engine
 MAX_Q, MAX_E = 64, 257        # caps of the C entry
 
 
@@ -21,7 +21,7 @@ def strided_group(n):
 
 
 def global_bytes_per_segment(n):
-    """workspace of one segment of the global engine (Chunk::bytes_per_seg): three key buffers, digit counts, two partials per tile"""
+    """workspace of one segment of the global engine (Workspace, for one segment): three key buffers, digit counts, two partials per tile"""
     al = lambda b: (b + 255) & ~255
     tiles = max(1, -(-n // TILE))
     return 3 * al(n * 4) + al(tiles * 1024) + al(tiles * 8) + al(tiles * 4)

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 ATOL = 1e-9
 LDS_MAX = 4096            # rank.hip RK_LDS_MAX: longest sequence the one-workgroup LDS engine sorts
+TILE = 4096               # sort_keys.h SORT_TILE: elements per tile of the global radix engine
 
 
 def precip(rng, shape):
@@ -46,8 +47,11 @@ def check(got, want):
 
 
 @pytest.mark.parametrize('shape,kind', [((3, 512, 512, 1), 'ties'), ((3, 512, 512, 1), 'signed_zero'), ((4, 96, 104, 2), 'normal'),
-                                        ((4, 96, 104, 2), 'ties'), ((5, 9, 8, 1), 'normal'), ((5, 9, 8, 1), 'signed_zero')])
+                                        ((4, 96, 104, 2), 'ties'), ((5, 9, 8, 1), 'normal'), ((5, 9, 8, 1), 'signed_zero'),
+                                        ((2, 1, 2 * TILE + 64, 1), 'ties')])
 def test_per_pair(shape, kind):
+    """the last shape: two full tiles of the radix sort with the index payload and a third of 64 elements, one chunk of one wave
+    (the tile's three other waves hold no valid lane)"""
     from dl4ds_amd.metrics import spearman
     y, p = pair(np.random.default_rng(sum(shape)), shape, kind)
     got = spearman(y, p, over='space')
