@@ -39,6 +39,7 @@ def __getattr__(name):
             'verify_ensemble': '.inference', 'EnsembleVerifier': '.inference', 'ensemble_scores': '.metrics',
             'neighbourhood_scores': '.metrics', 'fss': '.metrics',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
+            'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',

@@ -600,6 +600,15 @@ int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, siz
                  valid_dev, ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_spectrum(const float* y_dev, const float* p_dev, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
+                   int B, double* power_dev, long long* valid_dev, double* mean_dev) {
+    API_BEGIN
+    spectrum_check_args(N, H, W, C, bin_host, B);                                    // before the workspace is sized
+    const size_t ws = spectrum_workspace_bytes(N, H, W, C, p_dev ? 2 : 1, B);
+    spectrum(S(), y_dev, p_dev, N, H, W, C, detrend, window, bin_host, B, power_dev, valid_dev, mean_dev, ws ? scratch(ws) : nullptr,
+             ws);
+    API_END
+}
 int dl4ds_op_bce(const float* p, float label, int n, float* loss_dev, float* dp) {
     API_BEGIN
     bce_forward_backward(S(), p, label, n, 1.f, loss_dev, dp, 0);

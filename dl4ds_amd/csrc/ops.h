@@ -175,6 +175,15 @@ void distribution_check_args(size_t S, size_t L, const double* q, int Q, const f
 void distribution(hipStream_t s, const float* y, const float* p, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
                   const double* q, int Q, const float* edges, int E, double* quant, double* w1, long long* ks, long long* hist,
                   long long* valid, void* workspace, size_t workspace_bytes);
+// Spectral verification (spectrum.hip) of the N*C fields of y, p (N, H, W, C; p may be null): the unnormalised 2-D DFT of either
+// side in fp64 (kept cells, optional detrending and periodic Hann window), folded over the bins of the HOST map bin [H][W/2 + 1]
+// (values in [-1, B)) into power [N][C][4][B]; valid [N][C] kept cells, mean [N][C][2] the subtracted means.  Outputs are
+// overwritten.  Fixed-order reductions: bitwise reproducible.  `sides`: 2 with a prediction, 1 without.  Synchronises the stream
+// once, after the upload of the call's tables.  spectrum_check_args throws on a request the entry refuses.
+size_t spectrum_workspace_bytes(int N, int H, int W, int C, int sides, int B);
+void spectrum_check_args(int N, int H, int W, int C, const int* bin_host, int B);
+void spectrum(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
+              int B, double* power, long long* valid, double* mean, void* workspace, size_t workspace_bytes);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,

@@ -4,7 +4,12 @@ segmented rank engine (`dl4ds_spearman`, csrc/rank.hip), the summary statistics 
 `neighbourhood_scores` / `fss` (no counterpart in the reference): Fractions Skill Score and contingency scores per threshold and
 neighbourhood size from the exact integer sums of `dl4ds_fss` (csrc/fss.hip).
 `distribution_scores` / `quantile_maps` (no counterpart either): sample quantiles, 1-Wasserstein distance, Kolmogorov-Smirnov
-statistic, histograms and Perkins skill score per grid cell or per sample from `dl4ds_distribution` (csrc/distribution.hip)."""
+statistic, histograms and Perkins skill score per grid cell or per sample from `dl4ds_distribution` (csrc/distribution.hip).
+`spectral_scores` / `power_spectrum` (no counterpart either): radially averaged power spectral density, spectral ratio, coherence,
+log-spectral distance and effective resolution per field from the binned power and cross spectra of `dl4ds_spectrum`
+(csrc/spectrum.hip)."""
+import math
+
 import numpy as np
 
 from . import _lib
@@ -539,3 +544,212 @@ def quantile_maps(y, y_hat, quantiles, over='time', scaler=None, mask=None):
     """``(q_obs, q_pred)`` of `distribution_scores`: the sample quantiles of observation and prediction per segment, (..., Q)."""
     r = distribution_scores(y, y_hat, quantiles, over=over, scaler=scaler, mask=mask)
     return r['q_obs'], r['q_pred']
+
+
+SPECTRUM_MAX_DIM = 16384                           # caps of dl4ds_spectrum
+SPECTRUM_MAX_BINS = 16384
+SPECTRUM_FIELD_BOUND = 1 << 31
+
+
+def _folded(n):
+    """|signed wavenumber| of every DFT index of an axis of n points, as Python integers."""
+    return [min(k, n - k) for k in range(n)]
+
+
+def radial_bin_map(H, W):
+    """-> (int32 (H, W) full-plane bin map, B): bin b = round(L * sqrt((ky/H)^2 + (kx/W)^2)) with L = max(H, W), halves rounded up,
+    evaluated in Python integers as (isqrt(4 L^2 (ky^2 W^2 + kx^2 H^2) // (H W)^2) + 1) // 2; -1 where b >= B = L // 2 + 1."""
+    L = max(H, W)
+    B = L // 2 + 1
+    hw2 = (H * W) ** 2
+    quad = np.empty((H // 2 + 1, W // 2 + 1), np.int32)           # the map depends on (|ky|, |kx|) alone
+    for ky in range(H // 2 + 1):
+        for kx in range(W // 2 + 1):
+            b = (math.isqrt(4 * L * L * (ky * ky * W * W + kx * kx * H * H) // hw2) + 1) // 2
+            quad[ky, kx] = b if b < B else -1
+    return np.ascontiguousarray(quad[np.ix_(_folded(H), _folded(W))]), B
+
+
+def check_spectral_args(shape, bins='radial', detrend='mean', window=None, spacing=1.0, ratio_floor=0.5, batch_size=None):
+    """Validation of `spectral_scores` (no library call) -> (int32 (H, W) full-plane bin map, B, detrend flag, window flag)."""
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f'expected non-empty (N, H, W, C) arrays, got shape {tuple(shape)}')
+    n, h, w, c = (int(v) for v in shape)
+    if max(h, w) > SPECTRUM_MAX_DIM:
+        raise ValueError(f'fields of {h} x {w} cells are not supported: H and W must not exceed {SPECTRUM_MAX_DIM}')
+    if n * c >= SPECTRUM_FIELD_BOUND:
+        raise ValueError(f'{n * c} fields are not supported: N*C must stay below 2^31')
+    if detrend not in ('mean', None):
+        raise ValueError(f"`detrend` must be 'mean' or None, got {detrend!r}")
+    if window not in ('hann', None):
+        raise ValueError(f"`window` must be 'hann' or None, got {window!r}")
+    for name, v in (('spacing', spacing), ('ratio_floor', ratio_floor)):
+        if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v) or not v > 0:
+            raise ValueError(f'`{name}` must be a positive finite number, got {v!r}')
+    _check_batch_size(batch_size)
+    if isinstance(bins, str):
+        if bins != 'radial':
+            raise ValueError(f"`bins` must be 'radial' or an integer (H, W) map, got {bins!r}")
+        full, B = radial_bin_map(h, w)
+        return full, B, int(detrend == 'mean'), int(window == 'hann')
+    m = np.asarray(bins)
+    if m.dtype == bool or not np.issubdtype(m.dtype, np.integer) or m.shape != (h, w):
+        raise ValueError(f"`bins` must be 'radial' or an integer map shaped (H, W) = ({h}, {w})")
+    lo, hi = int(m.min()), int(m.max())
+    if lo < -1 or hi < 0 or hi >= SPECTRUM_MAX_BINS:
+        raise ValueError(f'the entries of `bins` must lie in [-1, {SPECTRUM_MAX_BINS}) and name at least one bin')
+    mirror = m[np.ix_([(-k) % h for k in range(h)], [(-k) % w for k in range(w)])]
+    if not np.array_equal(m, mirror):
+        raise ValueError('`bins` must be symmetric under (ky, kx) -> (-ky, -kx): a real field has a Hermitian transform')
+    return np.ascontiguousarray(m, np.int32), hi + 1, int(detrend == 'mean'), int(window == 'hann')
+
+
+def _fsum_axis0(a, keep):
+    """math.fsum over the kept entries of axis 0 of a float64 array: the correctly rounded sum, whatever the order."""
+    a = np.asarray(a, np.float64)
+    out = np.zeros(a.shape[1:])
+    for idx in np.ndindex(out.shape):
+        out[idx] = math.fsum(float(a[(n,) + idx]) for n in range(a.shape[0]) if keep[(n,) + idx[:keep.ndim - 1]])
+    return out
+
+
+def _lsd(ratio, usable):
+    """sqrt(mean((10 log10 ratio)^2)) over the usable bins of the last axis (math.fsum of the squares); NaN without one."""
+    ratio, usable = np.asarray(ratio, np.float64), np.asarray(usable, bool)
+    out = np.full(ratio.shape[:-1], np.nan)
+    for idx in np.ndindex(out.shape):
+        sel = usable[idx]
+        if sel.any():
+            d = 10.0 * np.log10(np.ascontiguousarray(ratio[idx][sel]))
+            out[idx] = math.sqrt(math.fsum(float(v) * float(v) for v in d) / int(sel.sum()))
+    return out
+
+
+def _spectral_ratios(po, pp, cr, ci, count):
+    """(psd_ratio, coherence, bins usable for the log-spectral distance) of power and cross spectra over the last axis."""
+    ratio, coh = _ratio(pp, po), _ratio(cr * cr + ci * ci, po * pp)
+    usable = (np.arange(po.shape[-1]) >= 1) & (count > 0) & (po > 0) & (pp > 0)
+    return ratio, coh, usable
+
+
+def spectra_from_sums(power, nvalid, mean, count, hw, spacing=1.0, ratio_floor=0.5):
+    """The result dict of `spectral_scores` from the outputs of `dl4ds_spectrum` (host arithmetic only): ``power`` (N, C, 4, B),
+    ``nvalid`` (N, C), ``mean`` (N, C, 2), ``count`` (B,) full-plane coefficients per bin, ``hw`` = (H, W)."""
+    power, nvalid = np.asarray(power, np.float64), np.asarray(nvalid, np.int64)
+    mean, count = np.asarray(mean, np.float64), np.asarray(count, np.int64)
+    H, W = (int(v) for v in hw)
+    B = power.shape[-1]
+    norm = float((H * W) ** 2)
+    empty = nvalid == 0
+    with np.errstate(divide='ignore'):
+        wavenumber = np.arange(B, dtype=np.float64) / (float(max(H, W)) * float(spacing))
+        wavelength = 1.0 / wavenumber
+    po, pp, cr, ci = (np.ascontiguousarray(power[:, :, k]) / norm for k in range(4))
+    cross = np.empty(po.shape, np.complex128)
+    cross.real, cross.imag = cr, ci
+    ratio, coh, usable = _spectral_ratios(po, pp, cr, ci, count)
+    blank = lambda a: np.where(empty[(...,) + (None,) * (a.ndim - 2)], np.nan, a)     # every score of an empty field is NaN
+    res = dict(wavenumber=wavenumber, wavelength=wavelength, count=count, n_valid=nvalid, mean_obs=mean[..., 0],
+               mean_pred=mean[..., 1], power_obs=po, power_pred=pp, psd_obs=blank(_ratio(po, count)),
+               psd_pred=blank(_ratio(pp, count)), cross=cross, coherence=blank(coh), psd_ratio=blank(ratio),
+               lsd=blank(_lsd(ratio, usable)))
+    keep = ~empty
+    pool = [_fsum_axis0(a, keep) for a in (po, pp, cr, ci)]
+    cpool = np.empty(pool[0].shape, np.complex128)
+    cpool.real, cpool.imag = pool[2], pool[3]
+    pratio, pcoh, pusable = _spectral_ratios(*pool, count)
+    eff = np.full(pratio.shape[0], np.nan)
+    for c in range(pratio.shape[0]):
+        best = 0
+        for b in range(1, B):
+            if count[b] > 0 and not pratio[c, b] >= ratio_floor:          # (NaN fails)
+                break
+            best = b
+        if best:
+            eff[c] = wavelength[best]
+    res.update(power_obs_pooled=pool[0], power_pred_pooled=pool[1], cross_pooled=cpool, psd_ratio_pooled=pratio,
+               coherence_pooled=pcoh, lsd_pooled=_lsd(pratio, pusable), effective_wavelength=eff)
+    return res
+
+
+def _device_spectra(obs, pred, full, B, detrend, window, batch_size):
+    """`dl4ds_spectrum` over sample blocks of the float32 observation (and prediction, or None) -> (power (N, C, 4, B), n_valid
+    (N, C), mean (N, C, 2))."""
+    N, H, W, C = obs.shape
+    half = np.ascontiguousarray(full[:, :W // 2 + 1], np.int32)
+    per = H * W * C
+    bmax = _upload_batch(batch_size, per, N)
+    power, nvalid, mean = np.empty((N, C, 4, B), np.float64), np.empty((N, C), np.int64), np.empty((N, C, 2), np.float64)
+    lib = _lib.lib()
+    dy = DeviceArray((bmax * per,))
+    dp = DeviceArray((bmax * per,)) if pred is not None else None
+    dpower, dvalid, dmean = (DeviceArray((bmax,) + a.shape[1:], a.dtype) for a in (power, nvalid, mean))
+    try:
+        for i in range(0, N, bmax):
+            b = min(bmax, N - i)
+            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, obs[i:i + b].ctypes.data, b * per * 4))
+            if dp is not None:
+                part = np.ascontiguousarray(pred[i:i + b], np.float32)
+                _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part.ctypes.data, b * per * 4))
+            _lib.check(lib.dl4ds_spectrum(dy.ptr, dp.ptr if dp is not None else None, b, H, W, C, detrend, window, half.ctypes.data,
+                                          B, dpower.ptr, dvalid.ptr, dmean.ptr))
+            for host, dev in ((power, dpower), (nvalid, dvalid), (mean, dmean)):
+                _lib.check(lib.dl4ds_memcpy_d2h(host[i:i + b].ctypes.data, dev.ptr, host[i:i + b].nbytes))
+    finally:
+        for d in (dy, dp, dpower, dvalid, dmean):
+            if d is not None:
+                d.free()
+    return power, nvalid, mean
+
+
+def _bin_counts(full, B):
+    return np.bincount(full[full >= 0].ravel(), minlength=B).astype(np.int64)
+
+
+def spectral_scores(y_test, y_test_hat, bins='radial', detrend='mean', window=None, spacing=1.0, ratio_floor=0.5, scaler=None,
+                    mask=None, batch_size=None):
+    """Does the prediction have the observation's variance at every spatial scale, and below which wavelength is it merely smooth?
+    Per field (each of the N*C planes of the (N, H, W, C) arrays), on the device (csrc/spectrum.hip): the two-dimensional DFT of
+    both sides in fp64, folded over wavenumber bins into power and cross spectra.  Inputs are prepared as in `neighbourhood_scores`
+    (5-D squeezed, optional ``scaler.inverse_transform``) and read as float32.  A cell is kept when both arrays are finite there
+    and ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it; ``detrend='mean'`` subtracts each side's own mean over the
+    kept cells (``None``: nothing); excluded cells are then 0; ``window='hann'`` multiplies by the periodic Hann window of either
+    axis.  ``bins='radial'``: bin b = round(L sqrt((ky/H)^2 + (kx/W)^2)) with L = max(H, W), halves up, in exact integers,
+    B = L // 2 + 1 bins, coefficients beyond dropped; or an integer (H, W) map of the full plane with values in [0, B) or -1
+    (dropped), symmetric under (ky, kx) -> (-ky, -kx) (directional spectra).  ``spacing``: the grid spacing, the unit of the
+    wavelengths.  The arrays are uploaded in chunks of ``batch_size`` samples (default: at most 256 MiB per array); the result is
+    bitwise independent of it.  Returns a dict (float64 unless said otherwise):
+
+    * ``wavenumber`` (B,) = b / (L spacing), ``wavelength`` its inverse (inf at b = 0), ``count`` (B,) int64 coefficients per bin;
+    * ``n_valid`` (N, C) int64, ``mean_obs``, ``mean_pred`` (N, C): the subtracted means (0 without detrending);
+    * ``power_obs``, ``power_pred`` (N, C, B): sum of |X|^2 over the bin / (H W)^2 -- with detrending and no window they add up to
+      the variance over the kept cells times n_valid / (H W), less the dropped coefficients; ``psd_obs``, ``psd_pred`` = power /
+      count; ``cross`` (N, C, B) complex128 = sum of Y conj(P) / (H W)^2;
+    * ``coherence`` = |cross|^2 / (power_obs power_pred), ``psd_ratio`` = power_pred / power_obs (N, C, B);
+    * ``lsd`` (N, C) = sqrt(mean((10 log10 psd_ratio)^2)) over the bins b >= 1 with count > 0 and both powers > 0;
+    * pooled over the samples with n_valid > 0, per channel: ``power_obs_pooled``, ``power_pred_pooled``, ``cross_pooled`` (C, B)
+      (math.fsum), ``psd_ratio_pooled``, ``coherence_pooled`` (C, B), ``lsd_pooled`` (C,) and ``effective_wavelength`` (C,): the
+      wavelength of the largest b* with psd_ratio_pooled >= ``ratio_floor`` on every bin 1 .. b* with count > 0, NaN when bin 1 fails.
+
+    Every ratio is NaN on a zero denominator; psd, coherence, psd_ratio and lsd of a field with n_valid = 0 are NaN (its power is 0)."""
+    obs, y_test_hat, (full, B, dt, win) = _prepared(
+        y_test, y_test_hat, scaler, mask, lambda shape: check_spectral_args(shape, bins, detrend, window, spacing, ratio_floor, batch_size))
+    power, nvalid, mean = _device_spectra(obs, y_test_hat, full, B, dt, win, batch_size)
+    return spectra_from_sums(power, nvalid, mean, _bin_counts(full, B), obs.shape[1:3], spacing, ratio_floor)
+
+
+def power_spectrum(y, bins='radial', detrend='mean', window=None, spacing=1.0, scaler=None, mask=None):
+    """``(wavenumber, psd)`` of one (N, H, W, C) array: (B,) and (N, C, B) as ``psd_obs`` of `spectral_scores`, without a prediction."""
+    y = np.asarray(getattr(y, 'values', y))
+    if y.ndim == 5:
+        y = np.squeeze(y, -1)
+    y = checkarray_ndim(y, 4, -1)
+    if y.ndim != 4:
+        raise ValueError(f'expected an (N, H, W, C) array, got {y.shape}')
+    full, B, dt, win = check_spectral_args(y.shape, bins, detrend, window, spacing)
+    if scaler is not None and hasattr(scaler, 'inverse_transform'):
+        y = scaler.inverse_transform(y)
+    obs = _masked_observation(y, mask)
+    power, nvalid, mean = _device_spectra(obs, None, full, B, dt, win, None)
+    r = spectra_from_sums(power, nvalid, mean, _bin_counts(full, B), obs.shape[1:3], spacing)
+    return r['wavenumber'], r['psd_obs']

@@ -260,6 +260,37 @@ int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C
 int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
                        const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
                        long long* ks_dev, long long* hist_dev, long long* valid_dev);
+/* Spectral verification of a prediction against an observation: binned power and cross spectra per field.  The reference has no
+ * such metric; DESIGN.md section 16 carries the same definitions.  y, p are observation and prediction, fp32, shaped (N, H, W, C).
+ * Each of the F = N*C planes is one field.  Fields are ordered [n][c].
+ * 1. Kept cells and detrending.  A cell is kept iff y and p are both finite there.  NaN in y is the masking mechanism.
+ *    n_valid[f] is the number of kept cells.  detrend = 1: each side has its own mean over its kept cells subtracted.  The mean is
+ *    an fp64 sum in a fixed order, and is returned in mean_dev[f][2].  detrend = 0: nothing is subtracted.  The means are written
+ *    as 0.  Excluded cells become 0 after that step.
+ * 2. Window.  window = 1 multiplies cell (i, j) by wy[i]*wx[j].  w[i] = 0.5 - 0.5*cos(2 pi i / n) is the periodic Hann window.  It
+ *    is computed on the host in fp64.  window = 0: no window.
+ * 3. Transform.  X(ky, kx) = sum_i sum_j v[i][j] * exp(-2 pi i (ky*i/H + kx*j/W)).  This is numpy's unnormalised fft2, evaluated in
+ *    fp64.  Twiddle factors come from host-made fp64 tables of H and W entries.  They are indexed by (k*i) mod n, an exact
+ *    integer, so no angle is ever reduced in floating point.
+ * 4. Bins.  The caller passes a HOST map bin_host[H][W/2+1] of int32 for the half plane kx = 0 .. floor(W/2).  Values lie in
+ *    [0, B), or -1 for a coefficient counted nowhere.  The library never computes a radius.  A half-plane coefficient counts
+ *    mult(kx) times.  mult is 1 for kx = 0 and for kx = W/2 when W is even, else 2.  The caller's map is symmetric under
+ *    (ky, kx) -> (-ky, -kx), so this equals the full-plane sum.
+ * 5. Outputs.  All are overwritten.
+ *      power_dev [F][4][B]  fp64: sum mult*|Y|^2, sum mult*|P|^2, Re sum mult*Y*conj(P), Im sum mult*Y*conj(P) over the half-plane
+ *                           coefficients of the bin
+ *      valid_dev [F]        int64
+ *      mean_dev  [F][2]     fp64
+ *    p_dev may be null.  Then only component 0 and column 0 of mean_dev carry values and the rest is written as 0.  A field with
+ *    n_valid = 0 gives zeros.  There are no floating-point atomics and every reduction has a fixed order.  A repeated call gives
+ *    the same bits, and the result does not depend on how fields are grouped into calls.
+ * 6. Refusals.  A non-zero return with dl4ds_last_error, for any of: H or W < 1 or > 16384; B < 1 or B > 16384; a map entry
+ *    outside [-1, B); N*C >= 2^31.
+ * The transform is a direct DFT as two fp64 matrix products (about 2 H W^2 + 4 H^2 W flops per field and side), tiled through LDS;
+ * the row transform's complex output and the four products per coefficient live in a workspace of at most 128 MiB per chunk of
+ * fields (64 bytes per half-plane coefficient and field), a field larger than that runs alone. */
+int dl4ds_spectrum(const float* y_dev, const float* p_dev, int N, int H, int W, int C, int detrend, int window,
+                   const int* bin_host, int B, double* power_dev, long long* valid_dev, double* mean_dev);
 /* Keras BinaryCrossentropy(from_logits=False) vs a constant label -- cgan.py:546-549,567-571 */
 int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float* dp_dev);
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
