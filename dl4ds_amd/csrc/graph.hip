@@ -737,6 +737,10 @@ struct ConcatOp : GOp {
             ConcatSlice sl[4];
             int n = 0, off = 0;
             bool ok = wide_plain && !exp_env("DL4DS_NO_CONCAT_SPLIT");
+            // the same tensor concatenated twice: its gradient is the SUM of its slices, and two slices of one launch storing
+            // into the same dense buffer would race -- the per-slice copies below accumulate in order
+            for (size_t k = 0; k < ins.size() && ok; ++k)
+                for (size_t j = 0; j < k; ++j) ok = ok && ins[j] != ins[k];
             for (size_t k = 0; k < ins.size() && ok; ++k) {
                 const GTensor& ti = g.tensors[ins[k]];
                 if (wants_grad(g, ins[k], c) && !ti.galias) {
