@@ -37,6 +37,7 @@ def __getattr__(name):
             'StandardScaler': '.preprocessing', 'MinMaxScaler': '.preprocessing',
             'predict': '.inference', 'predict_ensemble': '.inference', 'EnsemblePredictor': '.inference',
             'verify_ensemble': '.inference', 'EnsembleVerifier': '.inference', 'ensemble_scores': '.metrics',
+            'exceedance_scores': '.metrics', 'verify_exceedance': '.inference', 'ExceedanceVerifier': '.inference',
             'neighbourhood_scores': '.metrics', 'fss': '.metrics',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',

@@ -581,6 +581,20 @@ int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t me
                    ws);
     API_END
 }
+int dl4ds_ensemble_exceedance(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                              const float* thr_dev, int T, int thr_per_cell, short* count_dev, long long* sample_out_dev,
+                              long long* cell_acc_dev, unsigned long long* table_dev) {
+    API_BEGIN
+    ensemble_exceedance(S(), members_dev, K, n, member_stride, obs_dev, B, thr_dev, T, thr_per_cell, count_dev, sample_out_dev,
+                        cell_acc_dev, table_dev);
+    API_END
+}
+int dl4ds_ensemble_exceedance_walk_limit(size_t K, size_t* samples_out) {
+    API_BEGIN
+    DL4DS_REQUIRE(K >= 1 && K <= ENS_MAX_MEMBERS, "ensemble_exceedance: 1 <= K <= 256 members");
+    *samples_out = exc_walk_limit(K);
+    API_END
+}
 int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
               const int* windows_host, int n_windows, long long* sums_dev, long long* cont_dev, long long* valid_dev) {
     API_BEGIN

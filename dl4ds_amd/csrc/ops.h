@@ -158,6 +158,16 @@ void ensemble_score(hipStream_t s, const float* members, size_t K, size_t n, siz
                     unsigned long long elem_offset, const float* scale, int fair, unsigned long long seed, const float* q_host, int nq,
                     float* crps, float* sqerr, float* var, int* rank, double* sample_out, double* cell_acc,
                     unsigned long long* rank_hist, unsigned long long* covered, void* workspace, size_t workspace_bytes);
+// Exceedance verification of the ensemble members[K][n] against obs[n] at T thresholds (exceedance.hip): thr [T], or
+// [T][n / B] with thr_per_cell; per valid (t, e): o = [obs >= thr], c = #{k : x_k >= thr}.  count [T][n] = c or -1 (overwritten),
+// sample_out [B][T][4] = n_valid, sum o, sum c, sum (c - K o)^2 per sample (overwritten), cell_acc [T][4][n / B] the same per cell
+// (+=), table [T][K + 1][2] the number of valid elements with (c, o) (+=).  Outputs may be null.  Integer arithmetic only.
+// exc_walk_limit: the samples one lane may walk before its 32-bit partial sums could overflow (the launch splits a call by it).
+constexpr int EXC_MAX_THRESHOLDS = 16;
+size_t exc_walk_limit(size_t K);
+void ensemble_exceedance(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                         const float* thr, int T, int thr_per_cell, short* count, long long* sample_out, long long* cell_acc,
+                         unsigned long long* table);
 // Neighbourhood verification (fss.hip) of the N*C fields of y, p (N, H, W, C) at T thresholds and S window sizes (host arrays):
 // sums [N][C][T][S][3] = the exact integer sums D, F, O of the Fractions Skill Score, cont [N][C][T][4] = hits, misses, false
 // alarms, correct negatives over the valid (both finite) cells, valid [N][C] their count.  Outputs are overwritten.  Integer

@@ -102,3 +102,179 @@ class Scorer:
                        n_cells_excluded=self.n_cells_excluded)
         res.update(self.fields)
         return res
+
+
+# ------------------------------------------------------------------------------------------------ exceedance probabilities
+EXCEEDANCE_MAX_THRESHOLDS = 16                     # cap of dl4ds_ensemble_exceedance: thresholds and counters live in registers
+
+
+def check_exceedance_args(thresholds, sample_shape):
+    """Thresholds of the exceedance verification -> float32 array shaped (T,) (one value per threshold) or (T,) + sample_shape (a
+    threshold field per cell; NaN inside a field is legal and excludes that cell for that threshold).  Refuses an empty sequence,
+    more than 16 thresholds, anything that is not numeric, a scalar threshold that is not finite (as float32), and fields that do
+    not have one sample's shape (``sample_shape=None``: the shape of fields is not looked at; for a caller that does not know the
+    sample's shape yet).  Looks at its arguments only (no library, no device)."""
+    sample_shape = None if sample_shape is None else tuple(int(v) for v in sample_shape)
+    try:
+        t64 = np.asarray(getattr(thresholds, 'values', thresholds))
+        if t64.dtype == bool or t64.dtype == object or not np.issubdtype(t64.dtype, np.number) or np.iscomplexobj(t64):
+            raise TypeError
+        t64 = t64.astype(np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f'`thresholds` must be numbers, or one field of numbers per threshold, got {thresholds!r}') from None
+    if t64.ndim == 0:
+        t64 = t64.reshape(1)
+    if t64.shape[0] == 0:
+        raise ValueError('`thresholds` must not be empty')
+    if t64.shape[0] > EXCEEDANCE_MAX_THRESHOLDS:
+        raise ValueError(f'at most {EXCEEDANCE_MAX_THRESHOLDS} thresholds per call, got {t64.shape[0]}')
+    with np.errstate(over='ignore'):
+        thr = t64.astype(np.float32)
+    if t64.ndim == 1:
+        if not np.isfinite(t64).all() or not np.isfinite(thr).all():
+            raise ValueError('scalar `thresholds` must be finite (as float32)')
+    elif sample_shape is not None and tuple(t64.shape[1:]) != sample_shape:
+        raise ValueError(f'per-cell `thresholds` must be shaped (T,) + {sample_shape}, one field per threshold, got {t64.shape}')
+    return np.ascontiguousarray(thr)
+
+
+def _quotient(num, den):
+    """num / den element-wise for integer arrays (int64, or object arrays of Python integers), each quotient correctly rounded to
+    fp64, NaN where den == 0.  Operands below 2^53 are exact in fp64, where one IEEE division is the correctly rounded quotient;
+    anything larger goes through Python integers (``metrics._ratio_exact``)."""
+    from .metrics import _ratio_exact
+    num, den = np.asarray(num), np.asarray(den)
+    num, den = np.broadcast_arrays(num, den)
+    if num.dtype != object and den.dtype != object and (num.size == 0 or (max(int(np.abs(num).max()), int(np.abs(den).max())) < 1 << 53)):
+        n, d = num.astype(np.float64), den.astype(np.float64)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return np.where(d == 0, np.nan, n / np.where(d == 0, 1.0, d))
+    return _ratio_exact(num.astype(object), den.astype(object))
+
+
+def _wide(a, bound):
+    """int64 array ``a`` as it is when products up to ``bound`` fit into int64, else as Python integers"""
+    return a if bound < 1 << 62 else a.astype(object)
+
+
+def exceedance_from_counts(table, cell_sums, sample_sums, n_members, thresholds):
+    """The result dict of the exceedance verification from the integer outputs of ``dl4ds_ensemble_exceedance`` (host arithmetic
+    only, no library): ``table`` (T, K + 1, 2), ``cell_sums`` (T, 4) + sample_shape, ``sample_sums`` (N, T, 4).  Every quotient of
+    integers is evaluated on Python integers (or on fp64 operands that hold them exactly) and rounded once; a quotient with a zero
+    denominator is NaN."""
+    from fractions import Fraction
+    from .metrics import _ratio_exact
+    K = int(n_members)
+    table = np.asarray(table).astype(np.int64)
+    cell = np.asarray(cell_sums).astype(np.int64)
+    samp = np.asarray(sample_sums).astype(np.int64)
+    T = table.shape[0]
+    if table.shape != (T, K + 1, 2) or cell.shape[:2] != (T, 4) or samp.ndim != 3 or samp.shape[1:] != (T, 4):
+        raise ValueError(f'expected table (T, {K + 1}, 2), cell_sums (T, 4, ...) and sample_sums (N, T, 4), got {table.shape}, '
+                         f'{cell.shape}, {samp.shape}')
+    res = dict(thresholds=np.asarray(thresholds, np.float32), n_members=K, table=table)
+    nan = float('nan')
+    keys = ('base_rate', 'brier', 'brier_fair', 'reliability', 'resolution', 'uncertainty', 'bss', 'roc_auc')
+    out = {k: np.full(T, nan) for k in keys}
+    n_valid, n_events = np.zeros(T, np.int64), np.zeros(T, np.int64)
+    obs_freq, fc_count = np.full((T, K + 1), nan), np.zeros((T, K + 1), np.int64)
+    pod, pofd = np.full((T, K + 2), nan), np.full((T, K + 2), nan)
+    ratio = lambda a, b: a / b if b else nan                   # noqa: E731  (Python integers: correctly rounded)
+    for t in range(T):
+        m = [int(v) for v in table[t, :, 0]]                    # non-events with c = i
+        a = [int(v) for v in table[t, :, 1]]                    # events with c = i
+        ni = [x + y for x, y in zip(m, a)]
+        n, N1 = sum(ni), sum(a)
+        N0 = n - N1
+        n_valid[t], n_events[t] = n, N1
+        fc_count[t] = ni
+        obs_freq[t] = [ratio(a[i], ni[i]) for i in range(K + 1)]
+        num = sum(i * i * m[i] + (K - i) * (K - i) * a[i] for i in range(K + 1))
+        out['base_rate'][t] = ratio(N1, n)
+        out['brier'][t] = ratio(num, K * K * n)
+        out['brier_fair'][t] = ratio((K - 1) * num - sum(ni[i] * i * (K - i) for i in range(K + 1)), K * K * (K - 1) * n)
+        out['uncertainty'][t] = ratio(N1 * N0, n * n)
+        out['bss'][t] = ratio(K * K * N1 * N0 - num * n, K * K * N1 * N0)
+        if n:
+            # n_i (i/K - a_i/n_i)^2 = (i n_i - K a_i)^2 / (K^2 n_i);  n_i (a_i/n_i - N1/n)^2 = (a_i n - N1 n_i)^2 / (n_i n^2)
+            rel = sum((Fraction((i * ni[i] - K * a[i]) ** 2, ni[i]) for i in range(K + 1) if ni[i]), Fraction(0))
+            rsl = sum((Fraction((a[i] * n - N1 * ni[i]) ** 2, ni[i]) for i in range(K + 1) if ni[i]), Fraction(0))
+            out['reliability'][t] = float(rel / (K * K * n))
+            out['resolution'][t] = float(rsl / (n * n * n))
+        below, twice = 0, 0                                     # twice = 2 sum_i a_i (sum_{i' < i} m_i' + m_i / 2)
+        for i in range(K + 1):
+            twice += a[i] * (2 * below + m[i])
+            below += m[i]
+        out['roc_auc'][t] = ratio(twice, 2 * N1 * N0)
+        hit = fa = 0
+        pod[t, 0], pofd[t, 0] = ratio(0, N1), ratio(0, N0)
+        for j in range(1, K + 2):                               # point j: warn iff c >= K + 1 - j
+            hit += a[K + 1 - j]
+            fa += m[K + 1 - j]
+            pod[t, j], pofd[t, j] = ratio(hit, N1), ratio(fa, N0)
+    res.update(n_valid=n_valid, n_events=n_events, **out)
+    res.update(forecast_probability=_ratio_exact(np.arange(K + 1).astype(object), np.full(K + 1, K, object)),
+               observed_frequency=obs_freq, forecast_count=fc_count, roc_pod=pod, roc_pofd=pofd)
+    # per sample and per cell: n_valid, sum o, sum c, sum (c - K o)^2
+    snv = _wide(samp[..., 0], K * K * (int(samp[..., 0].max()) if samp.size else 0))
+    res.update(sample_sums=samp, n_valid_per_sample=samp[..., 0].copy(), brier_per_sample=_quotient(samp[..., 3], K * K * snv))
+    top = int(cell[:, 0].max()) if cell.size else 0             # valid samples of the fullest cell
+    nv, so, sc, sq = (_wide(cell[:, i], K * K * top * top * max(top, 1)) for i in range(4))
+    unc = K * K * so * (nv - so)
+    res.update(cell_sums=cell, n_valid_map=cell[:, 0].copy(), brier_map=_quotient(sq, K * K * nv), base_rate_map=_quotient(so, nv),
+               forecast_rate_map=_quotient(sc, K * nv), bss_map=_quotient(unc - sq * nv, unc))
+    return res
+
+
+class ExceedanceScorer:
+    """The counterpart of ``Scorer`` for exceedance probabilities (csrc/exceedance.hip): the integer
+    accumulators of one run on the device.  ``score`` is called once per batch of whole samples while the batch's member stack is
+    resident; ``result`` downloads the sums and derives the scores on the host (``exceedance_from_counts``).  ``thr32``: what
+    ``check_exceedance_args`` returned."""
+
+    def __init__(self, n_members, n_samples, sample_shape, thr32, return_fields, bmax):
+        from .device import DeviceArray
+        self.lib = _lib.lib()
+        self.K, self.N, self.sample_shape = int(n_members), int(n_samples), tuple(sample_shape)
+        self.per = int(np.prod(self.sample_shape, dtype=np.int64))
+        self.thr = np.ascontiguousarray(thr32, np.float32)
+        self.T = int(self.thr.shape[0])
+        self.per_cell = int(self.thr.ndim > 1)
+        self.return_fields = bool(return_fields)
+        self.bmax = int(bmax)
+        self.dev = dict(thr=DeviceArray.from_numpy(self.thr.reshape(-1)), cell=DeviceArray.zeros((self.T, 4, self.per), np.int64),
+                        table=DeviceArray.zeros((self.T, self.K + 1, 2), np.uint64),
+                        sample=DeviceArray((self.bmax, self.T, 4), np.int64))
+        self.sample_sums = np.zeros((self.N, self.T, 4), np.int64)
+        self.count_field = None
+        if self.return_fields:
+            self.dev['count'] = DeviceArray((self.T * self.bmax * self.per,), np.int16)
+            self.count_field = np.empty((self.N, self.T) + self.sample_shape, np.int16)
+
+    def score(self, stack_ptr, stride, obs_ptr, first, b):
+        """samples [first, first + b) of the run: their members at stack_ptr (member stride ``stride`` elements), their observation at
+        obs_ptr"""
+        lib, d = self.lib, self.dev
+        m = b * self.per
+        _lib.check(lib.dl4ds_ensemble_exceedance(stack_ptr, self.K, m, stride, obs_ptr, b, d['thr'].ptr, self.T, self.per_cell,
+                                                 d['count'].ptr if self.return_fields else None, d['sample'].ptr, d['cell'].ptr,
+                                                 d['table'].ptr))
+        _lib.check(lib.dl4ds_memcpy_d2h(self.sample_sums[first:first + b].ctypes.data, d['sample'].ptr, b * self.T * 4 * 8))
+        if self.return_fields:
+            part = np.empty((self.T, b, self.per), np.int16)                               # the entry's layout: [T][n]
+            _lib.check(lib.dl4ds_memcpy_d2h(part.ctypes.data, d['count'].ptr, part.nbytes))
+            self.count_field[first:first + b] = part.transpose(1, 0, 2).reshape((b, self.T) + self.sample_shape)
+
+    def free(self):
+        for a in self.dev.values():
+            a.free()
+        self.dev = {}
+
+    def result(self):
+        cell = self.dev['cell'].numpy().reshape((self.T, 4) + self.sample_shape)
+        res = exceedance_from_counts(self.dev['table'].numpy(), cell, self.sample_sums, self.K, self.thr)
+        if self.return_fields:
+            c = self.count_field
+            res['count_field'] = c
+            res['probability_field'] = np.where(c >= 0, c.astype(np.float32) / np.float32(self.K), np.float32(np.nan))
+        return res

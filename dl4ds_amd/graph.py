@@ -572,15 +572,36 @@ class Model:
         return self._run_ensemble(inputs, n_members, q, batch_size, seed, False,
                                   score=dict(y_true=y_true, fair=fair, scale=scale, return_fields=return_fields), who='score_ensemble')
 
-    def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, score=None, who='predict_ensemble'):
-        """The per-batch loop of ``predict_ensemble`` / ``score_ensemble``: inputs (and the observation) uploaded once per batch,
-        the members written into one device stack, reduced (and scored) there."""
+    def score_exceedance(self, inputs, y_true, n_members, thresholds, batch_size=32, seed=None, return_fields=False):
+        """``predict_ensemble`` plus the verification of the ensemble as a probability forecast of the events ``value >=
+        threshold`` against the observation ``y_true`` of shape (N,) + output_shape, counted on the device while each batch's
+        member stack is resident (csrc/exceedance.hip).  Returns ``predict_ensemble``'s dict with one more
+        key, 'exceedance': the dict ``metrics.exceedance_scores`` describes (contingency table of the forecast count c against the
+        observed event, Brier score and its decomposition, reliability diagram, ROC curve and area, Brier maps and per-sample
+        scores, all from exact integer sums).  ``thresholds``: up to 16 finite numbers, or one field per threshold shaped
+        (T,) + output_shape (NaN excludes the cell for that threshold), in the units of the model's output.  An element is valid
+        iff its observation and all its members are finite: write NaN into ``y_true`` to mask.  The counts do not depend on how
+        the scored samples are grouped (the members do depend on ``batch_size``, as in ``predict_ensemble``).  Inputs on another
+        grid than the model was built for run on the re-planned sibling (``resized``); threshold fields then have ITS output's
+        shape."""
+        n_members, q = check_ensemble_args(n_members, (), seed, batch_size)
+        from .ensemble_score import check_exceedance_args
+        # (fields are checked against the output's shape in _run_ensemble, once the model is the one planned for the inputs' grid)
+        check_exceedance_args(thresholds, None)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, who='score_exceedance',
+                                  exceed=dict(y_true=y_true, thresholds=thresholds, return_fields=return_fields))
+
+    def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, score=None, who='predict_ensemble',
+                      exceed=None):
+        """The per-batch loop of ``predict_ensemble`` / ``score_ensemble`` / ``score_exceedance``: inputs (and the observation)
+        uploaded once per batch, the members written into one device stack, reduced (and scored) there."""
         if isinstance(inputs, np.ndarray):
             inputs = [inputs]
         first = np.asarray(inputs[0])
         grid = tuple(first.shape[-3:-1])
         if grid != tuple(self.input_shapes[0][-3:-1]):
-            return self.resized(grid)._run_ensemble(inputs, n_members, q, batch_size, seed, return_members, score=score, who=who)
+            return self.resized(grid)._run_ensemble(inputs, n_members, q, batch_size, seed, return_members, score=score, who=who,
+                                                    exceed=exceed)
         from .device import DeviceArray
         inputs = [np.ascontiguousarray(a, np.float32) for a in inputs]
         n, K, nq = first.shape[0], n_members, len(q)
@@ -591,6 +612,12 @@ class Model:
             if y_true.shape != (n,) + self.output_shape:
                 raise ValueError(f'`y_true` must have the shape of the prediction {(n,) + self.output_shape}, got {y_true.shape}')
             scale = check_score_args(score['fair'], score['scale'], self.output_shape)
+        if exceed is not None:
+            from .ensemble_score import check_exceedance_args
+            y_true = np.ascontiguousarray(exceed['y_true'], np.float32)
+            if y_true.shape != (n,) + self.output_shape:
+                raise ValueError(f'`y_true` must have the shape of the prediction {(n,) + self.output_shape}, got {y_true.shape}')
+            thr = check_exceedance_args(exceed['thresholds'], self.output_shape)
         if self.graph.dropout_mc_count() == 0:
             import warnings
             warnings.warn(f'model {self.name} has no MC dropout layer: the {K} ensemble members are identical (build it with '
@@ -622,6 +649,10 @@ class Model:
                 from .ensemble_score import Scorer
                 dev_obs = DeviceArray((stride,))
                 scorer = Scorer(K, n, self.output_shape, q, score['fair'], seed, scale, score['return_fields'], bmax)
+            if exceed is not None:
+                from .ensemble_score import ExceedanceScorer
+                dev_obs = DeviceArray((stride,))
+                scorer = ExceedanceScorer(K, n, self.output_shape, thr, exceed['return_fields'], bmax)
             for i in range(0, n, bmax):
                 part, b = self._prep_inputs([a[i:i + bmax] for a in inputs])
                 m = b * per
@@ -643,7 +674,7 @@ class Model:
                     for k in range(K):
                         _lib.check(lib.dl4ds_memcpy_d2h(res['members'][k, i:i + b].ctypes.data, stack.ptr + k * stride * 4, m * 4))
             if scorer is not None:
-                res['scores'] = scorer.result()
+                res['scores' if exceed is None else 'exceedance'] = scorer.result()
         finally:
             for a in pinned:
                 lib.dl4ds_host_unregister(a.ctypes.data)

@@ -130,16 +130,17 @@ def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, 
     return (res, np.asarray(inputs[0])) if return_lr else res
 
 
-def _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, array_in_hr, time_window, batch_size, scaler=None):
-    """Everything ``verify_ensemble`` can refuse from its arguments alone (no library, no device) -> the observation as an array
-    with a channel axis."""
+def _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, array_in_hr, time_window, batch_size, scaler=None,
+                       who='verify_ensemble', model_method='Model.score_ensemble'):
+    """Everything ``verify_ensemble`` / ``verify_exceedance`` can refuse from the arguments they share (no library, no device) ->
+    the observation as an array with a channel axis."""
     from .graph import check_ensemble_args
     from .ensemble_score import check_score_args
     check_ensemble_args(n_members, quantiles, seed, batch_size)
     check_score_args(fair)
     if time_window is not None:
-        raise ValueError('verify_ensemble: `time_window` is not supported: how scores of overlapping windows flatten to spatial '
-                         'samples is not defined yet (score the 5-D output with Model.score_ensemble)')
+        raise ValueError(f'{who}: `time_window` is not supported: how scores of overlapping windows flatten to spatial '
+                         f'samples is not defined yet (score the 5-D output with {model_method})')
     array = np.asarray(getattr(array, 'values', array))
     if y_true is None:
         if not array_in_hr:
@@ -209,6 +210,78 @@ def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(),
     return (res, np.asarray(inputs[0])) if return_lr else res
 
 
+def _model_unit_thresholds(thresholds, scaler, sample_shape):
+    """Physical ``thresholds`` (checked by ``check_exceedance_args``; (T,) values or (T,) + sample_shape fields) -> (float32 threshold fields (T,) + sample_shape in the
+    model's units, number of cells excluded): every threshold goes through ``scaler.transform`` as a field, evaluated on two
+    samples of which the first is kept (the scalers drop size-1 axes); cells whose ``scaler_slope`` is not finite and positive
+    get NaN."""
+    sample_shape = tuple(sample_shape)
+    try:
+        slope = np.asarray(scaler_slope(scaler, sample_shape), np.float64)
+        fields = []
+        for t in thresholds:
+            both = np.broadcast_to(np.asarray(t, np.float64), (2,) + sample_shape).copy()
+            fields.append(np.asarray(scaler.transform(both), np.float32)[0].reshape(sample_shape))
+    except IndexError:
+        raise ValueError('verify_exceedance: `scaler` has no per-cell transform for one sample (a scaler fitted on data with NaNs '
+                         'carries a mask of the full array\'s shape); that is not supported') from None
+    thr = np.stack(fields)
+    with np.errstate(invalid='ignore'):
+        bad = ~(np.isfinite(slope) & (slope > 0))
+    bad = np.broadcast_to(bad.reshape(sample_shape) if bad.size == int(np.prod(sample_shape)) else bad, sample_shape)
+    thr[:, bad] = np.nan
+    return thr, int(np.count_nonzero(bad))
+
+
+def verify_exceedance(trainer, array, scale, n_members, thresholds, y_true=None, seed=None, mask=None, array_in_hr=True,
+                      static_vars=None, predictors=None, time_window=None, time_metadata=None, interpolation='inter_area',
+                      batch_size=64, scaler=None, save_path=None, save_fname='y_hat_exceedance.npz', return_lr=False, device='GPU'):
+    """``predict_ensemble`` plus the verification of the ensemble as a PROBABILITY forecast of the events ``value >= threshold``,
+    counted on the device while the member stack is resident (``Model.score_exceedance``, csrc/exceedance.hip): returns
+    ``predict_ensemble``'s dict of statistics with one more key, 'exceedance' -- the contingency table of the forecast count
+    against the observed event, the Brier score with its reliability / resolution / uncertainty decomposition and the skill
+    score, the reliability diagram, the ROC curve and its area, Brier maps and per-sample scores; see
+    ``metrics.exceedance_scores`` for every key.  All of them come from exact integer sums.
+
+    ``thresholds``: up to 16 numbers in PHYSICAL units (or one field per threshold shaped like one sample of the result).
+    ``y_true``, ``mask``: as in ``verify_ensemble`` (the observation in physical units; None means the HR ``array`` itself, allowed
+    only with ``array_in_hr=True`` and without a ``scaler``).  ``scaler``: the observation goes through ``scaler.transform`` and
+    each threshold becomes a per-cell field in the model's units (``scaler.transform`` of a constant field): EVENTS ARE DECIDED IN
+    THE MODEL'S UNITS, where the members live; for the increasing affine scalers of ``dl4ds_amd.preprocessing`` that is the event
+    in physical units up to the float32 rounding of the transform.  Cells whose ``scaler_slope`` is not finite and positive get a
+    NaN threshold, take no part, and are counted in ``exceedance['n_cells_excluded']``.  NaN in ``y_true`` stays NaN through the
+    transform.  ``save_path``: one ``np.savez`` of the statistics and the scores (flattened with an ``exceedance_`` prefix).
+
+    Out of scope: recurrent models.  ``time_window is not None`` raises ValueError, because how the scores of overlapping windows
+    flatten to spatial samples is not defined yet."""
+    from .ensemble_score import check_exceedance_args
+    y_true = _check_verify_args(array, scale, n_members, y_true, (), seed, False, array_in_hr, time_window, batch_size, scaler,
+                                who='verify_exceedance', model_method='Model.score_exceedance')
+    thr = check_exceedance_args(thresholds, y_true.shape[1:])
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    from .metrics import _masked_observation
+    obs, excluded = y_true, 0
+    if scaler is not None:
+        # (as in verify_ensemble: the transform fills NaN and may write into its argument)
+        bad = ~np.isfinite(np.asarray(y_true, np.float64))
+        obs = np.array(scaler.transform(np.array(y_true, copy=True)), np.float32).reshape(y_true.shape)
+        obs[bad] = np.nan
+        # (the caller's float64 values are transformed, not their float32 roundings)
+        physical = np.asarray(getattr(thresholds, 'values', thresholds), np.float64).reshape(thr.shape)
+        thr, excluded = _model_unit_thresholds(physical, scaler, y_true.shape[1:])
+    obs = _masked_observation(obs, mask)
+    res = model.score_exceedance(inputs, obs, n_members, thr, batch_size=batch_size, seed=seed)
+    scores = res.pop('exceedance')
+    scores['n_cells_excluded'] = excluded
+    _finish_ensemble(res, scaler, time_window)
+    res['exceedance'] = scores
+    if save_path is not None and save_fname is not None:
+        flat = {k: v for k, v in res.items() if k != 'exceedance'}
+        flat.update({'exceedance_' + k: np.asarray(v) for k, v in scores.items()})
+        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **flat)
+    return (res, np.asarray(inputs[0])) if return_lr else res
+
+
 class Predictor:
     """inference.py:12-106."""
 
@@ -255,3 +328,18 @@ class EnsembleVerifier:
 
     def run(self):
         return verify_ensemble(**self.kw)
+
+
+class ExceedanceVerifier:
+    """``EnsembleVerifier`` for exceedance probabilities: same constructor-then-``.run()`` shape, runs ``verify_exceedance``."""
+
+    def __init__(self, trainer, array, scale, n_members, thresholds, y_true=None, seed=None, mask=None, array_in_hr=False,
+                 static_vars=None, predictors=None, time_window=None, time_metadata=None, interpolation='inter_area', batch_size=64,
+                 scaler=None, save_path=None, save_fname='y_hat_exceedance.npz', return_lr=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, n_members=n_members, thresholds=thresholds, y_true=y_true,
+                       seed=seed, mask=mask, array_in_hr=array_in_hr, static_vars=static_vars, predictors=predictors,
+                       time_window=time_window, time_metadata=time_metadata, interpolation=interpolation, batch_size=batch_size,
+                       scaler=scaler, save_path=save_path, save_fname=save_fname, return_lr=return_lr, device=device)
+
+    def run(self):
+        return verify_exceedance(**self.kw)

@@ -259,6 +259,66 @@ def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None
         dev_obs.free()
 
 
+def exceedance_scores(y_true, members, thresholds, mask=None, batch_size=None, return_fields=False):
+    """Verification of an ensemble the caller already has on the host as a PROBABILITY forecast of the events ``value >=
+    threshold``: ``members`` shaped (K,) + y_true.shape against the observation ``y_true`` (samples on the leading axis), uploaded
+    in chunks of ``batch_size`` samples (default: chunks of at most 256 MiB of members) and counted on the device by the entry
+    ``Model.score_exceedance`` uses (csrc/exceedance.hip).  ``thresholds``: up to 16 finite numbers, or one
+    field per threshold shaped (T,) + y_true.shape[1:] (a local percentile; NaN excludes the cell for that threshold).  An element
+    is valid iff its observation and all its members are finite and ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it.
+    With c of the K members at or above the threshold the forecast probability is c / K: the device returns exact int64 sums, so
+    the result equals an integer reference and does not depend on ``batch_size``.  Returns a dict (T thresholds, N samples):
+
+    * ``thresholds`` (float32, as used), ``n_members``, ``table`` (T, K + 1, 2) int64: valid elements with c = i and the event
+      not observed / observed; ``n_valid``, ``n_events``, ``base_rate`` (T,);
+    * ``brier`` (T,), ``brier_fair`` (Ferro's fair Brier score, NaN for K = 1), ``reliability``, ``resolution``, ``uncertainty``
+      (brier = reliability - resolution + uncertainty holds exactly: the forecast takes only the K + 1 values i / K), ``bss`` =
+      1 - brier / uncertainty;
+    * ``forecast_probability`` (K + 1,), ``observed_frequency`` and ``forecast_count`` (T, K + 1): the reliability diagram and
+      the sharpness histogram;
+    * ``roc_pod``, ``roc_pofd`` (T, K + 2): point j warns iff c >= K + 1 - j, from (0, 0) to (1, 1); ``roc_auc`` (T,): the
+      trapezoid area (Mann-Whitney with ties);
+    * ``sample_sums`` (N, T, 4) and ``cell_sums`` (T, 4) + sample shape, int64: n_valid, sum o, sum c, sum (c - K o)^2;
+      ``brier_per_sample``, ``n_valid_per_sample`` (N, T); ``brier_map``, ``base_rate_map``, ``forecast_rate_map``, ``bss_map``,
+      ``n_valid_map`` (T,) + sample shape;
+    * with ``return_fields``: ``count_field`` int16 (N, T) + sample shape (c, -1 where invalid) and ``probability_field``
+      float32 (c / K, NaN where invalid).
+
+    Every ratio is a quotient of integers rounded to float64 once (Python integers, or one IEEE division where both operands are
+    below 2^53), NaN on a zero denominator."""
+    from .graph import check_ensemble_args
+    from .ensemble_score import ExceedanceScorer, check_exceedance_args
+    members = np.asarray(members)
+    if members.ndim < 2:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape, got {members.shape}')
+    K, _ = check_ensemble_args(int(members.shape[0]), (), None, batch_size)
+    y_true = np.asarray(getattr(y_true, 'values', y_true))
+    if y_true.ndim < 1 or members.shape[1:] != y_true.shape:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape = (K,) + {y_true.shape}, got {members.shape}')
+    N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
+    thr = check_exceedance_args(thresholds, sample_shape)
+    obs = _masked_observation(y_true, mask)
+    per = int(np.prod(sample_shape, dtype=np.int64))
+    bmax = _upload_batch(batch_size, max(K * per, 1), N)
+    stride = bmax * per
+    scorer = ExceedanceScorer(K, N, sample_shape, thr, return_fields, bmax)
+    stack, dev_obs = DeviceArray((K, stride)), DeviceArray((stride,))
+    lib = _lib.lib()
+    try:
+        for i in range(0, N, bmax):
+            b = min(bmax, N - i)
+            for k in range(K):
+                part = np.ascontiguousarray(members[k, i:i + b], np.float32)
+                _lib.check(lib.dl4ds_memcpy_h2d(stack.ptr + k * stride * 4, part.ctypes.data, part.nbytes))
+            _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, obs[i:i + b].ctypes.data, b * per * 4))
+            scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
+        return scorer.result()
+    finally:
+        scorer.free()
+        stack.free()
+        dev_obs.free()
+
+
 FSS_DEFAULT_WINDOWS = (1, 3, 5, 9, 17, 33, 65)
 FSS_SUM_BOUND = 1 << 62                            # H*W*m^2 must stay below it: the 64-bit sums of dl4ds_fss are exact
 FSS_CELL_BOUND = 1 << 31

@@ -219,6 +219,34 @@ int dl4ds_ensemble_score(const float* members_dev, size_t K, size_t n, size_t me
                          const float* q_host, int nq, float* crps_dev, float* sqerr_dev, float* var_dev, int* rank_dev,
                          double* sample_out_dev, double* cell_acc_dev, unsigned long long* rank_hist_dev,
                          unsigned long long* covered_dev);
+/* Exceedance-probability verification of an MC-dropout ensemble against an observation at T thresholds.  Serves the same MC*
+ * layers of blocks.py:658-676: the reference defines them and leaves both the ensemble loop and its verification to the user; the
+ * definitions are DESIGN.md section 17.  members_dev, K, n, member_stride, obs_dev and B as for dl4ds_ensemble_score: K rows of n
+ * fp32 values (row k at members_dev + k * member_stride, 1 <= K <= 256), the observation obs_dev [n], the n elements being B whole
+ * samples of per = n / B cells.  thr_dev: the 1 <= T <= 16 thresholds, a DEVICE array; thr_per_cell == 0: [T] values, thr(t, e) =
+ * thr_dev[t]; otherwise [T][per], a threshold field per cell (a local climatological percentile), thr(t, e) = thr_dev[t * per +
+ * e % per].  Thresholds may come in any order and may repeat.
+ * Element e is VALID for threshold t iff obs[e] and all K members are finite (no NaN, no infinity) and thr(t, e) is finite: NaN in
+ * obs_dev is the masking mechanism, a NaN threshold excludes its cell for that threshold only.  Per valid (t, e), every comparison on
+ * float32 (-0.0 equals +0.0):
+ *   o = [obs[e] >= thr(t, e)]            the event was observed
+ *   c = #{k : x_k[e] >= thr(t, e)}       0 ... K members forecast it: the forecast probability is c / K
+ * Outputs (each may be null and is then skipped):
+ *   count_dev      [T][n]        int16: c, or -1 where invalid; overwritten
+ *   sample_out_dev [B][T][4]     int64: per sample n_valid, sum o, sum c, sum (c - K o)^2 (K^2 n_valid times its Brier score);
+ *                                overwritten
+ *   cell_acc_dev   [T][4][per]   int64: the same four per cell, ADDED onto accumulators that the caller has zeroed
+ *   table_dev      [T][K + 1][2] uint64: the number of valid elements with c = i and o = 0 / 1, ADDED
+ * Integer arithmetic only (integer atomics, no floating-point accumulation anywhere): the sums equal an integer reference and do
+ * not depend on the order of the atomics, on how the samples are grouped into calls, or on B.  Partial sums narrower than 64 bits
+ * are flushed before they can overflow: a lane walks at most dl4ds_ensemble_exceedance_walk_limit(K) = min(65535, (2^32 - 1) /
+ * K^2) samples ((c - K o)^2 reaches K^2 per element), a call with more samples is split across workgroups.
+ * Refused (non-zero return, dl4ds_last_error): K or T out of range, n % B != 0, member_stride < n, null members_dev, obs_dev or
+ * thr_dev.  Algorithmic traffic (K + 1) * 4 * n bytes read once, plus 2 T n bytes written with count_dev. */
+int dl4ds_ensemble_exceedance(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                              const float* thr_dev, int T, int thr_per_cell, short* count_dev, long long* sample_out_dev,
+                              long long* cell_acc_dev, unsigned long long* table_dev);
+int dl4ds_ensemble_exceedance_walk_limit(size_t K, size_t* samples_out);
 /* Neighbourhood (scale- and threshold-dependent) verification of a prediction against an observation: the Fractions Skill Score
  * of Roberts & Lean (2008) and the 2 x 2 contingency table.  The reference has no such metric; the definitions are DESIGN.md
  * section 14.  y_dev / p_dev: observation and prediction, (N, H, W, C) fp32; each of the N*C planes is one field.
