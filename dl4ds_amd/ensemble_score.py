@@ -6,6 +6,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
+from ._exact import finite_float32, int_ratio, quotient, ratio_exact, wide
+from .device import DeviceArray
 
 U64 = 0xFFFFFFFFFFFFFFFF
 
@@ -29,54 +31,70 @@ def as_signed64(v):
     return v - (1 << 64) if v >> 63 else v
 
 
-class Scorer:
-    """Accumulators of one verification run on the device.  ``score`` is called once per batch of whole samples while the batch's
-    member stack is resident; ``result`` downloads the sums and takes the means in float64."""
+class _Accumulators:
+    """What the scorers of one verification run share: ``score`` is called once per batch of whole samples while the batch's
+    member stack is resident (the library call of the subclass, then the download of the batch's per-sample sums and, with
+    ``return_fields``, of its fields: ``_launch`` and ``_download_fields``); ``result`` downloads the run's sums and derives the
+    scores on the host; ``free`` releases the device buffers, all of which live in ``dev``.
+    ``sums``, ``dtype``: the shape and type of one sample's sums."""
 
-    def __init__(self, n_members, n_samples, sample_shape, q32, fair, seed, scale, return_fields, bmax):
-        from .device import DeviceArray
+    def __init__(self, n_members, n_samples, sample_shape, return_fields, bmax, sums, dtype):
         self.lib = _lib.lib()
         self.K, self.N, self.sample_shape = int(n_members), int(n_samples), tuple(sample_shape)
         self.per = int(np.prod(self.sample_shape, dtype=np.int64))
+        self.return_fields = bool(return_fields)
+        self.bmax = int(bmax)
+        self.dev = dict(sample=DeviceArray((self.bmax,) + sums, dtype))
+        self.sample_sums = np.zeros((self.N,) + sums, dtype)
+
+    def score(self, stack_ptr, stride, obs_ptr, first, b):
+        """samples [first, first + b) of the run: their members at stack_ptr (member stride ``stride`` elements), their observation at
+        obs_ptr"""
+        self._launch(stack_ptr, stride, obs_ptr, first, b)
+        self.dev['sample'].download(self.sample_sums[first:first + b])
+        if self.return_fields:
+            self._download_fields(first, b)
+
+    def free(self):
+        for a in self.dev.values():
+            a.free()
+        self.dev = {}
+
+
+class Scorer(_Accumulators):
+    """Accumulators of the CRPS / rank-histogram / spread-skill verification on the device (csrc/ensemble_score.hip); ``result``
+    takes the means in float64."""
+
+    def __init__(self, n_members, n_samples, sample_shape, q32, fair, seed, scale, return_fields, bmax):
+        super().__init__(n_members, n_samples, sample_shape, return_fields, bmax, (4,), np.float64)
         self.q = np.asarray(q32, np.float32)
         self.nq = len(self.q)
         self.qc = (ctypes.c_float * max(self.nq, 1))(*self.q.tolist())
         self.fair, self.seed = int(bool(fair)), as_signed64(0 if seed is None else seed)
-        self.return_fields = bool(return_fields)
-        self.bmax = int(bmax)
         self.n_cells_excluded = 0
-        self.dev = dict(cell=DeviceArray.zeros((4, self.per), np.float64), hist=DeviceArray.zeros((self.K + 1,), np.uint64),
-                        cov=DeviceArray.zeros((max(self.nq, 1),), np.uint64), sample=DeviceArray((self.bmax, 4), np.float64))
+        self.dev.update(cell=DeviceArray.zeros((4, self.per), np.float64), hist=DeviceArray.zeros((self.K + 1,), np.uint64),
+                        cov=DeviceArray.zeros((max(self.nq, 1),), np.uint64))
         if scale is not None:
             scale = np.ascontiguousarray(scale, np.float32).reshape(self.per)
             with np.errstate(invalid='ignore'):
                 self.n_cells_excluded = int(np.count_nonzero(~(np.isfinite(scale) & (scale > 0))))
             self.dev['scale'] = DeviceArray.from_numpy(scale)
-        self.sample_sums = np.zeros((self.N, 4), np.float64)
         self.fields = {}
         if self.return_fields:
             for k in ('crps', 'sqerr', 'var', 'rank'):
                 self.dev[k] = DeviceArray((self.bmax * self.per,), np.int32 if k == 'rank' else np.float32)
                 self.fields[k + '_field'] = np.empty((self.N,) + self.sample_shape, self.dev[k].dtype)
 
-    def score(self, stack_ptr, stride, obs_ptr, first, b):
-        """samples [first, first + b) of the run: their members at stack_ptr (member stride ``stride`` elements), their observation at
-        obs_ptr"""
-        lib, d = self.lib, self.dev
-        m = b * self.per
+    def _launch(self, stack_ptr, stride, obs_ptr, first, b):
+        d = self.dev
         ptr = lambda k: d[k].ptr if k in d else None                                       # noqa: E731
-        _lib.check(lib.dl4ds_ensemble_score(stack_ptr, self.K, m, stride, obs_ptr, b, first * self.per, ptr('scale'), self.fair,
-                                            self.seed, self.qc, self.nq, ptr('crps'), ptr('sqerr'), ptr('var'), ptr('rank'), d['sample'].ptr,
-                                            d['cell'].ptr, d['hist'].ptr, d['cov'].ptr))
-        _lib.check(lib.dl4ds_memcpy_d2h(self.sample_sums[first:first + b].ctypes.data, d['sample'].ptr, b * 4 * 8))
-        if self.return_fields:
-            for k in ('crps', 'sqerr', 'var', 'rank'):
-                _lib.check(lib.dl4ds_memcpy_d2h(self.fields[k + '_field'][first:first + b].ctypes.data, d[k].ptr, m * 4))
+        _lib.check(self.lib.dl4ds_ensemble_score(stack_ptr, self.K, b * self.per, stride, obs_ptr, b, first * self.per, ptr('scale'),
+                                                 self.fair, self.seed, self.qc, self.nq, ptr('crps'), ptr('sqerr'), ptr('var'),
+                                                 ptr('rank'), d['sample'].ptr, d['cell'].ptr, d['hist'].ptr, d['cov'].ptr))
 
-    def free(self):
-        for a in self.dev.values():
-            a.free()
-        self.dev = {}
+    def _download_fields(self, first, b):
+        for k in ('crps', 'sqerr', 'var', 'rank'):
+            self.dev[k].download(self.fields[k + '_field'][first:first + b])
 
     def result(self):
         cell = self.dev['cell'].numpy()
@@ -128,33 +146,12 @@ def check_exceedance_args(thresholds, sample_shape):
         raise ValueError('`thresholds` must not be empty')
     if t64.shape[0] > EXCEEDANCE_MAX_THRESHOLDS:
         raise ValueError(f'at most {EXCEEDANCE_MAX_THRESHOLDS} thresholds per call, got {t64.shape[0]}')
-    with np.errstate(over='ignore'):
-        thr = t64.astype(np.float32)
     if t64.ndim == 1:
-        if not np.isfinite(t64).all() or not np.isfinite(thr).all():
-            raise ValueError('scalar `thresholds` must be finite (as float32)')
-    elif sample_shape is not None and tuple(t64.shape[1:]) != sample_shape:
+        return finite_float32(t64, 'scalar `thresholds`')
+    if sample_shape is not None and tuple(t64.shape[1:]) != sample_shape:
         raise ValueError(f'per-cell `thresholds` must be shaped (T,) + {sample_shape}, one field per threshold, got {t64.shape}')
-    return np.ascontiguousarray(thr)
-
-
-def _quotient(num, den):
-    """num / den element-wise for integer arrays (int64, or object arrays of Python integers), each quotient correctly rounded to
-    fp64, NaN where den == 0.  Operands below 2^53 are exact in fp64, where one IEEE division is the correctly rounded quotient;
-    anything larger goes through Python integers (``metrics._ratio_exact``)."""
-    from .metrics import _ratio_exact
-    num, den = np.asarray(num), np.asarray(den)
-    num, den = np.broadcast_arrays(num, den)
-    if num.dtype != object and den.dtype != object and (num.size == 0 or (max(int(np.abs(num).max()), int(np.abs(den).max())) < 1 << 53)):
-        n, d = num.astype(np.float64), den.astype(np.float64)
-        with np.errstate(divide='ignore', invalid='ignore'):
-            return np.where(d == 0, np.nan, n / np.where(d == 0, 1.0, d))
-    return _ratio_exact(num.astype(object), den.astype(object))
-
-
-def _wide(a, bound):
-    """int64 array ``a`` as it is when products up to ``bound`` fit into int64, else as Python integers"""
-    return a if bound < 1 << 62 else a.astype(object)
+    with np.errstate(over='ignore'):
+        return np.ascontiguousarray(t64, np.float32)
 
 
 def exceedance_from_counts(table, cell_sums, sample_sums, n_members, thresholds):
@@ -163,7 +160,6 @@ def exceedance_from_counts(table, cell_sums, sample_sums, n_members, thresholds)
     integers is evaluated on Python integers (or on fp64 operands that hold them exactly) and rounded once; a quotient with a zero
     denominator is NaN."""
     from fractions import Fraction
-    from .metrics import _ratio_exact
     K = int(n_members)
     table = np.asarray(table).astype(np.int64)
     cell = np.asarray(cell_sums).astype(np.int64)
@@ -179,7 +175,7 @@ def exceedance_from_counts(table, cell_sums, sample_sums, n_members, thresholds)
     n_valid, n_events = np.zeros(T, np.int64), np.zeros(T, np.int64)
     obs_freq, fc_count = np.full((T, K + 1), nan), np.zeros((T, K + 1), np.int64)
     pod, pofd = np.full((T, K + 2), nan), np.full((T, K + 2), nan)
-    ratio = lambda a, b: a / b if b else nan                   # noqa: E731  (Python integers: correctly rounded)
+    ratio = int_ratio                                           # (Python integers: correctly rounded)
     for t in range(T):
         m = [int(v) for v in table[t, :, 0]]                    # non-events with c = i
         a = [int(v) for v in table[t, :, 1]]                    # events with c = i
@@ -213,62 +209,46 @@ def exceedance_from_counts(table, cell_sums, sample_sums, n_members, thresholds)
             fa += m[K + 1 - j]
             pod[t, j], pofd[t, j] = ratio(hit, N1), ratio(fa, N0)
     res.update(n_valid=n_valid, n_events=n_events, **out)
-    res.update(forecast_probability=_ratio_exact(np.arange(K + 1).astype(object), np.full(K + 1, K, object)),
+    res.update(forecast_probability=ratio_exact(np.arange(K + 1).astype(object), np.full(K + 1, K, object)),
                observed_frequency=obs_freq, forecast_count=fc_count, roc_pod=pod, roc_pofd=pofd)
     # per sample and per cell: n_valid, sum o, sum c, sum (c - K o)^2
-    snv = _wide(samp[..., 0], K * K * (int(samp[..., 0].max()) if samp.size else 0))
-    res.update(sample_sums=samp, n_valid_per_sample=samp[..., 0].copy(), brier_per_sample=_quotient(samp[..., 3], K * K * snv))
+    snv = wide(samp[..., 0], K * K * (int(samp[..., 0].max()) if samp.size else 0))
+    res.update(sample_sums=samp, n_valid_per_sample=samp[..., 0].copy(), brier_per_sample=quotient(samp[..., 3], K * K * snv))
     top = int(cell[:, 0].max()) if cell.size else 0             # valid samples of the fullest cell
-    nv, so, sc, sq = (_wide(cell[:, i], K * K * top * top * max(top, 1)) for i in range(4))
+    nv, so, sc, sq = (wide(cell[:, i], K * K * top * top * max(top, 1)) for i in range(4))
     unc = K * K * so * (nv - so)
-    res.update(cell_sums=cell, n_valid_map=cell[:, 0].copy(), brier_map=_quotient(sq, K * K * nv), base_rate_map=_quotient(so, nv),
-               forecast_rate_map=_quotient(sc, K * nv), bss_map=_quotient(unc - sq * nv, unc))
+    res.update(cell_sums=cell, n_valid_map=cell[:, 0].copy(), brier_map=quotient(sq, K * K * nv), base_rate_map=quotient(so, nv),
+               forecast_rate_map=quotient(sc, K * nv), bss_map=quotient(unc - sq * nv, unc))
     return res
 
 
-class ExceedanceScorer:
+class ExceedanceScorer(_Accumulators):
     """The counterpart of ``Scorer`` for exceedance probabilities (csrc/exceedance.hip): the integer
-    accumulators of one run on the device.  ``score`` is called once per batch of whole samples while the batch's member stack is
-    resident; ``result`` downloads the sums and derives the scores on the host (``exceedance_from_counts``).  ``thr32``: what
+    accumulators of one run on the device; ``result`` derives the scores on the host (``exceedance_from_counts``).  ``thr32``: what
     ``check_exceedance_args`` returned."""
 
     def __init__(self, n_members, n_samples, sample_shape, thr32, return_fields, bmax):
-        from .device import DeviceArray
-        self.lib = _lib.lib()
-        self.K, self.N, self.sample_shape = int(n_members), int(n_samples), tuple(sample_shape)
-        self.per = int(np.prod(self.sample_shape, dtype=np.int64))
         self.thr = np.ascontiguousarray(thr32, np.float32)
         self.T = int(self.thr.shape[0])
         self.per_cell = int(self.thr.ndim > 1)
-        self.return_fields = bool(return_fields)
-        self.bmax = int(bmax)
-        self.dev = dict(thr=DeviceArray.from_numpy(self.thr.reshape(-1)), cell=DeviceArray.zeros((self.T, 4, self.per), np.int64),
-                        table=DeviceArray.zeros((self.T, self.K + 1, 2), np.uint64),
-                        sample=DeviceArray((self.bmax, self.T, 4), np.int64))
-        self.sample_sums = np.zeros((self.N, self.T, 4), np.int64)
+        super().__init__(n_members, n_samples, sample_shape, return_fields, bmax, (self.T, 4), np.int64)
+        self.dev.update(thr=DeviceArray.from_numpy(self.thr.reshape(-1)), cell=DeviceArray.zeros((self.T, 4, self.per), np.int64),
+                        table=DeviceArray.zeros((self.T, self.K + 1, 2), np.uint64))
         self.count_field = None
         if self.return_fields:
             self.dev['count'] = DeviceArray((self.T * self.bmax * self.per,), np.int16)
             self.count_field = np.empty((self.N, self.T) + self.sample_shape, np.int16)
 
-    def score(self, stack_ptr, stride, obs_ptr, first, b):
-        """samples [first, first + b) of the run: their members at stack_ptr (member stride ``stride`` elements), their observation at
-        obs_ptr"""
-        lib, d = self.lib, self.dev
-        m = b * self.per
-        _lib.check(lib.dl4ds_ensemble_exceedance(stack_ptr, self.K, m, stride, obs_ptr, b, d['thr'].ptr, self.T, self.per_cell,
-                                                 d['count'].ptr if self.return_fields else None, d['sample'].ptr, d['cell'].ptr,
-                                                 d['table'].ptr))
-        _lib.check(lib.dl4ds_memcpy_d2h(self.sample_sums[first:first + b].ctypes.data, d['sample'].ptr, b * self.T * 4 * 8))
-        if self.return_fields:
-            part = np.empty((self.T, b, self.per), np.int16)                               # the entry's layout: [T][n]
-            _lib.check(lib.dl4ds_memcpy_d2h(part.ctypes.data, d['count'].ptr, part.nbytes))
-            self.count_field[first:first + b] = part.transpose(1, 0, 2).reshape((b, self.T) + self.sample_shape)
+    def _launch(self, stack_ptr, stride, obs_ptr, first, b):
+        d = self.dev
+        _lib.check(self.lib.dl4ds_ensemble_exceedance(stack_ptr, self.K, b * self.per, stride, obs_ptr, b, d['thr'].ptr, self.T,
+                                                      self.per_cell, d['count'].ptr if self.return_fields else None,
+                                                      d['sample'].ptr, d['cell'].ptr, d['table'].ptr))
 
-    def free(self):
-        for a in self.dev.values():
-            a.free()
-        self.dev = {}
+    def _download_fields(self, first, b):
+        part = np.empty((self.T, b, self.per), np.int16)                                   # the entry's layout: [T][n]
+        self.dev['count'].download(part)
+        self.count_field[first:first + b] = part.transpose(1, 0, 2).reshape((b, self.T) + self.sample_shape)
 
     def result(self):
         cell = self.dev['cell'].numpy().reshape((self.T, 4) + self.sample_shape)

@@ -8,6 +8,9 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib
+from ._chunks import check_batch_size, is_int
+from .device import Buffers
+from .ensemble_score import ExceedanceScorer, Scorer, check_exceedance_args, check_score_args
 
 ACT_KINDS = {'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'leaky_relu': 5, 'selu': 6, 'gelu': 7}
 
@@ -412,8 +415,6 @@ ENSEMBLE_MAX_QUANTILES = 32
 def check_ensemble_args(n_members, quantiles, seed=None, batch_size=None):
     """Arguments of ``predict_ensemble`` -> (n_members as int, probabilities as a float32 array).  Raises ValueError for anything
     else; looks at its arguments only (no library, no device)."""
-    def is_int(v):
-        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
     if not is_int(n_members):
         raise ValueError(f'`n_members` must be an integer, got {n_members!r}')
     if not 1 <= n_members <= ENSEMBLE_MAX_MEMBERS:
@@ -430,8 +431,7 @@ def check_ensemble_args(n_members, quantiles, seed=None, batch_size=None):
         raise ValueError(f'at most {ENSEMBLE_MAX_QUANTILES} quantiles per call, got {q.size}')
     if seed is not None and not is_int(seed):
         raise ValueError(f'`seed` must be None or an integer, got {seed!r}')
-    if batch_size is not None and (not is_int(batch_size) or batch_size < 1):
-        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
+    check_batch_size(batch_size, integers_only=True)
     return int(n_members), q.astype(np.float32)
 
 
@@ -567,10 +567,12 @@ class Model:
         ``seed=None``: the ranks do not depend on ``batch_size`` (the members do, as in ``predict_ensemble``).  Scores are per
         element and "sample" is the leading axis, whatever the output's rank; the stack is read twice (statistics, then scores)."""
         n_members, q = check_ensemble_args(n_members, quantiles, seed, batch_size)
-        from .ensemble_score import check_score_args
         check_score_args(fair)
-        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False,
-                                  score=dict(y_true=y_true, fair=fair, scale=scale, return_fields=return_fields), who='score_ensemble')
+
+        def prepare(shape):
+            scale32 = check_score_args(fair, scale, shape)
+            return lambda n, bmax: Scorer(n_members, n, shape, q, fair, seed, scale32, return_fields, bmax)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('scores', y_true, prepare), 'score_ensemble')
 
     def score_exceedance(self, inputs, y_true, n_members, thresholds, batch_size=32, seed=None, return_fields=False):
         """``predict_ensemble`` plus the verification of the ensemble as a probability forecast of the events ``value >=
@@ -585,39 +587,33 @@ class Model:
         grid than the model was built for run on the re-planned sibling (``resized``); threshold fields then have ITS output's
         shape."""
         n_members, q = check_ensemble_args(n_members, (), seed, batch_size)
-        from .ensemble_score import check_exceedance_args
         # (fields are checked against the output's shape in _run_ensemble, once the model is the one planned for the inputs' grid)
         check_exceedance_args(thresholds, None)
-        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, who='score_exceedance',
-                                  exceed=dict(y_true=y_true, thresholds=thresholds, return_fields=return_fields))
 
-    def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, score=None, who='predict_ensemble',
-                      exceed=None):
+        def prepare(shape):
+            thr = check_exceedance_args(thresholds, shape)
+            return lambda n, bmax: ExceedanceScorer(n_members, n, shape, thr, return_fields, bmax)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('exceedance', y_true, prepare), 'score_exceedance')
+
+    def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, verify=None, who='predict_ensemble'):
         """The per-batch loop of ``predict_ensemble`` / ``score_ensemble`` / ``score_exceedance``: inputs (and the observation)
-        uploaded once per batch, the members written into one device stack, reduced (and scored) there."""
+        uploaded once per batch, the members written into one device stack, reduced (and scored) there.  ``verify``: (the result's
+        key, the observation, prepare), where prepare(output_shape) checks the arguments that need the output's shape and returns
+        what builds the scorer (ensemble_score.py) for n samples in batches of bmax: prepare(output_shape)(n, bmax)."""
         if isinstance(inputs, np.ndarray):
             inputs = [inputs]
         first = np.asarray(inputs[0])
         grid = tuple(first.shape[-3:-1])
         if grid != tuple(self.input_shapes[0][-3:-1]):
-            return self.resized(grid)._run_ensemble(inputs, n_members, q, batch_size, seed, return_members, score=score, who=who,
-                                                    exceed=exceed)
-        from .device import DeviceArray
+            return self.resized(grid)._run_ensemble(inputs, n_members, q, batch_size, seed, return_members, verify, who)
         inputs = [np.ascontiguousarray(a, np.float32) for a in inputs]
         n, K, nq = first.shape[0], n_members, len(q)
-        y_true = None
-        if score is not None:
-            from .ensemble_score import check_score_args
-            y_true = np.ascontiguousarray(score['y_true'], np.float32)
+        if verify is not None:
+            result_key, y_true, prepare = verify
+            y_true = np.ascontiguousarray(y_true, np.float32)
             if y_true.shape != (n,) + self.output_shape:
                 raise ValueError(f'`y_true` must have the shape of the prediction {(n,) + self.output_shape}, got {y_true.shape}')
-            scale = check_score_args(score['fair'], score['scale'], self.output_shape)
-        if exceed is not None:
-            from .ensemble_score import check_exceedance_args
-            y_true = np.ascontiguousarray(exceed['y_true'], np.float32)
-            if y_true.shape != (n,) + self.output_shape:
-                raise ValueError(f'`y_true` must have the shape of the prediction {(n,) + self.output_shape}, got {y_true.shape}')
-            thr = check_exceedance_args(exceed['thresholds'], self.output_shape)
+            make_scorer = prepare(self.output_shape)
         if self.graph.dropout_mc_count() == 0:
             import warnings
             warnings.warn(f'model {self.name} has no MC dropout layer: the {K} ensemble members are identical (build it with '
@@ -629,60 +625,50 @@ class Model:
         per = int(np.prod(self.output_shape))
         bmax = max(min(int(batch_size), n), 1)
         stride = bmax * per                                    # member stride of the stack, in elements
-        try:
-            stack = DeviceArray((K, stride))
-        except _lib.Dl4dsHipError as e:
-            raise MemoryError(f'{who}: the member stack of {K} x {bmax} outputs ({K * stride * 4 / 2**30:.2f} GiB) does '
-                              f'not fit on the device; lower batch_size ({e})') from None
-        stats = DeviceArray((4 + nq, stride))
-        scorer = dev_obs = None
-        dev_in = [DeviceArray((bmax,) + tuple(a.shape[1:])) for a in inputs]
-        in_ptrs = (ctypes.c_void_p * len(dev_in))(*[d.ptr for d in dev_in])
-        qc = (ctypes.c_float * max(nq, 1))(*q.tolist())
-        res = {k: np.empty((n,) + self.output_shape, np.float32) for k in ('mean', 'std', 'min', 'max')}
-        res['quantiles'] = np.empty((nq, n) + self.output_shape, np.float32)
-        if return_members:
-            res['members'] = np.empty((K, n) + self.output_shape, np.float32)
-        pinned = [a for a in res.values() if a.nbytes >= (1 << 22) and lib.dl4ds_host_register(a.ctypes.data, a.nbytes) == 0]
-        try:
-            if score is not None:                      # (inside the try: a refused allocation here still frees the stack)
-                from .ensemble_score import Scorer
-                dev_obs = DeviceArray((stride,))
-                scorer = Scorer(K, n, self.output_shape, q, score['fair'], seed, scale, score['return_fields'], bmax)
-            if exceed is not None:
-                from .ensemble_score import ExceedanceScorer
-                dev_obs = DeviceArray((stride,))
-                scorer = ExceedanceScorer(K, n, self.output_shape, thr, exceed['return_fields'], bmax)
-            for i in range(0, n, bmax):
-                part, b = self._prep_inputs([a[i:i + bmax] for a in inputs])
-                m = b * per
-                for d, a in zip(dev_in, part):                                 # the only upload of this batch
-                    _lib.check(lib.dl4ds_memcpy_h2d(d.ptr, a.ctypes.data, a.nbytes))
-                for k in range(K):
-                    _lib.check(lib.dl4ds_graph_forward(self.graph.h, in_ptrs, len(part), b, 0, 0, stack.ptr + k * stride * 4))
-                sp = [stats.ptr + r * stride * 4 for r in range(5)]
-                _lib.check(lib.dl4ds_ensemble_reduce(stack.ptr, K, m, stride, qc, nq, sp[0], sp[1], sp[2], sp[3],
-                                                     sp[4] if nq else None))
-                for r, key in enumerate(('mean', 'std', 'min', 'max')):
-                    _lib.check(lib.dl4ds_memcpy_d2h(res[key][i:i + b].ctypes.data, sp[r], m * 4))
-                for j in range(nq):                                            # quant[j] lies at j * m for this batch's m
-                    _lib.check(lib.dl4ds_memcpy_d2h(res['quantiles'][j, i:i + b].ctypes.data, sp[4] + j * m * 4, m * 4))
-                if scorer is not None:                                         # the stack is still resident: second read
-                    _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, y_true[i:i + b].ctypes.data, m * 4))
-                    scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
-                if return_members:
+        with Buffers() as buf:
+            try:
+                stack = buf.alloc((K, stride))
+            except _lib.Dl4dsHipError as e:
+                raise MemoryError(f'{who}: the member stack of {K} x {bmax} outputs ({K * stride * 4 / 2**30:.2f} GiB) does '
+                                  f'not fit on the device; lower batch_size ({e})') from None
+            stats = buf.alloc((4 + nq, stride))
+            dev_in = [buf.alloc((bmax,) + tuple(a.shape[1:])) for a in inputs]
+            in_ptrs = (ctypes.c_void_p * len(dev_in))(*[d.ptr for d in dev_in])
+            qc = (ctypes.c_float * max(nq, 1))(*q.tolist())
+            res = {k: np.empty((n,) + self.output_shape, np.float32) for k in ('mean', 'std', 'min', 'max')}
+            res['quantiles'] = np.empty((nq, n) + self.output_shape, np.float32)
+            if return_members:
+                res['members'] = np.empty((K, n) + self.output_shape, np.float32)
+            pinned = [a for a in res.values() if a.nbytes >= (1 << 22) and lib.dl4ds_host_register(a.ctypes.data, a.nbytes) == 0]
+            scorer = None
+            try:
+                if verify is not None:                 # (inside the try: a refusal here still unpins the result arrays)
+                    dev_obs, scorer = buf.alloc((stride,)), buf.own(make_scorer(n, bmax))
+                for i in range(0, n, bmax):
+                    part, b = self._prep_inputs([a[i:i + bmax] for a in inputs])
+                    m = b * per
+                    for d, a in zip(dev_in, part):                             # the only upload of this batch
+                        d.upload(a)
                     for k in range(K):
-                        _lib.check(lib.dl4ds_memcpy_d2h(res['members'][k, i:i + b].ctypes.data, stack.ptr + k * stride * 4, m * 4))
-            if scorer is not None:
-                res['scores' if exceed is None else 'exceedance'] = scorer.result()
-        finally:
-            for a in pinned:
-                lib.dl4ds_host_unregister(a.ctypes.data)
-            for d in (scorer, dev_obs):
-                if d is not None:
-                    d.free()
-            for d in [stack, stats] + dev_in:
-                d.free()
+                        _lib.check(lib.dl4ds_graph_forward(self.graph.h, in_ptrs, len(part), b, 0, 0, stack.ptr + k * stride * 4))
+                    sp = [stats.ptr + r * stride * 4 for r in range(5)]
+                    _lib.check(lib.dl4ds_ensemble_reduce(stack.ptr, K, m, stride, qc, nq, sp[0], sp[1], sp[2], sp[3],
+                                                         sp[4] if nq else None))
+                    for r, key in enumerate(('mean', 'std', 'min', 'max')):
+                        stats.download(res[key][i:i + b], r * stride)
+                    for j in range(nq):                                        # quant[j] lies at j * m for this batch's m
+                        stats.download(res['quantiles'][j, i:i + b], 4 * stride + j * m)
+                    if scorer is not None:                                     # the stack is still resident: second read
+                        dev_obs.upload(y_true[i:i + b])
+                        scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
+                    if return_members:
+                        for k in range(K):
+                            stack.download(res['members'][k, i:i + b], k * stride)
+                if scorer is not None:
+                    res[result_key] = scorer.result()
+            finally:
+                for a in pinned:
+                    lib.dl4ds_host_unregister(a.ctypes.data)
         return res
 
     def resized(self, grid):

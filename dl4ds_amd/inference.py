@@ -3,6 +3,9 @@ import numpy as np
 
 from . import POSTUPSAMPLING_METHODS
 from .dataloader import create_batch_hr_lr
+from .ensemble_score import check_exceedance_args, check_score_args
+from .graph import check_ensemble_args
+from .metrics import _masked_observation
 
 
 def _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation):
@@ -119,7 +122,6 @@ def predict_ensemble(trainer, array, scale, n_members, quantiles=(), seed=None, 
     float64 on one sample's shape (``scaler_slope``).  That is exact for both scalers of ``dl4ds_amd.preprocessing``, which are
     affine per cell (for an inverse transform that is not affine it would be meaningless).  ``save_path``: one ``np.savez`` of
     the dict."""
-    from .graph import check_ensemble_args
     check_ensemble_args(n_members, quantiles, seed, batch_size)         # before anything touches the device
     model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
     res = model.predict_ensemble(inputs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed,
@@ -134,8 +136,6 @@ def _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, a
                        who='verify_ensemble', model_method='Model.score_ensemble'):
     """Everything ``verify_ensemble`` / ``verify_exceedance`` can refuse from the arguments they share (no library, no device) ->
     the observation as an array with a channel axis."""
-    from .graph import check_ensemble_args
-    from .ensemble_score import check_score_args
     check_ensemble_args(n_members, quantiles, seed, batch_size)
     check_score_args(fair)
     if time_window is not None:
@@ -156,6 +156,28 @@ def _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, a
     if y_true.ndim != 4 or tuple(y_true.shape[:3]) != (array.shape[0],) + grid:
         raise ValueError(f"`y_true` must have the shape of predict's result {(array.shape[0],) + grid + ('C',)}, got {y_true.shape}")
     return y_true
+
+
+def _model_unit_observation(y_true, scaler, mask):
+    """The physical observation as the model sees it: through ``scaler.transform`` (if any), NaN kept as NaN, NaN where ``mask``
+    excludes.  The scalers' transform replaces NaN by a fill value and, built with copy=False, writes into its argument: the
+    positions that are not finite are recorded first and the transform gets a copy."""
+    obs = y_true
+    if scaler is not None:
+        bad = ~np.isfinite(np.asarray(y_true, np.float64))
+        obs = np.array(scaler.transform(np.array(y_true, copy=True)), np.float32).reshape(y_true.shape)
+        obs[bad] = np.nan
+    return _masked_observation(obs, mask)
+
+
+def _saved_and_returned(res, key, inputs, save_path, save_fname, return_lr):
+    """The end of ``verify_ensemble`` / ``verify_exceedance``: one ``np.savez`` of the statistics and of the scores ``res[key]``
+    (flattened with a ``key_`` prefix) -> ``res``, or ``(res, lr)`` with ``return_lr``."""
+    if save_path is not None and save_fname is not None:
+        flat = {k: v for k, v in res.items() if k != key}
+        flat.update({f'{key}_{k}': np.asarray(v) for k, v in res[key].items()})
+        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **flat)
+    return (res, np.asarray(inputs[0])) if return_lr else res
 
 
 def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(), seed=None, fair=False, mask=None,
@@ -182,14 +204,8 @@ def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(),
     y_true = _check_verify_args(array, scale, n_members, y_true, quantiles, seed, fair, array_in_hr, time_window, batch_size,
                                 scaler)
     model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
-    from .metrics import _masked_observation
-    obs, slope = y_true, None
+    obs, slope = _model_unit_observation(y_true, scaler, mask), None
     if scaler is not None:
-        # the scalers' transform replaces NaN by a fill value and, built with copy=False, writes into its argument: the positions
-        # that are not finite are recorded first and the transform gets a copy
-        bad = ~np.isfinite(np.asarray(y_true, np.float64))
-        obs = np.array(scaler.transform(np.array(y_true, copy=True)), np.float32).reshape(y_true.shape)
-        obs[bad] = np.nan
         try:
             slope = np.asarray(scaler_slope(scaler, y_true.shape[1:]), np.float64)
         except IndexError:
@@ -197,17 +213,12 @@ def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(),
                              'carries a mask of the full array\'s shape); that is not supported') from None
         if slope.size == int(np.prod(y_true.shape[1:])):       # (the scalers drop size-1 axes)
             slope = slope.reshape(y_true.shape[1:])
-    obs = _masked_observation(obs, mask)
     res = model.score_ensemble(inputs, obs, n_members, batch_size=batch_size, quantiles=quantiles, seed=seed, fair=fair,
                                scale=slope)
     scores = res.pop('scores')
     _finish_ensemble(res, scaler, time_window)
     res['scores'] = scores
-    if save_path is not None and save_fname is not None:
-        flat = {k: v for k, v in res.items() if k != 'scores'}
-        flat.update({'scores_' + k: np.asarray(v) for k, v in scores.items()})
-        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **flat)
-    return (res, np.asarray(inputs[0])) if return_lr else res
+    return _saved_and_returned(res, 'scores', inputs, save_path, save_fname, return_lr)
 
 
 def _model_unit_thresholds(thresholds, scaler, sample_shape):
@@ -254,32 +265,21 @@ def verify_exceedance(trainer, array, scale, n_members, thresholds, y_true=None,
 
     Out of scope: recurrent models.  ``time_window is not None`` raises ValueError, because how the scores of overlapping windows
     flatten to spatial samples is not defined yet."""
-    from .ensemble_score import check_exceedance_args
     y_true = _check_verify_args(array, scale, n_members, y_true, (), seed, False, array_in_hr, time_window, batch_size, scaler,
                                 who='verify_exceedance', model_method='Model.score_exceedance')
     thr = check_exceedance_args(thresholds, y_true.shape[1:])
     model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
-    from .metrics import _masked_observation
-    obs, excluded = y_true, 0
+    obs, excluded = _model_unit_observation(y_true, scaler, mask), 0
     if scaler is not None:
-        # (as in verify_ensemble: the transform fills NaN and may write into its argument)
-        bad = ~np.isfinite(np.asarray(y_true, np.float64))
-        obs = np.array(scaler.transform(np.array(y_true, copy=True)), np.float32).reshape(y_true.shape)
-        obs[bad] = np.nan
         # (the caller's float64 values are transformed, not their float32 roundings)
         physical = np.asarray(getattr(thresholds, 'values', thresholds), np.float64).reshape(thr.shape)
         thr, excluded = _model_unit_thresholds(physical, scaler, y_true.shape[1:])
-    obs = _masked_observation(obs, mask)
     res = model.score_exceedance(inputs, obs, n_members, thr, batch_size=batch_size, seed=seed)
     scores = res.pop('exceedance')
     scores['n_cells_excluded'] = excluded
     _finish_ensemble(res, scaler, time_window)
     res['exceedance'] = scores
-    if save_path is not None and save_fname is not None:
-        flat = {k: v for k, v in res.items() if k != 'exceedance'}
-        flat.update({'exceedance_' + k: np.asarray(v) for k, v in scores.items()})
-        np.savez(save_path + ('' if save_path.endswith('/') else '/') + save_fname, **flat)
-    return (res, np.asarray(inputs[0])) if return_lr else res
+    return _saved_and_returned(res, 'exceedance', inputs, save_path, save_fname, return_lr)
 
 
 class Predictor:

@@ -12,9 +12,12 @@ import math
 
 import numpy as np
 
-from . import _lib
+from . import _exact, _lib
+from ._chunks import check_batch_size, host_ensemble, paired_chunks
 from .device import DeviceArray
 from .dataloader import checkarray_ndim
+from .ensemble_score import ExceedanceScorer, Scorer, check_exceedance_args, check_score_args
+from .graph import check_ensemble_args
 
 
 def _upload(y_test, y_test_hat):
@@ -206,14 +209,16 @@ def _prepared(y_test, y_test_hat, scaler, mask, check):
     return _masked_observation(y_test, mask), y_test_hat, checked
 
 
-def _check_batch_size(batch_size):
-    if batch_size is not None and (int(batch_size) != batch_size or int(batch_size) < 1):
-        raise ValueError(f'`batch_size` must be a positive integer, got {batch_size!r}')
-
-
-def _upload_batch(batch_size, per, count):
-    """Units per upload out of `count`, `per` floats each: ``batch_size``, by default chunks of at most 256 MiB per array."""
-    return max(min(int(max(1, (1 << 26) // per) if batch_size is None else batch_size), count), 1)
+def _host_ensemble_args(y_true, members, quantiles, seed, batch_size):
+    """What `ensemble_scores` and `exceedance_scores` check alike -> (members, K, quantiles as float32, y_true), all arrays."""
+    members = np.asarray(members)
+    if members.ndim < 2:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape, got {members.shape}')
+    K, q = check_ensemble_args(int(members.shape[0]), quantiles, seed, batch_size)
+    y_true = np.asarray(getattr(y_true, 'values', y_true))
+    if y_true.ndim < 1 or members.shape[1:] != y_true.shape:
+        raise ValueError(f'`members` must be shaped (K,) + y_true.shape = (K,) + {y_true.shape}, got {members.shape}')
+    return members, K, q, y_true
 
 
 def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None, batch_size=None, scale=None,
@@ -226,37 +231,11 @@ def ensemble_scores(y_true, members, quantiles=(), fair=False, seed=0, mask=None
     does not depend on ``batch_size``.  ``mask``: 2-D or with a channel axis, 0 = excluded (NaN is written into the observation;
     elements next to a non-finite value are excluded anyway).  The folds run one lane per cell and walk a chunk's samples in
     turn: made for fields; samples of very few cells (a 1-D ``y_true`` has one) are slow.  ``scale``: a positive factor per cell, see ``Model.score_ensemble``."""
-    from .graph import check_ensemble_args
-    from .ensemble_score import Scorer, check_score_args
-    members = np.asarray(members)
-    if members.ndim < 2:
-        raise ValueError(f'`members` must be shaped (K,) + y_true.shape, got {members.shape}')
-    K, q = check_ensemble_args(int(members.shape[0]), quantiles, seed, batch_size)
-    y_true = np.asarray(getattr(y_true, 'values', y_true))
-    if y_true.ndim < 1 or members.shape[1:] != y_true.shape:
-        raise ValueError(f'`members` must be shaped (K,) + y_true.shape = (K,) + {y_true.shape}, got {members.shape}')
+    members, K, q, y_true = _host_ensemble_args(y_true, members, quantiles, seed, batch_size)
     N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
     scale = check_score_args(fair, scale, sample_shape)
-    obs = _masked_observation(y_true, mask)
-    per = int(np.prod(sample_shape, dtype=np.int64))
-    bmax = _upload_batch(batch_size, max(K * per, 1), N)
-    stride = bmax * per
-    scorer = Scorer(K, N, sample_shape, q, fair, seed, scale, return_fields, bmax)
-    stack, dev_obs = DeviceArray((K, stride)), DeviceArray((stride,))
-    lib = _lib.lib()
-    try:
-        for i in range(0, N, bmax):
-            b = min(bmax, N - i)
-            for k in range(K):
-                part = np.ascontiguousarray(members[k, i:i + b], np.float32)
-                _lib.check(lib.dl4ds_memcpy_h2d(stack.ptr + k * stride * 4, part.ctypes.data, part.nbytes))
-            _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, obs[i:i + b].ctypes.data, b * per * 4))
-            scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
-        return scorer.result()
-    finally:
-        scorer.free()
-        stack.free()
-        dev_obs.free()
+    return host_ensemble(_masked_observation(y_true, mask), members, batch_size=batch_size,
+                         make_scorer=lambda bmax: Scorer(K, N, sample_shape, q, fair, seed, scale, return_fields, bmax))
 
 
 def exceedance_scores(y_true, members, thresholds, mask=None, batch_size=None, return_fields=False):
@@ -286,37 +265,11 @@ def exceedance_scores(y_true, members, thresholds, mask=None, batch_size=None, r
 
     Every ratio is a quotient of integers rounded to float64 once (Python integers, or one IEEE division where both operands are
     below 2^53), NaN on a zero denominator."""
-    from .graph import check_ensemble_args
-    from .ensemble_score import ExceedanceScorer, check_exceedance_args
-    members = np.asarray(members)
-    if members.ndim < 2:
-        raise ValueError(f'`members` must be shaped (K,) + y_true.shape, got {members.shape}')
-    K, _ = check_ensemble_args(int(members.shape[0]), (), None, batch_size)
-    y_true = np.asarray(getattr(y_true, 'values', y_true))
-    if y_true.ndim < 1 or members.shape[1:] != y_true.shape:
-        raise ValueError(f'`members` must be shaped (K,) + y_true.shape = (K,) + {y_true.shape}, got {members.shape}')
+    members, K, _, y_true = _host_ensemble_args(y_true, members, (), None, batch_size)
     N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
     thr = check_exceedance_args(thresholds, sample_shape)
-    obs = _masked_observation(y_true, mask)
-    per = int(np.prod(sample_shape, dtype=np.int64))
-    bmax = _upload_batch(batch_size, max(K * per, 1), N)
-    stride = bmax * per
-    scorer = ExceedanceScorer(K, N, sample_shape, thr, return_fields, bmax)
-    stack, dev_obs = DeviceArray((K, stride)), DeviceArray((stride,))
-    lib = _lib.lib()
-    try:
-        for i in range(0, N, bmax):
-            b = min(bmax, N - i)
-            for k in range(K):
-                part = np.ascontiguousarray(members[k, i:i + b], np.float32)
-                _lib.check(lib.dl4ds_memcpy_h2d(stack.ptr + k * stride * 4, part.ctypes.data, part.nbytes))
-            _lib.check(lib.dl4ds_memcpy_h2d(dev_obs.ptr, obs[i:i + b].ctypes.data, b * per * 4))
-            scorer.score(stack.ptr, stride, dev_obs.ptr, i, b)
-        return scorer.result()
-    finally:
-        scorer.free()
-        stack.free()
-        dev_obs.free()
+    return host_ensemble(_masked_observation(y_true, mask), members, batch_size=batch_size,
+                         make_scorer=lambda bmax: ExceedanceScorer(K, N, sample_shape, thr, return_fields, bmax))
 
 
 FSS_DEFAULT_WINDOWS = (1, 3, 5, 9, 17, 33, 65)
@@ -329,15 +282,7 @@ def check_neighbourhood_args(shape, thresholds, windows, batch_size=None):
     if len(shape) != 4 or min(shape) < 1:
         raise ValueError(f'expected non-empty (N, H, W, C) arrays, got shape {tuple(shape)}')
     _, h, w, _ = (int(v) for v in shape)
-    t64 = np.atleast_1d(np.asarray(thresholds, np.float64))
-    if t64.ndim != 1 or t64.size == 0:
-        raise ValueError('`thresholds` must be a non-empty 1-D sequence')
-    with np.errstate(over='ignore'):
-        thr = t64.astype(np.float32)
-    if not np.isfinite(t64).all() or not np.isfinite(thr).all():
-        raise ValueError('`thresholds` must be finite (as float32)')
-    if not (np.diff(thr) > 0).all():
-        raise ValueError('`thresholds` must be strictly increasing as float32 values')
+    thr = _exact.finite_float32(np.atleast_1d(np.asarray(thresholds, np.float64)), '`thresholds`', increasing=True)
     win = np.atleast_1d(np.asarray(windows))
     if win.ndim != 1 or win.size == 0:
         raise ValueError('`windows` must be a non-empty 1-D sequence')
@@ -355,31 +300,20 @@ def check_neighbourhood_args(shape, thresholds, windows, batch_size=None):
         if h * w * m * m >= FSS_SUM_BOUND:
             raise ValueError(f'window {n} on a {h} x {w} field: H*W*m^2 = {h * w * m * m} with m = min(n, H)*min(n, W) = {m} '
                              'must stay below 2^62 for the exact 64-bit sums')
-    _check_batch_size(batch_size)
+    check_batch_size(batch_size)
     return thr, np.asarray(wl, np.int32)
-
-
-def _ratio(num, den):
-    """num / den in fp64, NaN where den == 0 (arrays of integers, or Python integers)."""
-    num, den = np.asarray(num, np.float64), np.asarray(den, np.float64)
-    with np.errstate(divide='ignore', invalid='ignore'):
-        return np.where(den == 0, np.nan, num / np.where(den == 0, 1.0, den))
 
 
 def _contingency_scores(hits, misses, fa, nvalid):
     """POD, FAR, CSI, ETS, frequency bias from integer counts (int64 arrays, or object arrays of Python integers)."""
     to = lambda a: np.asarray(a, np.float64)
     obs, fc = hits + misses, hits + fa
-    hr = _ratio(to(obs) * to(fc), nvalid)                              # hits expected by chance
+    hr = _exact.ratio(to(obs) * to(fc), nvalid)                              # hits expected by chance
     ets_den = to(hits + misses + fa) - hr
     with np.errstate(invalid='ignore'):
         ets = np.where(np.isnan(hr) | (ets_den == 0), np.nan, (to(hits) - hr) / np.where(ets_den == 0, 1.0, ets_den))
-    return dict(pod=_ratio(hits, obs), far=_ratio(fa, fc), csi=_ratio(hits, hits + misses + fa), ets=ets, bias=_ratio(fc, obs))
-
-
-def _pysum(a, axis):
-    """Sum of an int64 array over `axis` as Python integers (object array): cannot overflow."""
-    return np.sum(a.astype(object), axis=axis)
+    ratio = _exact.ratio
+    return dict(pod=ratio(hits, obs), far=ratio(fa, fc), csi=ratio(hits, hits + misses + fa), ets=ets, bias=ratio(fc, obs))
 
 
 def neighbourhood_scores(y_test, y_test_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=None, batch_size=None):
@@ -406,27 +340,14 @@ def neighbourhood_scores(y_test, y_test_hat, thresholds, windows=FSS_DEFAULT_WIN
                                             lambda shape: check_neighbourhood_args(shape, thresholds, windows, batch_size))
     N, H, W, C = obs.shape
     T, S = len(thr), len(win)
-    per = H * W * C
-    bmax = _upload_batch(batch_size, per, N)
     sums = np.empty((N, C, T, S, 3), np.int64)
     cont = np.empty((N, C, T, 4), np.int64)
     nvalid = np.empty((N, C), np.int64)
     lib = _lib.lib()
-    dy, dp = DeviceArray((bmax * per,)), DeviceArray((bmax * per,))
-    dsums, dcont, dvalid = (DeviceArray((bmax,) + a.shape[1:], np.int64) for a in (sums, cont, nvalid))
-    try:
-        for i in range(0, N, bmax):
-            b = min(bmax, N - i)
-            part = np.ascontiguousarray(y_test_hat[i:i + b], np.float32)
-            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, obs[i:i + b].ctypes.data, b * per * 4))
-            _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part.ctypes.data, b * per * 4))
-            _lib.check(lib.dl4ds_fss(dy.ptr, dp.ptr, b, H, W, C, thr.ctypes.data, T, win.ctypes.data, S, dsums.ptr, dcont.ptr,
-                                     dvalid.ptr))
-            for host, dev in ((sums, dsums), (cont, dcont), (nvalid, dvalid)):
-                _lib.check(lib.dl4ds_memcpy_d2h(host[i:i + b].ctypes.data, dev.ptr, host[i:i + b].nbytes))
-    finally:
-        for d in (dy, dp, dsums, dcont, dvalid):
-            d.free()
+
+    def call(b, dy, dp, dsums, dcont, dvalid):
+        _lib.check(lib.dl4ds_fss(dy, dp, b, H, W, C, thr.ctypes.data, T, win.ctypes.data, S, dsums, dcont, dvalid))
+    paired_chunks(obs, y_test_hat, (sums, cont, nvalid), call, batch_size)
     return scores_from_counts(sums, cont, nvalid, thr, win)
 
 
@@ -434,34 +355,24 @@ def scores_from_counts(sums, cont, nvalid, thresholds, windows):
     """The result dict of `neighbourhood_scores` from the integer outputs of `dl4ds_fss` (host arithmetic only)."""
     sums, cont, nvalid = np.asarray(sums, np.int64), np.asarray(cont, np.int64), np.asarray(nvalid, np.int64)
     D, FO = sums[..., 0], sums[..., 1] + sums[..., 2]                  # F + O < 2^63 by the overflow rule
-    res = dict(sums=sums, fss=1.0 - _ratio(D, FO), n_valid=nvalid, thresholds=np.asarray(thresholds, np.float32),
+    res = dict(sums=sums, fss=1.0 - _exact.ratio(D, FO), n_valid=nvalid, thresholds=np.asarray(thresholds, np.float32),
                windows=np.asarray(windows, np.int64))
     so = sums.astype(object)
-    res['fss_pooled'] = 1.0 - _ratio_exact(np.sum(so[..., 0], axis=(0, 1)), np.sum(so[..., 1] + so[..., 2], axis=(0, 1)))
-    res['fss_pooled_per_channel'] = 1.0 - _ratio_exact(np.sum(so[..., 0], axis=0), np.sum(so[..., 1] + so[..., 2], axis=0))
+    res['fss_pooled'] = 1.0 - _exact.ratio_exact(np.sum(so[..., 0], axis=(0, 1)), np.sum(so[..., 1] + so[..., 2], axis=(0, 1)))
+    res['fss_pooled_per_channel'] = 1.0 - _exact.ratio_exact(np.sum(so[..., 0], axis=0), np.sum(so[..., 1] + so[..., 2], axis=0))
     hits, misses, fa, cn = (cont[..., k] for k in range(4))
     res.update(hits=hits, misses=misses, false_alarms=fa, correct_negatives=cn)
     res.update(_contingency_scores(hits, misses, fa, nvalid[..., None]))
-    ph, pm, pf = (_pysum(a, (0, 1)) for a in (hits, misses, fa))
-    pn = int(_pysum(nvalid, (0, 1)))
+    ph, pm, pf = (_exact.pysum(a, (0, 1)) for a in (hits, misses, fa))
+    pn = int(_exact.pysum(nvalid, (0, 1)))
     for k, v in _contingency_scores(ph, pm, pf, np.full(ph.shape, pn, object)).items():
         res[k + '_pooled'] = v
-    base = _ratio_exact(ph + pm, np.full(ph.shape, pn, object))
+    base = _exact.ratio_exact(ph + pm, np.full(ph.shape, pn, object))
     res.update(base_rate=base, fss_random=base.copy(), fss_useful=0.5 + base / 2.0)
     with np.errstate(invalid='ignore'):
         reach = res['fss_pooled'] >= res['fss_useful'][:, None]       # NaN compares false
     res['useful_window'] = np.where(reach.any(1), res['windows'][np.argmax(reach, 1)], -1).astype(np.int64)
     return res
-
-
-def _ratio_exact(num, den):
-    """Element-wise num / den of object arrays of Python integers, each quotient correctly rounded to fp64; NaN where den == 0."""
-    num, den = np.asarray(num, object), np.asarray(den, object)
-    out = np.full(num.shape, np.nan)
-    for idx in np.ndindex(num.shape):
-        if den[idx] != 0:
-            out[idx] = int(num[idx]) / int(den[idx])
-    return out
 
 
 def fss(y, y_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=None, batch_size=None):
@@ -496,18 +407,10 @@ def check_distribution_args(shape, quantiles, bins=None, over='time', batch_size
         raise ValueError('`quantiles` must lie in [0, 1]')
     edges = None
     if bins is not None:
-        b64 = np.asarray(bins, np.float64)
-        if b64.ndim != 1 or b64.size < 2:
-            raise ValueError('`bins` must be a 1-D sequence of at least two bin edges')
-        if b64.size > DIST_MAX_EDGES:
-            raise ValueError(f'at most {DIST_MAX_EDGES} bin edges are supported, got {b64.size}')
-        with np.errstate(over='ignore'):
-            edges = b64.astype(np.float32)
-        if not np.isfinite(b64).all() or not np.isfinite(edges).all():
-            raise ValueError('`bins` must be finite (as float32)')
-        if not (np.diff(edges) > 0).all():
-            raise ValueError('`bins` must be strictly increasing as float32 values')
-    _check_batch_size(batch_size)
+        edges = _exact.finite_float32(bins, '`bins` (the bin edges)', least=2, increasing=True)
+        if edges.size > DIST_MAX_EDGES:
+            raise ValueError(f'at most {DIST_MAX_EDGES} bin edges are supported, got {edges.size}')
+    check_batch_size(batch_size)
     return np.ascontiguousarray(q), edges
 
 
@@ -517,18 +420,18 @@ def distribution_from_counts(quant, w1, ks_count, hist, nvalid, quantiles, bins)
     quant, nvalid = np.asarray(quant, np.float64), np.asarray(nvalid, np.int64)
     ks_count = np.asarray(ks_count, np.int64)
     res = dict(n_valid=nvalid, q_obs=quant[..., 0, :], q_pred=quant[..., 1, :], q_bias=quant[..., 1, :] - quant[..., 0, :],
-               wasserstein=np.asarray(w1, np.float64), ks_count=ks_count, ks=_ratio(ks_count, nvalid),
+               wasserstein=np.asarray(w1, np.float64), ks_count=ks_count, ks=_exact.ratio(ks_count, nvalid),
                quantiles=np.asarray(quantiles, np.float64), bins=None)
     if hist is not None:
         hist = np.asarray(hist, np.int64)
         ho, hp = hist[..., 0, :], hist[..., 1, :]
         lead = tuple(range(nvalid.ndim))
-        po, pp = np.atleast_1d(_pysum(ho, lead)), np.atleast_1d(_pysum(hp, lead))
+        po, pp = np.atleast_1d(_exact.pysum(ho, lead)), np.atleast_1d(_exact.pysum(hp, lead))
         common = sum(min(int(a), int(b)) for a, b in zip(po, pp))
         total = sum(int(v) for v in nvalid.ravel())
-        res.update(hist_obs=ho, hist_pred=hp, perkins=_ratio(np.minimum(ho, hp).sum(-1), nvalid),
+        res.update(hist_obs=ho, hist_pred=hp, perkins=_exact.ratio(np.minimum(ho, hp).sum(-1), nvalid),
                    hist_obs_pooled=po.astype(np.int64), hist_pred_pooled=pp.astype(np.int64),
-                   perkins_pooled=_ratio_exact(common, total)[()], bins=np.asarray(bins, np.float32))
+                   perkins_pooled=_exact.ratio_exact(common, total)[()], bins=np.asarray(bins, np.float32))
     return res
 
 
@@ -555,47 +458,21 @@ def distribution_scores(y_test, y_test_hat, quantiles=DIST_DEFAULT_QUANTILES, bi
     N, H, W, C = obs.shape
     Q, E = len(q), 0 if edges is None else len(edges)
     if over == 'time':
-        lead, units, unit = (H, W, C), H, W * C                            # uploaded in bands of rows: `unit` segments per row
-        per_unit = N * W * C
+        lead, axis, segs = (H, W, C), 1, H * W * C                         # uploaded in bands of rows: W * C segments per row
     else:
-        lead, units, unit = (N,), N, 1                                     # uploaded in blocks of samples: one segment each
-        per_unit = H * W * C
-    bmax = _upload_batch(batch_size, per_unit, units)
-    segs = units * unit
+        lead, axis, segs = (N,), 0, N                                      # uploaded in blocks of samples: one segment each
     quant = np.empty((segs, 2, Q), np.float64)
     w1 = np.empty((segs,), np.float64)
     ks, nvalid = np.empty((segs,), np.int64), np.empty((segs,), np.int64)
     hist = np.empty((segs, 2, E - 1), np.int64) if E else None
     lib = _lib.lib()
-    dy, dp = DeviceArray((bmax * per_unit,)), DeviceArray((bmax * per_unit,))
-    dquant, dw1 = DeviceArray((bmax * unit, 2, max(Q, 1)), np.float64), DeviceArray((bmax * unit,), np.float64)
-    dks, dvalid = DeviceArray((bmax * unit,), np.int64), DeviceArray((bmax * unit,), np.int64)
-    dhist = DeviceArray((bmax * unit, 2, E - 1), np.int64) if E else None
-    try:
-        for i in range(0, units, bmax):
-            b = min(bmax, units - i)
-            if over == 'time':
-                part_y = np.ascontiguousarray(obs[:, i:i + b])
-                part_p = np.ascontiguousarray(y_test_hat[:, i:i + b], np.float32)
-                s, length, seg_stride, elem_stride = b * unit, N, 1, b * unit
-            else:
-                part_y = obs[i:i + b]
-                part_p = np.ascontiguousarray(y_test_hat[i:i + b], np.float32)
-                s, length, seg_stride, elem_stride = b, per_unit, per_unit, 1
-            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, part_y.ctypes.data, part_y.nbytes))
-            _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part_p.ctypes.data, part_p.nbytes))
-            _lib.check(lib.dl4ds_distribution(dy.ptr, dp.ptr, s, length, seg_stride, elem_stride, q.ctypes.data, Q,
-                                              edges.ctypes.data if E else None, E, dquant.ptr, dw1.ptr, dks.ptr,
-                                              dhist.ptr if E else None, dvalid.ptr))
-            s0 = i * unit
-            outs = [(quant, dquant), (w1, dw1), (ks, dks), (nvalid, dvalid)] + ([(hist, dhist)] if E else [])
-            for host, dev in outs:
-                if host[s0:s0 + s].nbytes:
-                    _lib.check(lib.dl4ds_memcpy_d2h(host[s0:s0 + s].ctypes.data, dev.ptr, host[s0:s0 + s].nbytes))
-    finally:
-        for d in (dy, dp, dquant, dw1, dks, dvalid, dhist):
-            if d is not None:
-                d.free()
+
+    def call(b, dy, dp, dquant, dw1, dks, dvalid, dhist=None):
+        s = b * W * C if over == 'time' else b                             # segments of the chunk
+        length, seg_stride, elem_stride = (N, 1, s) if over == 'time' else (H * W * C, H * W * C, 1)
+        _lib.check(lib.dl4ds_distribution(dy, dp, s, length, seg_stride, elem_stride, q.ctypes.data, Q,
+                                          edges.ctypes.data if E else None, E, dquant, dw1, dks, dhist, dvalid))
+    paired_chunks(obs, y_test_hat, (quant, w1, ks, nvalid) + ((hist,) if E else ()), call, batch_size, axis)
     return distribution_from_counts(quant.reshape(lead + (2, Q)), w1.reshape(lead), ks.reshape(lead),
                                     None if hist is None else hist.reshape(lead + (2, E - 1)), nvalid.reshape(lead), q, edges)
 
@@ -646,7 +523,7 @@ def check_spectral_args(shape, bins='radial', detrend='mean', window=None, spaci
     for name, v in (('spacing', spacing), ('ratio_floor', ratio_floor)):
         if isinstance(v, (bool, str)) or not np.isscalar(v) or not np.isfinite(v) or not v > 0:
             raise ValueError(f'`{name}` must be a positive finite number, got {v!r}')
-    _check_batch_size(batch_size)
+    check_batch_size(batch_size)
     if isinstance(bins, str):
         if bins != 'radial':
             raise ValueError(f"`bins` must be 'radial' or an integer (H, W) map, got {bins!r}")
@@ -687,7 +564,7 @@ def _lsd(ratio, usable):
 
 def _spectral_ratios(po, pp, cr, ci, count):
     """(psd_ratio, coherence, bins usable for the log-spectral distance) of power and cross spectra over the last axis."""
-    ratio, coh = _ratio(pp, po), _ratio(cr * cr + ci * ci, po * pp)
+    ratio, coh = _exact.ratio(pp, po), _exact.ratio(cr * cr + ci * ci, po * pp)
     usable = (np.arange(po.shape[-1]) >= 1) & (count > 0) & (po > 0) & (pp > 0)
     return ratio, coh, usable
 
@@ -710,8 +587,8 @@ def spectra_from_sums(power, nvalid, mean, count, hw, spacing=1.0, ratio_floor=0
     ratio, coh, usable = _spectral_ratios(po, pp, cr, ci, count)
     blank = lambda a: np.where(empty[(...,) + (None,) * (a.ndim - 2)], np.nan, a)     # every score of an empty field is NaN
     res = dict(wavenumber=wavenumber, wavelength=wavelength, count=count, n_valid=nvalid, mean_obs=mean[..., 0],
-               mean_pred=mean[..., 1], power_obs=po, power_pred=pp, psd_obs=blank(_ratio(po, count)),
-               psd_pred=blank(_ratio(pp, count)), cross=cross, coherence=blank(coh), psd_ratio=blank(ratio),
+               mean_pred=mean[..., 1], power_obs=po, power_pred=pp, psd_obs=blank(_exact.ratio(po, count)),
+               psd_pred=blank(_exact.ratio(pp, count)), cross=cross, coherence=blank(coh), psd_ratio=blank(ratio),
                lsd=blank(_lsd(ratio, usable)))
     keep = ~empty
     pool = [_fsum_axis0(a, keep) for a in (po, pp, cr, ci)]
@@ -737,28 +614,12 @@ def _device_spectra(obs, pred, full, B, detrend, window, batch_size):
     (N, C), mean (N, C, 2))."""
     N, H, W, C = obs.shape
     half = np.ascontiguousarray(full[:, :W // 2 + 1], np.int32)
-    per = H * W * C
-    bmax = _upload_batch(batch_size, per, N)
     power, nvalid, mean = np.empty((N, C, 4, B), np.float64), np.empty((N, C), np.int64), np.empty((N, C, 2), np.float64)
     lib = _lib.lib()
-    dy = DeviceArray((bmax * per,))
-    dp = DeviceArray((bmax * per,)) if pred is not None else None
-    dpower, dvalid, dmean = (DeviceArray((bmax,) + a.shape[1:], a.dtype) for a in (power, nvalid, mean))
-    try:
-        for i in range(0, N, bmax):
-            b = min(bmax, N - i)
-            _lib.check(lib.dl4ds_memcpy_h2d(dy.ptr, obs[i:i + b].ctypes.data, b * per * 4))
-            if dp is not None:
-                part = np.ascontiguousarray(pred[i:i + b], np.float32)
-                _lib.check(lib.dl4ds_memcpy_h2d(dp.ptr, part.ctypes.data, b * per * 4))
-            _lib.check(lib.dl4ds_spectrum(dy.ptr, dp.ptr if dp is not None else None, b, H, W, C, detrend, window, half.ctypes.data,
-                                          B, dpower.ptr, dvalid.ptr, dmean.ptr))
-            for host, dev in ((power, dpower), (nvalid, dvalid), (mean, dmean)):
-                _lib.check(lib.dl4ds_memcpy_d2h(host[i:i + b].ctypes.data, dev.ptr, host[i:i + b].nbytes))
-    finally:
-        for d in (dy, dp, dpower, dvalid, dmean):
-            if d is not None:
-                d.free()
+
+    def call(b, dy, dp, dpower, dvalid, dmean):
+        _lib.check(lib.dl4ds_spectrum(dy, dp, b, H, W, C, detrend, window, half.ctypes.data, B, dpower, dvalid, dmean))
+    paired_chunks(obs, pred, (power, nvalid, mean), call, batch_size)
     return power, nvalid, mean
 
 
