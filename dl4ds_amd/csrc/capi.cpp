@@ -614,6 +614,19 @@ int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, siz
                  valid_dev, ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_quantile_table(const float* x_dev, size_t N, size_t per, const double* q_host, int Q, float* table_dev,
+                         long long* valid_dev) {
+    API_BEGIN
+    const size_t ws = quantile_table_workspace_bytes(N, per);                        // (refuses sizes the entry does not take)
+    quantile_table(S(), x_dev, N, per, q_host, Q, table_dev, valid_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, const float* model_tab_dev, const float* obs_tab_dev,
+                     const float* target_tab_dev, int Q, int kind, int keep_unfitted, unsigned long long* counts_dev) {
+    API_BEGIN
+    qmap_apply(S(), x_dev, out_dev, B, per, model_tab_dev, obs_tab_dev, target_tab_dev, Q, kind, keep_unfitted, counts_dev);
+    API_END
+}
 int dl4ds_spectrum(const float* y_dev, const float* p_dev, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
                    int B, double* power_dev, long long* valid_dev, double* mean_dev) {
     API_BEGIN

@@ -34,11 +34,11 @@
 namespace {
 
 constexpr int DS_LDS_MAX = 8192;                       // longest segment whose two sides one workgroup sorts in LDS (64 KiB of keys)
-constexpr int DS_STRIDED_MAX = 512;                    // longest segment of the strided LDS engine (16 segments of pitch 513)
+constexpr int DS_STRIDED_MAX = SORT_STRIDED_MAX;       // longest segment of the strided LDS engine (16 segments of pitch 513)
 constexpr int DS_ROW = 16;                             // fewest segments per strided workgroup: rows of 64 contiguous bytes
 constexpr size_t DS_LDS_BUDGET = size_t(72) << 10;     // LDS of a workgroup, keys + reduction buffers: two workgroups per 160 KiB CU
 constexpr int DS_MAX_Q = 64, DS_MAX_E = 257;           // (the C header states both)
-constexpr uint32_t DS_INVALID = 0xFFFFFFFFu;           // key of an invalid element and of the padding
+constexpr uint32_t DS_INVALID = SORT_INVALID;          // key of an invalid element and of the padding
 constexpr int DS_TR = 64;                              // gather kernel: 64 segments x 64 elements per transposed tile
 
 struct DistParams {
@@ -54,8 +54,6 @@ struct DistOut {
     long long* hist;
     long long* valid;
 };
-
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
 
 __device__ __forceinline__ void make_keys(float yv, float pv, uint32_t& a, uint32_t& b) {
     const bool ok = finite_bits(yv) && finite_bits(pv);
@@ -73,16 +71,6 @@ __device__ __forceinline__ void position_terms(P ka, P kb, uint32_t n, uint32_t 
     if (a == b) return;                                // v = a[j] = b[j]: the run that ends later decides, at its own end
     if (j + 1 == n || ka[j + 1] != a) ks = max(ks, absdiff(j + 1, bound<false>(kb, n, a)));
     if (j + 1 == n || kb[j + 1] != b) ks = max(ks, absdiff(j + 1, bound<false>(ka, n, b)));
-}
-
-template <typename P>
-__device__ __forceinline__ double quantile_of(P k, uint32_t n, double q) {
-#pragma clang fp contract(off)                         // h - floor(h) and the interpolation as written: every product is rounded
-    if (n == 0) return __builtin_nan("");
-    const double h = q * (double)(n - 1), fl = floor(h), g = h - fl;
-    const uint32_t j = (uint32_t)fl;
-    const double x0 = (double)key_value(k[j]), x1 = (double)key_value(k[min(j + 1, n - 1)]);
-    return x0 + (x1 - x0) * g;
 }
 
 // quantiles and histogram of one segment by the R threads r = 0 .. R-1 that share it

@@ -185,6 +185,17 @@ void distribution_check_args(size_t S, size_t L, const double* q, int Q, const f
 void distribution(hipStream_t s, const float* y, const float* p, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
                   const double* q, int Q, const float* edges, int E, double* quant, double* w1, long long* ks, long long* hist,
                   long long* valid, void* workspace, size_t workspace_bytes);
+// Quantile-mapping bias correction (qmap.hip).  quantile_table: per cell c < per the Q 'linear' sample quantiles
+// of the finite values among x[n*per + c], n < N, rounded to fp32 into table [Q][per], and their number into valid [per] (may be
+// null); q is a host array.  qmap_apply: B samples of per cells through the tables of the model's history, the observation and
+// (QDM; null: EQM) the period being corrected; kind 0 additive, 1 multiplicative; counts [4] (nonfinite, unfitted, below, above;
+// may be null) are added to; out may be x.  quantile_table_workspace_bytes throws on an empty array or N >= 2^31 (before anything
+// is sized); quantile_table checks the probabilities, once.
+size_t quantile_table_workspace_bytes(size_t N, size_t per);
+void quantile_table(hipStream_t s, const float* x, size_t N, size_t per, const double* q, int Q, float* table, long long* valid,
+                    void* workspace, size_t workspace_bytes);
+void qmap_apply(hipStream_t s, const float* x, float* out, size_t B, size_t per, const float* model_tab, const float* obs_tab,
+                const float* target_tab, int Q, int kind, int keep_unfitted, unsigned long long* counts);
 // Spectral verification (spectrum.hip) of the N*C fields of y, p (N, H, W, C; p may be null): the unnormalised 2-D DFT of either
 // side in fp64 (kept cells, optional detrending and periodic Hann window), folded over the bins of the HOST map bin [H][W/2 + 1]
 // (values in [-1, B)) into power [N][C][4][B]; valid [N][C] kept cells, mean [N][C][2] the subtracted means.  Outputs are

@@ -4,7 +4,9 @@
 //  * in LDS: one bitonic network over independent rows of keys, with or without an index payload;
 //  * in global memory: a stable 8-bit LSD radix sort, four passes of (per-tile digit histogram, scan per segment, stable
 //    scatter) ping-ponged between two buffers, the first pass reading either keys or the floats themselves;
-//  * a fixed-order reduction tree, and the chunk planner and workspace carving of the clients' global engines.
+//  * a fixed-order reduction tree, and the chunk planner and workspace carving of the clients' global engines;
+//  * what distribution.hip and qmap.hip share on top: the key of an invalid element, the longest segment of the strided LDS
+//    engine, and the 'linear' sample quantile read from sorted keys.
 // Chunk-local layout of the global engine: segment i of a chunk owns elements [i*L, (i+1)*L) of every per-element buffer and tiles
 // [i*ntiles, (i+1)*ntiles) of every per-tile buffer; every per-tile kernel runs with blockIdx.x = i*ntiles + tile (TileGrid).
 #pragma once
@@ -21,6 +23,8 @@ constexpr int SORT_WAVES = SORT_THREADS / 64;
 constexpr int SORT_WAVE_SPAN = SORT_TILE / SORT_WAVES; // 1024 consecutive elements per wave, 16 chunks of 64
 constexpr size_t SORT_WS_BUDGET = size_t(128) << 20;   // workspace of a global engine (one chunk of segments)
 constexpr size_t SORT_MAX_GRID = size_t(1) << 30;      // most (segment, tile) workgroups of one launch
+constexpr uint32_t SORT_INVALID = 0xFFFFFFFFu;         // key of an invalid element and of the padding: no finite float has it, sorts last
+constexpr int SORT_STRIDED_MAX = 512;                  // longest segment of the strided (seg_stride == 1) LDS engines
 
 // The grid convention of every per-tile kernel: blockIdx.x = segment*ntiles + tile.  A workgroup splits its index without a
 // division: magic = floor((2^64 - 1) / ntiles) + 1 = (2^64 + e) / ntiles with 0 <= e <= ntiles, so the high half of b*magic is
@@ -48,6 +52,8 @@ __device__ __forceinline__ float key_value(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
+__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
+
 // first position in sorted k[0, n) whose key is >= x (LB) or > x (!LB)
 template <bool LB, typename P>
 __device__ __forceinline__ uint32_t bound(P k, uint32_t n, uint32_t x) {
@@ -58,6 +64,17 @@ __device__ __forceinline__ uint32_t bound(P k, uint32_t n, uint32_t x) {
         if (LB ? (v < x) : (v <= x)) lo = mid + 1; else hi = mid;
     }
     return lo;
+}
+
+// numpy's 'linear' quantile q of the n ascending values behind the sorted keys k[0, n), in fp64; NaN when n == 0
+template <typename P>
+__device__ __forceinline__ double quantile_of(P k, uint32_t n, double q) {
+#pragma clang fp contract(off)                         // h - floor(h) and the interpolation as written: every product is rounded
+    if (n == 0) return __builtin_nan("");
+    const double h = q * (double)(n - 1), fl = floor(h), g = h - fl;
+    const uint32_t j = (uint32_t)fl;
+    const double x0 = (double)key_value(k[j]), x1 = (double)key_value(k[min(j + 1, n - 1)]);
+    return x0 + (x1 - x0) * g;
 }
 
 // fixed-order tree over groups of R consecutive threads whose partials the caller has stored in LDS: combine(i, j) folds slot j

@@ -288,6 +288,37 @@ int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C
 int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t S, size_t L, size_t seg_stride, size_t elem_stride,
                        const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
                        long long* ks_dev, long long* hist_dev, long long* valid_dev);
+/* Quantile-mapping bias correction: empirical quantile mapping (EQM) and quantile delta mapping (QDM; Cannon et al. 2015).  The
+ * reference has no counterpart; DESIGN.md section 18 carries the same definitions.  Arrays are fp32 (N, H, W, C); a cell is one
+ * (h, w, c), per = H*W*C, cell c of sample n lives at x[n*per + c].
+ * dl4ds_quantile_table (the fit).  The valid values of a cell are the finite ones among its N samples: NaN and +-inf are dropped
+ *   (NaN is the masking mechanism), -0.0 counts as +0.0.  With x_0 <= ... <= x_{n-1} the ascending valid values, for each of the Q
+ *   probabilities q_host[i] (HOST array, fp64, strictly increasing, in [0, 1]), in fp64 with every operation rounded on its own:
+ *     h = q_i*(n-1), j = floor(h), g = h - j, val = x_j + (x_{min(j+1, n-1)} - x_j) * g
+ *   (numpy's method='linear'), rounded once to fp32 into table_dev[i*per + c] (layout [Q][per]); with n = 0 all Q entries are NaN.
+ *   valid_dev [per] (may be null) = n.  Segments of up to 512 samples are sorted in LDS, longer ones by the key-only radix sort of
+ *   dl4ds_distribution in a workspace of at most 128 MiB per chunk of cells.  No floating-point atomics: a repeated call gives
+ *   the same bits.
+ * dl4ds_qmap_apply (the map), B samples of per cells; m = model_tab_dev (the model's historical table), o = obs_tab_dev, f =
+ *   target_tab_dev (the table of the period being corrected; null selects EQM, non-null QDM), all [Q][per]; the search table s is m
+ *   for EQM and f for QDM.  Every operation is on fp32 and rounded on its own (no fused multiply-add, division correctly rounded).
+ *   For element value v in cell c:
+ *     1. v not finite: out = v; counted in counts[0] (n_nonfinite).
+ *     2. the cell is UNFITTED iff row 0 of any table in use is NaN there: out = NaN, or v with keep_unfitted != 0; counts[1].
+ *     3. v < s[0]: j = 0, t = 0 (counts[2], n_below); v >= s[Q-1]: j = Q-1, t = 0 (counts[3], n_above); otherwise j is the largest
+ *        index with s[j] <= v (so s[j+1] > v) and t = (v - s[j]) / (s[j+1] - s[j]).
+ *     4. o_t = o[j] at the two ends, otherwise o[j] + (o[j+1] - o[j]) * t; m_t likewise from m.
+ *     5. EQM in the interior: out = o_t.  QDM everywhere and EQM at the two ends: kind 0 (additive): out = v + (o_t - m_t); kind 1
+ *        (multiplicative): out = v * (o_t / m_t), and out = o_t where m_t == 0.
+ *   Tables are non-decreasing by construction; ties are legal (rule 3 never divides by zero).  out_dev may be x_dev.  counts_dev
+ *   [4] (may be null): 64-bit counts ADDED onto what the caller has zeroed (integer atomics, one per workgroup and counter).
+ *   Algorithmic traffic 8 B per element plus the tables once, 4*Q B per cell and table.
+ * Refused (non-zero return, dl4ds_last_error): Q < 2 or Q > 256, a q outside [0, 1] or q not strictly increasing, N == 0,
+ * per == 0, N >= 2^31, a null required pointer, kind not 0 or 1. */
+int dl4ds_quantile_table(const float* x_dev, size_t N, size_t per, const double* q_host, int Q, float* table_dev,
+                         long long* valid_dev);
+int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, const float* model_tab_dev, const float* obs_tab_dev,
+                     const float* target_tab_dev, int Q, int kind, int keep_unfitted, unsigned long long* counts_dev);
 /* Spectral verification of a prediction against an observation: binned power and cross spectra per field.  The reference has no
  * such metric; DESIGN.md section 16 carries the same definitions.  y, p are observation and prediction, fp32, shaped (N, H, W, C).
  * Each of the F = N*C planes is one field.  Fields are ordered [n][c].
