@@ -42,6 +42,8 @@ def __getattr__(name):
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'QuantileMapper': '.postprocessing', 'quantile_map': '.postprocessing', 'check_qmap_args': '.postprocessing',
+            'climate_indices': '.indices', 'precipitation_indices': '.indices', 'temperature_indices': '.indices',
+            'percentile_threshold': '.indices', 'index_scores': '.indices', 'check_index_args': '.indices',
             'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',

@@ -627,6 +627,15 @@ int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, c
     qmap_apply(S(), x_dev, out_dev, B, per, model_tab_dev, obs_tab_dev, target_tab_dev, Q, kind, keep_unfitted, counts_dev);
     API_END
 }
+int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P,
+                          const float* thr_dev, int T, int thr_per_cell, int op, int window, int* valid_dev, int* event_dev,
+                          float* ext_dev, double* sum_dev) {
+    API_BEGIN
+    const size_t ws = climate_indices_workspace_bytes(N, per, period_starts_host, P, T, op, window);      // (refuses a bad request)
+    climate_indices(S(), x_dev, N, per, period_starts_host, P, thr_dev, T, thr_per_cell, op, window, valid_dev, event_dev, ext_dev,
+                    sum_dev, scratch(ws), ws);
+    API_END
+}
 int dl4ds_spectrum(const float* y_dev, const float* p_dev, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
                    int B, double* power_dev, long long* valid_dev, double* mean_dev) {
     API_BEGIN

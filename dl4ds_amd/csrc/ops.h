@@ -196,6 +196,17 @@ void quantile_table(hipStream_t s, const float* x, size_t N, size_t per, const d
                     void* workspace, size_t workspace_bytes);
 void qmap_apply(hipStream_t s, const float* x, float* out, size_t B, size_t per, const float* model_tab, const float* obs_tab,
                 const float* target_tab, int Q, int kind, int keep_unfitted, unsigned long long* counts);
+// Climate indices along the time axis (indices.hip) of x (N samples of per cells) over the P periods of the
+// HOST array period_starts [P + 1] at T <= 4 thresholds (thr [T] or, thr_per_cell, [T][per]; DEVICE) under one comparison op:
+// valid [P][per], event [P][T][6][per] (events, longest event / non-event run, event runs, first / last event offset), ext
+// [P][2][per] (max, min), sum [P][2 + T][per] (sum, largest window sum, event sums; fp64 in sample order).  Outputs may be null
+// (not all) and are overwritten.  climate_indices_workspace_bytes throws on a request the entry refuses, before anything is sized;
+// the workspace takes the period starts.  Synchronises the stream once, after their upload.
+constexpr int IDX_MAX_THRESHOLDS = 4;
+size_t climate_indices_workspace_bytes(size_t N, size_t per, const long long* period_starts, int P, int T, int op, int window);
+void climate_indices(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
+                     int T, int thr_per_cell, int op, int window, int* valid, int* event, float* ext, double* sum, void* workspace,
+                     size_t workspace_bytes);
 // Spectral verification (spectrum.hip) of the N*C fields of y, p (N, H, W, C; p may be null): the unnormalised 2-D DFT of either
 // side in fp64 (kept cells, optional detrending and periodic Hann window), folded over the bins of the HOST map bin [H][W/2 + 1]
 // (values in [-1, B)) into power [N][C][4][B]; valid [N][C] kept cells, mean [N][C][2] the subtracted means.  Outputs are

@@ -319,6 +319,43 @@ int dl4ds_quantile_table(const float* x_dev, size_t N, size_t per, const double*
                          long long* valid_dev);
 int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, const float* model_tab_dev, const float* obs_tab_dev,
                      const float* target_tab_dev, int Q, int kind, int keep_unfitted, unsigned long long* counts_dev);
+/* Climate indices along the time axis: spells, extremes, threshold days and sums per grid cell and period, the raw material of the
+ * ETCCDI indices (CDD / CWD, Rx1day / Rx5day, R1mm / R10mm / R20mm, SDII, PRCPTOT, TXx / TNn, FD / SU, R95pTOT, start and end of a
+ * season).  The reference has no counterpart; DESIGN.md section 19 carries the same definitions.
+ * x is fp32 with shape (N, H, W, C).  A cell is one (h, w, c), and per = H*W*C.  Cell c of sample n lives at x[n*per + c].
+ * The samples are in time order.  The P periods are given by period_starts_host with P + 1 entries: a HOST array of int64, strictly
+ * increasing, first 0, last N.  Period p is the set of samples with start_p <= n < start_{p+1}.  Periods are independent.  Nothing
+ * carries across a boundary: a run is cut there, and a window lies inside one period.
+ * A sample is VALID in a cell iff its value is finite.  NaN is the masking mechanism.  -0.0 counts as +0.0.
+ * There are 1 <= T <= 4 thresholds in the DEVICE array thr_dev, used as in dl4ds_ensemble_exceedance: thr_per_cell == 0 means [T]
+ * values, otherwise [T][per] is a threshold field per cell (a local wet-day percentile, say).  One comparison op applies to all of
+ * them: 0 is >=, 1 is >, 2 is <, 3 is <=.  Comparisons are made on float32.
+ * A valid sample is an EVENT for threshold t iff x op thr(t, c) holds, and is a non-event otherwise.  An event run is a maximal
+ * stretch of consecutive samples of the period that are all events.  A non-event run is the same over valid non-events.  An
+ * invalid sample ends both kinds of run.
+ * If thr(t, c) is not finite, the per-threshold outputs of that (t, c) are -1 for the integers and NaN for the sum, in every period.
+ * Per period p and cell c, each output may be null and is then skipped.  All outputs are overwritten.
+ *   valid_dev int32 [P][per]         the number of valid samples
+ *   event_dev int32 [P][T][6][per]   in this order: the number of events; the longest event run; the longest non-event run; the
+ *                                    number of event runs; the offset from the period's first sample of the first event, -1 if
+ *                                    none; the offset of the last event, -1 if none
+ *   ext_dev   fp32  [P][2][per]      the largest and smallest valid value, NaN if there is none; a zero is always written as +0.0
+ *   sum_dev   fp64  [P][2 + T][per]  row 0: the sum of the valid values, added one by one in ascending sample order, in fp64,
+ *                                    starting from the first valid value; NaN if there is none.
+ *                                    row 1: the largest window sum, over all windows of `window` consecutive samples
+ *                                    (1 <= window <= 32) that lie wholly inside the period and are all valid.  Each window sum is
+ *                                    formed afresh: its `window` values are added in ascending sample order in fp64 (no sliding add
+ *                                    and subtract, which gives other bits).  NaN if no such window exists.
+ *                                    row 2 + t: the sum of the event values for threshold t, in the same order as row 0; 0.0 if
+ *                                    the threshold is finite and there is no event.
+ * There are no floating-point atomics and no sum whose order can vary.  A repeated call gives the same bits.
+ * Refused (non-zero return, dl4ds_last_error): P < 1; starts that are not strictly increasing from 0 to N; N == 0, per == 0 or
+ * N >= 2^31; T or window out of range; an op outside 0..3; a null x_dev, thr_dev or period_starts_host; all four outputs null.
+ * A lane owns one cell and walks one period in order, so parallelism is cells x periods; a period is never split over time, which
+ * would change the order of the fp64 sums.  Algorithmic traffic: 4 B per element read once, the outputs written once. */
+int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P,
+                          const float* thr_dev, int T, int thr_per_cell, int op, int window, int* valid_dev, int* event_dev,
+                          float* ext_dev, double* sum_dev);
 /* Spectral verification of a prediction against an observation: binned power and cross spectra per field.  The reference has no
  * such metric; DESIGN.md section 16 carries the same definitions.  y, p are observation and prediction, fp32, shaped (N, H, W, C).
  * Each of the F = N*C planes is one field.  Fields are ordered [n][c].
