@@ -50,6 +50,17 @@ def signs(shape, seed):
     return (1.0 - 2.0 * ((h >> np.uint32(9)) & np.uint32(1)).astype(np.float32)).reshape(shape)
 
 
+def hashed_small_ints(shape, seed, zeros=False):
+    """Integer-valued float32 in {-2, -1, 1, 2} (``zeros``: a fifth of the entries exactly 0) from the same hash: so few values that
+    a 2x2 window often holds its maximum more than once."""
+    h = _mix(int(np.prod(shape)), seed)
+    v = ((h & np.uint32(1)) + np.uint32(1)).astype(np.float32)
+    v *= (1.0 - 2.0 * ((h >> np.uint32(6)) & np.uint32(1)).astype(np.float32))
+    if zeros:
+        v[((h >> np.uint32(7)) % np.uint32(5)) == 0] = 0.0
+    return v.reshape(shape)
+
+
 # ---------------------------------------------------------------------------------------------------------------- size rule
 def is_large(totalv):
     """The second-iteration rule: between 1.25x and 1.5x the grid cap in vector elements, so at least a quarter of the threads
@@ -131,3 +142,68 @@ def act_error(got, ref, x, scale=1.0):
 
 def act_bound(e_cpu):
     return max(4.0 * e_cpu, ACT_FLOOR)
+
+
+# ---------------------------------------------------------------------------------------------------------------- max-pool 2x2
+POOL_QUAD_CHANS, POOL_SCALAR_CHANS = (4, 8), (3, 6)
+POOL_GRIDS = ((2, 8, 12), (1, 7, 9), (1, 3, 2), (1, 2, 2))
+POOL_ODD_GRIDS = tuple(g for g in POOL_GRIDS if (g[1] | g[2]) & 1)
+POOL_WINDOW = ((0, 0), (0, 1), (1, 0), (1, 1))       # the order in which the backward kernels look for the maximum
+
+
+def pool_quad(c):
+    """pool_quad_ok for every view of a dense tensor in a 16-byte-aligned buffer (make_view sets vec = C % 4 == 0 and aligned; no
+    depth_to_space layout, no channel affine): the four-channel kernels run iff C % 4 == 0."""
+    return c % 4 == 0
+
+
+def pool_quad_ok_in_source():
+    """The conjuncts of pool_quad_ok (csrc/elementwise.hip) and make_view's rule for TView::vec (csrc/common.h), as written."""
+    src = open(os.path.join(ROOT, 'dl4ds_amd', 'csrc', 'elementwise.hip')).read()
+    m = re.search(r'static bool pool_quad_ok\(const TView& v\) \{ return ([^;]*); \}', src)
+    hdr = open(os.path.join(ROOT, 'dl4ds_amd', 'csrc', 'common.h')).read()
+    v = re.search(r'inline TView make_view\(float\* p, int N, int H, int W, int C\) \{.*?v\.vec = ([^;]*);', hdr, re.S)
+    return sorted(t.strip() for t in m.group(1).split('&&')), re.sub(r'\s+', '', v.group(1))
+
+
+def pool_windows(x):
+    """(4, N, H // 2, W // 2, C): the entries of every 2x2 window in POOL_WINDOW order."""
+    ho, wo = x.shape[1] // 2, x.shape[2] // 2
+    return np.stack([x[:, dy:2 * ho:2, dx:2 * wo:2, :] for dy, dx in POOL_WINDOW])
+
+
+def maxpool2_ref(x):
+    return pool_windows(x).max(axis=0)
+
+
+def maxpool2_bwd_ref(x, dy):
+    """dx: dy at the first maximum of each window in POOL_WINDOW order, 0 at the other three and in the row / column that VALID
+    pooling drops."""
+    win = pool_windows(x)
+    first = np.argmax(win == win.max(axis=0), axis=0)          # (argmax returns the first True)
+    ho, wo = x.shape[1] // 2, x.shape[2] // 2
+    dx = np.zeros_like(x)
+    for k, (oy, ox) in enumerate(POOL_WINDOW):
+        dx[:, oy:2 * ho:2, ox:2 * wo:2, :] = np.where(first == k, dy, 0)
+    return dx
+
+
+def pool_tie_share(x):
+    win = pool_windows(x)
+    return float(((win == win.max(axis=0)).sum(axis=0) > 1).mean())
+
+
+def pool_has_dead_window(x):
+    """A window whose four entries are all <= 0."""
+    return bool((pool_windows(x).max(axis=0) <= 0).any())
+
+
+def pool_input(shape, relu):
+    """hashed_small_ints with the first seed >= 1 at which the case has what it is there for: at least a quarter of the windows of
+    the tensor the pooling reads (``relu``: max(x, 0)) hold their maximum more than once, and with ``relu`` at least one window of x
+    is all <= 0.  tests/test_graph_ops_oracle.py checks both on every named case."""
+    for seed in range(1, 1000):
+        x = hashed_small_ints(shape, seed, zeros=relu)
+        if pool_tie_share(np.maximum(x, 0) if relu else x) >= 0.25 and (not relu or pool_has_dead_window(x)):
+            return x
+    raise AssertionError(shape)

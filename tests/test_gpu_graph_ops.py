@@ -1,6 +1,7 @@
 """Op-level, bit-exact tests of the kernels that move activations and gradients between the convolutions: Concatenate (concat_join /
 concat_split and the per-slice view_axpy / view_axpy_masked fallback), Add (add_act, view_axpy, masked_axpy, masked_axpy_pair),
-Activation (act_forward / act_backward), slice / crop / zero padding and repeat_time -- each through a one- or two-op graph.
+Activation (act_forward / act_backward), slice / crop / zero padding, repeat_time and MaxPooling2D (maxpool2_forward /
+maxpool2_backward) -- each through a one- or two-op graph.
 
 How the gradient is made exact (tests/graph_ops_cases.py): the MAE loss writes dY = g * sign(pred - target) with g = 1 / size; the
 targets are ``forward - s`` for a +-1 pattern s, so dY = g * s and the expected gradient of a copy op is a selection of g * s.  g is
@@ -526,3 +527,69 @@ def test_repeat_time_into_concat(monkeypatch, B, T, chans):
         assert np.abs(d).max() > 0
         _eq(da, _seq_sum(d[..., :chans[0]]), 'gradient of a')
         _eq(db, _seq_sum(d[..., chans[0]:]), 'gradient of b')
+
+
+# ------------------------------------------------------------------------------------------------------------------- MaxPooling2D
+def _pool_case(monkeypatch, c, grid, relu=False, twice=False, x=None):
+    """maxpool2 of one input (``relu``: behind the ReLU identity convolution, so the pooled tensor is grad_masked; ``twice``: pooled
+    by two ops whose results are concatenated, so the second backward to run accumulates onto the first's).  Forward and the
+    gradient of the pooled tensor bitwise against tests/graph_ops_cases.maxpool2_ref / maxpool2_bwd_ref."""
+    monkeypatch.setenv('DL4DS_NO_CONCAT_ALIAS', '1')
+    n, h, w = grid
+    if x is None:
+        x = K.pool_input((n, h, w, c), relu)
+    g = _builder()
+    t = g.input(h, w, c, requires_grad=True)
+    src = _relu_id(g, t, 'id') if relu else t
+    xv = np.maximum(x, 0) if relu else x
+    out = g.concat([g.maxpool2(src, 'p0'), g.maxpool2(src, 'p1')]) if twice else g.maxpool2(src)
+    y, s, (dx,), tf, tb, gu = _run(g, out, [x], [src])
+    ref = K.maxpool2_ref(xv)
+    _eq(y, np.concatenate([ref, ref], axis=-1) if twice else ref, 'forward')
+    dy = gu * s
+    want = K.maxpool2_bwd_ref(xv, dy[..., :c])
+    if twice:
+        want = want + K.maxpool2_bwd_ref(xv, dy[..., c:])
+    if relu:
+        want = np.where(xv > 0, want, 0)
+    _eq(dx, want, 'gradient of the pooled tensor')
+    dropped = np.ones((h, w), bool)
+    dropped[:h // 2 * 2, :w // 2 * 2] = False
+    assert (dx[:, dropped] == 0).all()
+    k = 2 if twice else 1
+    assert tf.get('maxpool2_fwd') == k and tb.get('maxpool2_bwd') == k
+    return tf, tb
+
+
+@pytest.mark.parametrize('relu', [False, True])
+@pytest.mark.parametrize('grid', K.POOL_GRIDS)
+@pytest.mark.parametrize('c', K.POOL_QUAD_CHANS + K.POOL_SCALAR_CHANS)
+def test_maxpool(monkeypatch, c, grid, relu):
+    """maxpool2_fwd4_kernel / maxpool2_bwd4_kernel (C = 4, 8: pool_quad_ok) and maxpool2_fwd_kernel / maxpool2_bwd_kernel (C = 3, 6)
+    on inputs from {-2 .. 2} where at least a quarter of the windows hold their maximum more than once: y is the window maximum,
+    dx gets dY at the first maximum in the order (0,0), (0,1), (1,0), (1,1) and exact zeros elsewhere, the row / column dropped by
+    VALID pooling on (7, 9) and (3, 2) included (MaxPoolOp::backward fills, then accumulates).  ``relu``: the pooled tensor is a
+    ReLU output whose only consumer is the pooling (grad_masked): relu_mask = 1, expected where(x > 0, routed, 0); at least one
+    window is all zero there, so its first entry is selected and then masked."""
+    assert K.pool_quad(c) == (c in K.POOL_QUAD_CHANS)
+    _pool_case(monkeypatch, c, grid, relu=relu)
+
+
+@pytest.mark.parametrize('relu', [False, True])
+@pytest.mark.parametrize('grid', K.POOL_GRIDS)
+@pytest.mark.parametrize('c', K.POOL_QUAD_CHANS + K.POOL_SCALAR_CHANS)
+def test_maxpool_same_tensor_twice(monkeypatch, c, grid, relu):
+    """concat([maxpool2(x), maxpool2(x)]): the pooling whose backward runs second finds grad_written set and accumulates
+    (accumulate = 1 in both kernels, with and without relu_mask); the sum of two g * s terms is exact: {-2g, 0, 2g}.  On the odd
+    grids the first backward fills and accumulates, the second accumulates again: the dropped row and column stay 0."""
+    tf, tb = _pool_case(monkeypatch, c, grid, relu=relu, twice=True)
+    assert tf.get('concat_join') == 1 and tb.get('concat_split') == 1
+
+
+def test_maxpool_quad_second_iteration(monkeypatch):
+    """C = 4 with total / 4 output quads between 1.25 and 1.5 x the grid cap: maxpool2_fwd4_kernel / maxpool2_bwd4_kernel past the
+    first grid-stride iteration, forward and backward bitwise."""
+    n, ho, wo = K.large_grid(1)
+    assert K.is_large(n * ho * wo * 4 // 4)
+    grid = (n, 2 * ho, 2 * wo)
+    _pool_case(monkeypatch, 4, grid, x=K.hashed_small_ints(grid + (4,), 7))
