@@ -109,6 +109,27 @@ static float* scratch(size_t bytes) {       // grow-only scratch for the single-
     return p;
 }
 static float* nc(const float* p) { return const_cast<float*>(p); }
+// The three B-element index lists of a batch (first frame, crop corner; a null list: zeros) travel in one small upload into a
+// persistent device buffer, grown on demand -> [idx | cy | cx].  The upload is ordered on the library stream behind the previous
+// batch's kernels, which read the old contents.
+static const int* upload_index_lists(const int* idx_host, const int* cy_host, const int* cx_host, int B) {
+    static int* d_idx = nullptr;
+    static int cap = 0;
+    static std::vector<int> h_idx;
+    if (3 * B > cap) {
+        if (d_idx) HIP_CHECK(hipFree(d_idx));
+        cap = std::max(3 * B, 3 * 256);
+        HIP_CHECK(hipMalloc((void**)&d_idx, (size_t)cap * sizeof(int)));
+    }
+    h_idx.assign(3 * (size_t)B, 0);
+    for (int b = 0; b < B; ++b) {
+        if (idx_host) h_idx[b] = idx_host[b];
+        if (cy_host) h_idx[B + b] = cy_host[b];
+        if (cx_host) h_idx[2 * B + b] = cx_host[b];
+    }
+    HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), 3 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, S()));
+    return d_idx;
+}
 
 extern "C" {
 
@@ -326,19 +347,7 @@ int dl4ds_batch_prepare(const float* hr, const float* pred, const float* stat, c
                         int T, int B, int scale, int psy, int psx, int pin, int static_in_lr) {
     API_BEGIN
     DL4DS_REQUIRE(B > 0 && idx_host && cy_host && cx_host, "batch_prepare: index lists missing");
-    // the three B-element index lists travel in one small upload (persistent device buffer, grown on demand)
-    static int* d_idx = nullptr;
-    static int cap = 0;
-    static std::vector<int> h_idx;
-    if (3 * B > cap) {
-        if (d_idx) HIP_CHECK(hipFree(d_idx));
-        cap = std::max(3 * B, 3 * 256);
-        HIP_CHECK(hipMalloc((void**)&d_idx, (size_t)cap * sizeof(int)));
-    }
-    // the upload is ordered on the library stream behind the previous batch's kernels, which read the old contents
-    h_idx.resize(3 * (size_t)B);
-    for (int b = 0; b < B; ++b) { h_idx[b] = idx_host[b]; h_idx[B + b] = cy_host[b]; h_idx[2 * B + b] = cx_host[b]; }
-    HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), 3 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, S()));
+    const int* d_idx = upload_index_lists(idx_host, cy_host, cx_host, B);
     batch_prepare(S(), hr, pred, stat, d_idx, d_idx + B, d_idx + 2 * B, out_lr, out_hr, out_stat, H, W, C, P, S_, T, B, scale,
                   psy, psx, pin, static_in_lr);
     API_END
@@ -349,17 +358,7 @@ int dl4ds_batch_prepare_taps(const float* hr, const float* pred, const float* st
                              const dl4ds_tap_axis* dn_patch, const dl4ds_tap_axis* dn_field, const dl4ds_tap_axis* up_field) {
     API_BEGIN
     DL4DS_REQUIRE(B > 0 && idx_host && cy_host && cx_host, "batch_prepare_taps: index lists missing");
-    static int* d_idx = nullptr;
-    static int cap = 0;
-    static std::vector<int> h_idx;
-    if (3 * B > cap) {
-        if (d_idx) HIP_CHECK(hipFree(d_idx));
-        cap = std::max(3 * B, 3 * 256);
-        HIP_CHECK(hipMalloc((void**)&d_idx, (size_t)cap * sizeof(int)));
-    }
-    h_idx.resize(3 * (size_t)B);
-    for (int b = 0; b < B; ++b) { h_idx[b] = idx_host[b]; h_idx[B + b] = cy_host[b]; h_idx[2 * B + b] = cx_host[b]; }
-    HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), 3 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, S()));
+    const int* d_idx = upload_index_lists(idx_host, cy_host, cx_host, B);
     auto axes = [](const dl4ds_tap_axis* t, TapAxis* o) -> const TapAxis* {
         if (!t) return nullptr;
         for (int i = 0; i < 2; ++i) { o[i].idx = t[i].idx; o[i].wt = t[i].wt; o[i].k = t[i].k; }
@@ -375,20 +374,7 @@ int dl4ds_batch_gather(const dl4ds_gather_group* groups, int n_groups, const int
     API_BEGIN
     DL4DS_REQUIRE(groups && n_groups >= 1 && n_groups <= 3 && B > 0, "batch_gather: groups / batch size");
     DL4DS_REQUIRE((cy_host == nullptr) == (cx_host == nullptr), "batch_gather: crop corner lists");
-    static int* d_idx = nullptr;
-    static int cap = 0;
-    static std::vector<int> h_idx;
-    if (3 * B > cap) {
-        if (d_idx) HIP_CHECK(hipFree(d_idx));
-        cap = std::max(3 * B, 3 * 256);
-        HIP_CHECK(hipMalloc((void**)&d_idx, (size_t)cap * sizeof(int)));
-    }
-    h_idx.assign(3 * (size_t)B, 0);
-    for (int b = 0; b < B; ++b) {
-        if (idx_host) h_idx[b] = idx_host[b];
-        if (cy_host) { h_idx[B + b] = cy_host[b]; h_idx[2 * B + b] = cx_host[b]; }
-    }
-    HIP_CHECK(hipMemcpyAsync(d_idx, h_idx.data(), 3 * (size_t)B * sizeof(int), hipMemcpyHostToDevice, S()));
+    const int* d_idx = upload_index_lists(idx_host, cy_host, cx_host, B);
     GatherGroup g[3];
     for (int i = 0; i < n_groups; ++i) {
         const dl4ds_gather_group& q = groups[i];

@@ -17,6 +17,7 @@
 #include "ops.h"
 #include "prof.h"
 #include "conv_kernels.h"
+#include "conv_cache.h"
 #include <algorithm>
 #include <mutex>
 #include <vector>
@@ -229,26 +230,7 @@ __global__ void splitk_combine_kernel(const float* __restrict__ slabs, int S, si
     }
 }
 
-struct StreamScratch { hipStream_t stream; float* buf; size_t floats; };
-float* splitk_scratch(hipStream_t s, size_t floats) {     // grow-only, one buffer per stream (launches on a stream are ordered)
-    static std::mutex mu;
-    static std::vector<StreamScratch> all;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : all) {
-        if (e.stream != s) continue;
-        if (e.floats < floats) {
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipFree(e.buf));
-            HIP_CHECK(hipMalloc((void**)&e.buf, floats * sizeof(float)));
-            e.floats = floats;
-        }
-        return e.buf;
-    }
-    StreamScratch e{s, nullptr, std::max<size_t>(floats, (size_t)1 << 20)};
-    HIP_CHECK(hipMalloc((void**)&e.buf, e.floats * sizeof(float)));
-    all.push_back(e);
-    return e.buf;
-}
+float* splitk_scratch(hipStream_t s, size_t floats) { static StreamScratch sc((size_t)1 << 20); return sc.get(s, floats); }
 
 // --------------------------------------------------------------------------------------------
 // Double-buffered ("db") variant for the MFMA-bound layers.  The K loop is flattened into stages

@@ -26,6 +26,7 @@
 #include "ops.h"
 #include "prof.h"
 #include "launch.h"
+#include "conv_cache.h"
 #include <algorithm>
 #include <cstdlib>
 #include <string>
@@ -118,9 +119,7 @@ __global__ void __launch_bounds__(256) split_filter_kernel(const float* __restri
 // The fragments of ALL the layers a graph pass will run on this kernel, in one launch (the Winograd layers' scheme, conv_wino.hip: "transformed
 // filters of a GRAPH's layers"): 8 launches of split_filter_kernel per cfg2 step become 2.  Job = (filter, its passes of 48 input channels).
 struct SplitFilterJob { const float* w; u32x4* frag; int Cin, Cout, per_pass, total, first; };      // total: entries of all passes; first: the job's first block
-constexpr int SPLIT_JOBS_MAX = 24;
-struct SplitFilterJobs { SplitFilterJob j[SPLIT_JOBS_MAX]; int n, total; };                        // total: blocks
-__global__ void __launch_bounds__(256) split_filter_batched_kernel(const SplitFilterJobs jobs) {
+__global__ void __launch_bounds__(256) split_filter_batched_kernel(const FilterJobs<SplitFilterJob> jobs) {
     int k = 0;                                                       // block -> job: wave-uniform (scalar loads from the kernel arguments)
 #pragma unroll 1
     while (k + 1 < jobs.n && (int)blockIdx.x >= jobs.j[k + 1].first) ++k;
@@ -501,85 +500,35 @@ int cu_count() {
 }
 
 // The filter fragments of a call live in a scratch buffer of the call's STREAM (one per stream, like the Winograd kernels' scratch: two
-// streams may each have a convolution in flight; on one stream the fragment kernel and the convolution that reads it are ordered).  They are
-// rebuilt on every call -- one short launch.
-float* frag_scratch(hipStream_t s, size_t floats) {
-    struct Slot { hipStream_t s; float* buf; size_t cap; };
-    static std::vector<Slot> slots;
-    for (auto& e : slots) {
-        if (e.s != s) continue;
-        if (e.cap < floats) {
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipFree(e.buf));
-            HIP_CHECK(hipMalloc((void**)&e.buf, floats * sizeof(float)));
-            e.cap = floats;
-        }
-        return e.buf;
-    }
-    Slot e{s, nullptr, std::max<size_t>(floats, 1 << 18)};
-    HIP_CHECK(hipMalloc((void**)&e.buf, e.cap * sizeof(float)));
-    slots.push_back(e);
-    return e.buf;
-}
-
-// Inside a graph pass a layer's fragments have a buffer of their own and are rebuilt by ONE launch per pass for all registered layers
-// (split_filters_refresh, called where the Winograd filters are refreshed); freshness never outlives a forward pass.  Outside a pass (the
-// op-level API) nothing is registered or trusted: the stream's scratch and one launch per call.
-struct SplitFilterEntry { const float* w; int Cin, Cout, per_pass, passes, kind; hipStream_t stream; u32x4* frag; bool fresh; };
-std::vector<SplitFilterEntry>& split_entries() { static std::vector<SplitFilterEntry> v; return v; }
-constexpr size_t SPLIT_ENTRIES_MAX = 512;
-
-u32x4* split_filter_lookup(hipStream_t s, const float* w, int Cin, int Cout, int per_pass, int passes, bool& need) {
-    need = true;
-    int kind = 0;
-    if (!wino_pass_active(kind)) return reinterpret_cast<u32x4*>(frag_scratch(s, (size_t)per_pass * passes * 4));
-    auto& es = split_entries();
-    for (auto& e : es)
-        if (e.w == w && e.Cin == Cin && e.Cout == Cout && e.per_pass == per_pass && e.passes == passes && e.stream == s) {
-            need = !e.fresh;
-            e.fresh = true;                      // (the caller builds them now if they were not)
-            return e.frag;
-        }
-    if (es.size() >= SPLIT_ENTRIES_MAX) return reinterpret_cast<u32x4*>(frag_scratch(s, (size_t)per_pass * passes * 4));
-    SplitFilterEntry e{w, Cin, Cout, per_pass, passes, kind, s, nullptr, true};
-    HIP_CHECK(hipMalloc((void**)&e.frag, (size_t)per_pass * passes * sizeof(u32x4)));
-    es.push_back(e);
-    return e.frag;
-}
+// streams may each have a convolution in flight; on one stream the fragment kernel and the convolution that reads it are ordered) and are
+// rebuilt on every call -- one short launch.  Inside a graph pass a layer's fragments have a buffer of their own and are rebuilt by ONE
+// launch per pass for all registered layers (conv_cache.h: DerivedFilterCache; split_filters_refresh, called where the Winograd filters
+// are refreshed).
+struct SplitFilterKey {
+    int Cin, Cout, per_pass, passes;
+    bool operator==(const SplitFilterKey& o) const { return Cin == o.Cin && Cout == o.Cout && per_pass == o.per_pass && passes == o.passes; }
+};
+typedef DerivedFilterCache<SplitFilterKey, SplitFilterJob> SplitFilterCache;
+SplitFilterCache& split_filters() { static SplitFilterCache c(1 << 18); return c; }
 
 }  // namespace
 
-void split_filters_invalidate(const float* lo, const float* hi) {
-    for (auto& e : split_entries())
-        if (e.w >= lo && e.w < hi) e.fresh = false;
-}
-
-void split_filters_release(const float* lo, const float* hi) {
-    auto& es = split_entries();
-    for (size_t i = 0; i < es.size();) {
-        if (es[i].w >= lo && es[i].w < hi) { (void)hipFree(es[i].frag); es[i] = es.back(); es.pop_back(); }
-        else ++i;
-    }
-}
+void split_filters_invalidate(const float* lo, const float* hi) { split_filters().invalidate(lo, hi); }
+void split_filters_release(const float* lo, const float* hi) { split_filters().release(lo, hi); }
 
 void split_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind) {
-    SplitFilterJobs jobs;
-    jobs.n = 0; jobs.total = 0;
-    auto flush = [&]() {
-        if (!jobs.n) return;
-        ProfScope ps(s, "split_filters", 0.0, 16.0 * jobs.total * 256);
-        DL4DS_LAUNCH(split_filter_batched_kernel, dim3(jobs.total), dim3(256), 0, s, jobs);
-        HIP_CHECK(hipGetLastError());
-        jobs.n = 0; jobs.total = 0;
-    };
-    for (auto& e : split_entries()) {
-        if (e.fresh || e.kind != kind || e.stream != s || e.w < lo || e.w >= hi) continue;
-        if (jobs.n == SPLIT_JOBS_MAX) flush();
-        jobs.j[jobs.n++] = SplitFilterJob{e.w, e.frag, e.Cin, e.Cout, e.per_pass, e.per_pass * e.passes, jobs.total};
-        jobs.total += cdiv(e.per_pass * e.passes, 256);
-        e.fresh = true;
-    }
-    flush();
+    split_filters().refresh(
+        s, lo, hi, kind,
+        [](const SplitFilterCache::Entry& e, SplitFilterJob& j) {
+            const SplitFilterKey& k = e.key;
+            j = SplitFilterJob{e.w, reinterpret_cast<u32x4*>(e.buf), k.Cin, k.Cout, k.per_pass, k.per_pass * k.passes, 0};
+            return cdiv(j.total, 256);
+        },
+        [&](const FilterJobs<SplitFilterJob>& jobs) {
+            ProfScope ps(s, "split_filters", 0.0, 16.0 * jobs.total * 256);
+            DL4DS_LAUNCH(split_filter_batched_kernel, dim3(jobs.total), dim3(256), 0, s, jobs);
+            HIP_CHECK(hipGetLastError());
+        });
 }
 
 bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep) {
@@ -628,7 +577,8 @@ bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const 
                  4.0 * (px * (in.C + out.C * (1 + (ep.add.p ? 1 : 0) + (ep.mask.p ? 1 : 0) + (ep.accumulate ? 1 : 0))) + 9.0 * in.C * out.C), fl);
     const int per_pass = p.nchunk * (NMW + NHW) * 12 * 64;                  // uint4 entries
     bool need_frag = true;
-    u32x4* frag = split_filter_lookup(s, w, in.C, out.C, per_pass, passes, need_frag);
+    u32x4* frag = reinterpret_cast<u32x4*>(
+        split_filters().lookup(s, w, SplitFilterKey{in.C, out.C, per_pass, passes}, (size_t)per_pass * passes * 4, need_frag));
     int grid = std::min((int)std::min<long>(items, cu_count()), cu_count()) * 1;
     grid = std::max(1, grid / p.nchunk) * p.nchunk;
     if (grid > cu_count()) grid = (cu_count() / p.nchunk) * p.nchunk;

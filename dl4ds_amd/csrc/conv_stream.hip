@@ -20,6 +20,7 @@
 #include "ops.h"
 #include "prof.h"
 #include "conv_kernels.h"
+#include "conv_cache.h"
 #include <algorithm>
 #include <type_traits>
 #include <mutex>
@@ -774,26 +775,7 @@ __global__ void pad_filter_kernel(const float* __restrict__ w, float* __restrict
         wp[e] = c < Cout ? w[(size_t)r * Cout + c] : 0.f;
     }
 }
-struct PadScratch { hipStream_t stream; float* buf; size_t floats; };
-float* pad_scratch(hipStream_t s, size_t floats) {       // grow-only, one buffer per stream (launches on a stream are ordered)
-    static std::mutex mu;
-    static std::vector<PadScratch> all;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : all) {
-        if (e.stream != s) continue;
-        if (e.floats < floats) {
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipFree(e.buf));
-            HIP_CHECK(hipMalloc((void**)&e.buf, floats * sizeof(float)));
-            e.floats = floats;
-        }
-        return e.buf;
-    }
-    PadScratch e{s, nullptr, std::max<size_t>(floats, 1 << 16)};
-    HIP_CHECK(hipMalloc((void**)&e.buf, e.floats * sizeof(float)));
-    all.push_back(e);
-    return e.buf;
-}
+float* pad_scratch(hipStream_t s, size_t floats) { static StreamScratch sc(1 << 16); return sc.get(s, floats); }
 
 template <int KS, int E, int NT, int MT>
 void launch_stream(hipStream_t s, StreamParams& sp, int N) {

@@ -1,6 +1,7 @@
 // dl4ds_amd -- Winograd F(2x2, 3x3) convolution: eligibility, channel passes, epilogue form (kernel: conv_wino_kernel.h)
 #include "conv_wino_kernel.h"
 #include "conv_wino4_kernel.h"
+#include "conv_cache.h"
 
 namespace {
 
@@ -17,33 +18,33 @@ int wino_cu_count() {
 // U = G g G^T in the fragment order the workgroups load it in: element ((pc * 4 + xi) * F/4 + f4) * 64 + lane, component j,
 // f = 4 f4 + j = (nu * 4 KQ + ks) * NT + cb (pc = pass * nchunk + chunk, F = 16 KQ NT); nu = 3 negated
 // (both forms of the kernel -- conv_wino_kernel / conv_wino2_kernel -- read this one layout: nu = 1, 2 hold (U0 +- U1 + U2) / 2)
+__device__ __forceinline__ float wino_filter_value(const float* __restrict__ w, int Cin, int Cout, int KQ, int NT, int nchunk, int idx) {
+    const int F = 16 * KQ * NT;
+    const int j = idx & 3, lane = (idx >> 2) & 63;
+    int r = idx >> 8;
+    const int f4 = r % (F / 4); r /= F / 4;
+    const int xi = r & 3; r >>= 2;
+    const int chunk = r % nchunk, pass = r / nchunk;
+    const int f = 4 * f4 + j;
+    const int nu = f / (4 * KQ * NT), ks = (f / NT) % (4 * KQ), cb = f % NT;
+    const int cin = pass * 16 * KQ + 16 * (ks >> 2) + 4 * (lane >> 4) + (ks & 3);
+    const int co = chunk * 16 * NT + 16 * cb + (lane & 15);
+    if (cin >= Cin || co >= Cout) return 0.f;
+    const float c0 = xi == 0 ? 1.f : (xi == 3 ? 0.f : .5f);
+    const float c1 = xi == 1 ? .5f : (xi == 2 ? -.5f : 0.f);
+    const float c2 = xi == 3 ? 1.f : (xi == 0 ? 0.f : .5f);
+    const size_t tap = (size_t)Cin * Cout;
+    const float* p = w + (size_t)cin * Cout + co;
+    float t[3];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) t[b] = c0 * p[(0 * 3 + b) * tap] + c1 * p[(1 * 3 + b) * tap] + c2 * p[(2 * 3 + b) * tap];
+    return nu == 0 ? t[0] : (nu == 1 ? .5f * (t[0] + t[1] + t[2]) : (nu == 2 ? .5f * (t[0] - t[1] + t[2]) : -t[2]));
+}
+
 __global__ void __launch_bounds__(256) wino_filter_kernel(const float* __restrict__ w, float* __restrict__ u, int Cin, int Cout, int KQ,
                                                           int NT, int nchunk, int total) {
-    const int F = 16 * KQ * NT;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x) {
-        const int j = idx & 3, lane = (idx >> 2) & 63;
-        int r = idx >> 8;
-        const int f4 = r % (F / 4); r /= F / 4;
-        const int xi = r & 3; r >>= 2;
-        const int chunk = r % nchunk, pass = r / nchunk;
-        const int f = 4 * f4 + j;
-        const int nu = f / (4 * KQ * NT), ks = (f / NT) % (4 * KQ), cb = f % NT;
-        const int cin = pass * 16 * KQ + 16 * (ks >> 2) + 4 * (lane >> 4) + (ks & 3);
-        const int co = chunk * 16 * NT + 16 * cb + (lane & 15);
-        float val = 0.f;
-        if (cin < Cin && co < Cout) {
-            const float c0 = xi == 0 ? 1.f : (xi == 3 ? 0.f : .5f);
-            const float c1 = xi == 1 ? .5f : (xi == 2 ? -.5f : 0.f);
-            const float c2 = xi == 3 ? 1.f : (xi == 0 ? 0.f : .5f);
-            const size_t tap = (size_t)Cin * Cout;
-            const float* p = w + (size_t)cin * Cout + co;
-            float t[3];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) t[b] = c0 * p[(0 * 3 + b) * tap] + c1 * p[(1 * 3 + b) * tap] + c2 * p[(2 * 3 + b) * tap];
-            val = nu == 0 ? t[0] : (nu == 1 ? .5f * (t[0] + t[1] + t[2]) : (nu == 2 ? .5f * (t[0] - t[1] + t[2]) : -t[2]));
-        }
-        u[idx] = val;
-    }
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += gridDim.x * blockDim.x)
+        u[idx] = wino_filter_value(w, Cin, Cout, KQ, NT, nchunk, idx);
 }
 
 // F(4x4, 3x3): U = G g G^T (6 x 6 positions, points 0, +-1, +-2, inf) in the order conv_wino4_kernel's waves load it in: element
@@ -89,41 +90,17 @@ __global__ void __launch_bounds__(256) wino4_filter_kernel(const float* __restri
         u[idx] = wino4_filter_value(w, Cin, Cout, KQ, NT, nchunk, idx);
 }
 
-// transformed filters: grow-only, one buffer per stream (launches on a stream are ordered)
-struct WinoScratch { hipStream_t stream; float* buf; size_t floats; };
-float* wino_scratch(hipStream_t s, size_t floats) {
-    static std::mutex mu;
-    static std::vector<WinoScratch> all;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : all) {
-        if (e.stream != s) continue;
-        if (e.floats < floats) {
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipFree(e.buf));
-            HIP_CHECK(hipMalloc((void**)&e.buf, floats * sizeof(float)));
-            e.floats = floats;
-        }
-        return e.buf;
-    }
-    WinoScratch e{s, nullptr, std::max<size_t>(floats, 1 << 20)};
-    HIP_CHECK(hipMalloc((void**)&e.buf, e.floats * sizeof(float)));
-    all.push_back(e);
-    return e.buf;
-}
+// ---- transformed filters of a GRAPH's layers: one batched launch per pass (conv_cache.h: DerivedFilterCache) ---------------------
+struct WinoFilterKey {
+    int Cin, Cout, KQ, NT, nchunk, f44;                                                               // f44: F(4x4) order
+    bool operator==(const WinoFilterKey& o) const { return Cin == o.Cin && Cout == o.Cout && KQ == o.KQ && NT == o.NT && nchunk == o.nchunk && f44 == o.f44; }
+};
+struct WinoFilterJob { const float* w; float* u; int Cin, Cout, KQ, NT, nchunk, total, first, f44; };     // first: the job's first block
+constexpr int WINO_FILTER_PER_BLOCK = 1024;
+typedef DerivedFilterCache<WinoFilterKey, WinoFilterJob> WinoFilterCache;
+WinoFilterCache& wino_filters() { static WinoFilterCache c(1 << 20); return c; }
 
-// ---- transformed filters of a GRAPH's layers: one batched launch per pass (round 5) ---------------------------------------------
-// Inside a graph pass (WinoPassGuard, opened by Graph::forward / Graph::backward) every Winograd layer registers its filter
-// (pointer into the graph's parameter arena W or its derived-weights arena Wt, shape, fragment geometry) with a buffer of its own.
-// From the second pass on, wino_filters_refresh(range) transforms ALL registered filters of that range in ONE launch -- at the start
-// of the forward pass for W, right after the dgrad arrangements have been rebuilt for Wt -- and the layers find their entry fresh:
-// 20 launches of wino_filter_kernel per cfg2 step become 2.  Freshness never outlives a forward pass: Graph::forward invalidates
-// the graph's ranges first (the optimiser, set_weights, a checkpoint load or a broadcast may have touched W).  Outside a graph pass
-// (the op-level API) nothing is registered or trusted: the shared scratch and one launch per call, as before.
-struct WinoFilterJob { const float* w; float* u; int Cin, Cout, KQ, NT, nchunk, total, first, f44; };     // first: the job's first block; f44: F(4x4) order
-constexpr int WINO_JOBS_MAX = 24, WINO_FILTER_PER_BLOCK = 1024;
-struct WinoFilterJobs { WinoFilterJob j[WINO_JOBS_MAX]; int n, total; };                            // total: blocks
-
-__global__ void __launch_bounds__(256) wino_filter_batched_kernel(const WinoFilterJobs jobs) {
+__global__ void __launch_bounds__(256) wino_filter_batched_kernel(const FilterJobs<WinoFilterJob> jobs) {
     // block -> job: wave-uniform (scalar loads from the kernel arguments; a per-thread job index made the compiler copy the
     // whole table into scratch memory per thread)
     int k = 0;
@@ -133,117 +110,49 @@ __global__ void __launch_bounds__(256) wino_filter_batched_kernel(const WinoFilt
     float* const u = jobs.j[k].u;
     const int Cin = jobs.j[k].Cin, Cout = jobs.j[k].Cout, KQ = jobs.j[k].KQ, NT = jobs.j[k].NT, nchunk = jobs.j[k].nchunk;
     const int total = jobs.j[k].total, b0 = jobs.j[k].first;
-    const int F = 16 * KQ * NT;
-    if (jobs.j[k].f44) {
-#pragma unroll 1
-        for (int q = 0; q < WINO_FILTER_PER_BLOCK / 256; ++q) {
-            const int idx = ((int)blockIdx.x - b0) * WINO_FILTER_PER_BLOCK + q * 256 + (int)threadIdx.x;
-            if (idx >= total) break;
-            u[idx] = wino4_filter_value(w, Cin, Cout, KQ, NT, nchunk, idx);
-        }
-        return;
-    }
+    const bool f44 = jobs.j[k].f44;
 #pragma unroll 1
     for (int q = 0; q < WINO_FILTER_PER_BLOCK / 256; ++q) {
         const int idx = ((int)blockIdx.x - b0) * WINO_FILTER_PER_BLOCK + q * 256 + (int)threadIdx.x;
         if (idx >= total) break;
-        const int j = idx & 3, lane = (idx >> 2) & 63;
-        int r = idx >> 8;
-        const int f4 = r % (F / 4); r /= F / 4;
-        const int xi = r & 3; r >>= 2;
-        const int chunk = r % nchunk, pass = r / nchunk;
-        const int f = 4 * f4 + j;
-        const int nu = f / (4 * KQ * NT), ks = (f / NT) % (4 * KQ), cb = f % NT;
-        const int cin = pass * 16 * KQ + 16 * (ks >> 2) + 4 * (lane >> 4) + (ks & 3);
-        const int co = chunk * 16 * NT + 16 * cb + (lane & 15);
-        float val = 0.f;
-        if (cin < Cin && co < Cout) {
-            const float c0 = xi == 0 ? 1.f : (xi == 3 ? 0.f : .5f);
-            const float c1 = xi == 1 ? .5f : (xi == 2 ? -.5f : 0.f);
-            const float c2 = xi == 3 ? 1.f : (xi == 0 ? 0.f : .5f);
-            const size_t tap = (size_t)Cin * Cout;
-            const float* p = w + (size_t)cin * Cout + co;
-            float t[3];
-#pragma unroll
-            for (int b = 0; b < 3; ++b) t[b] = c0 * p[(0 * 3 + b) * tap] + c1 * p[(1 * 3 + b) * tap] + c2 * p[(2 * 3 + b) * tap];
-            val = nu == 0 ? t[0] : (nu == 1 ? .5f * (t[0] + t[1] + t[2]) : (nu == 2 ? .5f * (t[0] - t[1] + t[2]) : -t[2]));
-        }
-        u[idx] = val;
+        u[idx] = f44 ? wino4_filter_value(w, Cin, Cout, KQ, NT, nchunk, idx) : wino_filter_value(w, Cin, Cout, KQ, NT, nchunk, idx);
     }
 }
-
-struct WinoFilterEntry {
-    const float* w; int Cin, Cout, KQ, NT, nchunk; int total; int kind;       // kind: pass it was registered in (0 forward, 1 backward)
-    hipStream_t stream; float* u; bool fresh; int f44;
-};
-std::vector<WinoFilterEntry>& wino_entries() { static std::vector<WinoFilterEntry> v; return v; }
-int g_wino_pass_depth = 0, g_wino_pass_kind = 0;
-constexpr size_t WINO_ENTRIES_MAX = 512;
 
 // -> the transformed filter to use and whether it still has to be computed (by the caller, on s)
 float* wino_filter_lookup(hipStream_t s, const float* w, int Cin, int Cout, int KQ, int NT, int nchunk, int total, bool& need, int f44 = 0) {
     static const bool off = exp_env("DL4DS_WINO_NO_FILTER_CACHE") != nullptr;          // (A/B)
-    need = true;
-    if (g_wino_pass_depth <= 0 || off) return wino_scratch(s, (size_t)total);
-    auto& es = wino_entries();
-    for (auto& e : es)
-        if (e.w == w && e.Cin == Cin && e.Cout == Cout && e.KQ == KQ && e.NT == NT && e.nchunk == nchunk && e.stream == s && e.f44 == f44) {
-            need = !e.fresh;
-            e.fresh = true;                      // (the caller transforms it now if it was not)
-            return e.u;
-        }
-    if (es.size() >= WINO_ENTRIES_MAX) return wino_scratch(s, (size_t)total);
-    WinoFilterEntry e{w, Cin, Cout, KQ, NT, nchunk, total, g_wino_pass_kind, s, nullptr, true, f44};
-    HIP_CHECK(hipMalloc((void**)&e.u, (size_t)total * sizeof(float)));
-    es.push_back(e);
-    return e.u;
+    return wino_filters().lookup(s, w, WinoFilterKey{Cin, Cout, KQ, NT, nchunk, f44}, (size_t)total, need, !off);
 }
 
 }  // namespace
 
-WinoPassGuard::WinoPassGuard(int kind) : prev_kind(g_wino_pass_kind) { ++g_wino_pass_depth; g_wino_pass_kind = kind; }
-WinoPassGuard::~WinoPassGuard() { --g_wino_pass_depth; g_wino_pass_kind = prev_kind; }
-
-bool wino_pass_active(int& kind) { kind = g_wino_pass_kind; return g_wino_pass_depth > 0; }
-
-void wino_filters_invalidate(const float* lo, const float* hi) {
-    for (auto& e : wino_entries())
-        if (e.w >= lo && e.w < hi) e.fresh = false;
-    split_filters_invalidate(lo, hi);                      // (conv_split.hip: the six-term kernel's filter fragments follow the same life cycle)
+// The three entry points of Graph (ops.h): the Winograd filters, then the six-term kernel's fragments (conv_split.hip)
+void derived_filters_invalidate(const float* lo, const float* hi) {
+    wino_filters().invalidate(lo, hi);
+    split_filters_invalidate(lo, hi);
 }
 
-void wino_filters_release(const float* lo, const float* hi) {
+void derived_filters_release(const float* lo, const float* hi) {
     split_filters_release(lo, hi);
-    auto& es = wino_entries();
-    for (size_t i = 0; i < es.size();) {
-        if (es[i].w >= lo && es[i].w < hi) { (void)hipFree(es[i].u); es[i] = es.back(); es.pop_back(); }
-        else ++i;
-    }
+    wino_filters().release(lo, hi);
 }
 
-void wino_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind) {
-    WinoFilterJobs jobs;
-    jobs.n = 0; jobs.total = 0;
-    auto flush = [&]() {
-        if (!jobs.n) return;
-        ProfScope ps(s, "wino_filters", 0.0, 4.0 * jobs.total * WINO_FILTER_PER_BLOCK);
-        DL4DS_LAUNCH(wino_filter_batched_kernel, dim3(jobs.total), dim3(256), 0, s, jobs);
-        HIP_CHECK(hipGetLastError());
-        jobs.n = 0; jobs.total = 0;
-    };
-    for (auto& e : wino_entries()) {
-        if (e.fresh || e.kind != kind || e.stream != s || e.w < lo || e.w >= hi) continue;
-        if (jobs.n == WINO_JOBS_MAX) flush();
-        jobs.j[jobs.n++] = WinoFilterJob{e.w, e.u, e.Cin, e.Cout, e.KQ, e.NT, e.nchunk, e.total, jobs.total, e.f44};
-        jobs.total += cdiv(e.total, WINO_FILTER_PER_BLOCK);
-        e.fresh = true;
-    }
-    flush();
+void derived_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind) {
+    wino_filters().refresh(
+        s, lo, hi, kind,
+        [](const WinoFilterCache::Entry& e, WinoFilterJob& j) {
+            const WinoFilterKey& k = e.key;
+            j = WinoFilterJob{e.w, e.buf, k.Cin, k.Cout, k.KQ, k.NT, k.nchunk, (int)e.floats, 0, k.f44};
+            return cdiv(j.total, WINO_FILTER_PER_BLOCK);
+        },
+        [&](const FilterJobs<WinoFilterJob>& jobs) {
+            ProfScope ps(s, "wino_filters", 0.0, 4.0 * jobs.total * WINO_FILTER_PER_BLOCK);
+            DL4DS_LAUNCH(wino_filter_batched_kernel, dim3(jobs.total), dim3(256), 0, s, jobs);
+            HIP_CHECK(hipGetLastError());
+        });
     split_filters_refresh(s, lo, hi, kind);
 }
-
-namespace {
-}  // namespace
 
 // Winograd F(4x4, 3x3) (conv_wino4_kernel.h): the layers whose transformed filter fits the register file of one workgroup per CU --
 // cout chunks of 32 (NT = 2) with 48 or 32 input channels per pass.  Same contract as conv2d_wino_forward below, which tries this first.

@@ -13,6 +13,7 @@
 // slabs of each (cin chunk, cout chunk) pair in a fixed order (bitwise reproducible) and wino_wgrad_finish_kernel applies the row half
 // and the remaining sign, and writes / accumulates dW and db.  DL4DS_NO_WINOGRAD=1 or DL4DS_NO_WINOGRAD_WGRAD=1: direct kernels.
 #include "conv_wino_kernel.h"
+#include "conv_cache.h"
 
 namespace {
 
@@ -433,26 +434,7 @@ int wgrad_cu_count() {
     return n;
 }
 
-struct WgScratch { hipStream_t stream; float* buf; size_t floats; };
-float* wgrad_scratch(hipStream_t s, size_t floats) {       // grow-only, one buffer per stream (launches on a stream are ordered)
-    static std::mutex mu;
-    static std::vector<WgScratch> all;
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& e : all) {
-        if (e.stream != s) continue;
-        if (e.floats < floats) {
-            HIP_CHECK(hipStreamSynchronize(s));
-            HIP_CHECK(hipFree(e.buf));
-            HIP_CHECK(hipMalloc((void**)&e.buf, floats * sizeof(float)));
-            e.floats = floats;
-        }
-        return e.buf;
-    }
-    WgScratch e{s, nullptr, floats};
-    HIP_CHECK(hipMalloc((void**)&e.buf, e.floats * sizeof(float)));
-    all.push_back(e);
-    return e.buf;
-}
+float* wgrad_scratch(hipStream_t s, size_t floats) { static StreamScratch sc; return sc.get(s, floats); }
 
 template <int KQ, int NT>
 void launch_wgrad2(hipStream_t s, WinoWgradParams& wp, int SX) {

@@ -164,6 +164,14 @@ struct Graph {
     float* gp(int pid) const { return G + params[pid].offset; }
 };
 
+// does the backward pass c need d(loss)/d(tensor tid)?
+inline bool wants_grad(const Graph& g, int tid, const BwdCtx& c) {
+    const GTensor& t = g.tensors[tid];
+    // (a pass without parameter gradients -- the generator's adversarial gradient through the discriminator -- only needs the
+    //  tensors that depend on an input that takes a gradient: the conditioning branch of the discriminator is skipped)
+    return t.requires_grad && (!t.is_input || c.input_grads) && (c.param_grads || t.dep_grad_input || exp_env("DL4DS_NO_BWD_PRUNE") != nullptr);
+}
+
 // ---- op constructors (graph.hip)
 int g_conv2d(Graph& g, int in, int w, int b, int add, int KS, int Cout, int relu, int d2s);
 int g_conv2d_transpose(Graph& g, int in, int w, int KS, int stride, int Cout, int relu);

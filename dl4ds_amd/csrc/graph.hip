@@ -2,6 +2,7 @@
 #include "graph.h"
 #include <cstdlib>
 #include "prof.h"
+#include "conv_cache.h"
 #include <algorithm>
 #include <cstring>
 #include <cmath>
@@ -12,8 +13,8 @@ static void plan_grad_aliases(Graph& g);
 
 // ============================================================================================ Graph
 Graph::~Graph() {
-    if (W) wino_filters_release(W, W + n_params);
-    if (Wt) wino_filters_release(Wt, Wt + wt_floats);
+    if (W) derived_filters_release(W, W + n_params);
+    if (Wt) derived_filters_release(Wt, Wt + wt_floats);
     for (float* p : allocations) (void)hipFree(p);
     if (own_arena) {
         if (W) (void)hipFree(W);
@@ -229,10 +230,10 @@ void Graph::forward(int B, bool training) {
     prepare(B);
     wt_fresh = false;          // the filters may have been updated since the last backward pass
     // ... and so are the Winograd layers' transformed filters: all stale, those made from W re-made in one launch (conv_wino.hip)
-    WinoPassGuard wino_pass(0);
-    wino_filters_invalidate(W, W + n_params);
-    if (Wt) wino_filters_invalidate(Wt, Wt + wt_floats);
-    wino_filters_refresh(stream, W, W + n_params, 0);
+    GraphPassGuard graph_pass(0);
+    derived_filters_invalidate(W, W + n_params);
+    if (Wt) derived_filters_invalidate(Wt, Wt + wt_floats);
+    derived_filters_refresh(stream, W, W + n_params, 0);
     const bool sh = shared_groups > 1 && !op_shared.empty() && B % shared_groups == 0;
     for (size_t i = 0; i < ops.size(); ++i) {
         GOp* op = ops[i].get();
@@ -268,7 +269,7 @@ void Graph::refresh_dgrad_weights() {
     }
     conv2d_dgrad_weights_batched(stream, static_cast<const DgradWeightsJob*>(wt_jobs_dev), (int)wt_jobs.size(), wt_job_blocks);
     wt_fresh = true;
-    wino_filters_refresh(stream, Wt, Wt + wt_floats, 1);       // the dgrad layers' transformed filters, from the arrangements just made
+    derived_filters_refresh(stream, Wt, Wt + wt_floats, 1);       // the dgrad layers' transformed filters, from the arrangements just made
 }
 
 void Graph::zero_grad_flags() {
@@ -277,7 +278,7 @@ void Graph::zero_grad_flags() {
 }
 
 void Graph::backward(const BwdCtx& c) {
-    WinoPassGuard wino_pass(1);
+    GraphPassGuard graph_pass(1);
     refresh_dgrad_weights();
     for (auto& t : tensors) { t.grad_written = false; t.pending_add = nullptr; }
     for (int o : outputs) tensors[o].grad_written = true;      // seeded by the loss
@@ -322,13 +323,6 @@ void Graph::backward(const BwdCtx& c) {
 }
 
 namespace {
-
-inline bool wants_grad(const Graph& g, int tid, const BwdCtx& c) {
-    const GTensor& t = g.tensors[tid];
-    // (a pass without parameter gradients -- the generator's adversarial gradient through the discriminator -- only needs the
-    //  tensors that depend on an input that takes a gradient: the conditioning branch of the discriminator is skipped)
-    return t.requires_grad && (!t.is_input || c.input_grads) && (c.param_grads || t.dep_grad_input || exp_env("DL4DS_NO_BWD_PRUNE") != nullptr);
-}
 
 // ChannelAttention2D between two convolutions (ConvBlock(attention=True) followed by another conv: blocks.py:87-103,
 // sp_postups.py:204-211) costs three passes over the HR tensor when run as its own kernels.  Where the neighbouring

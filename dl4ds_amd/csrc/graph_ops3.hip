@@ -7,11 +7,6 @@
 
 namespace {
 
-inline bool wants_grad(const Graph& g, int tid, const BwdCtx& c) {
-    const GTensor& t = g.tensors[tid];
-    return t.requires_grad && (!t.is_input || c.input_grads) && (c.param_grads || t.dep_grad_input || exp_env("DL4DS_NO_BWD_PRUNE") != nullptr);
-}
-
 // ============================================================================================ LayerNorm / BatchNorm
 struct NormOp : GOp {
     int in, out, gamma, beta, mov_mean = -1, mov_var = -1;

@@ -54,15 +54,14 @@ bool conv2d_gemm_forward(hipStream_t s, const TView& in, const float* w, int KS,
 bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
 // the 40 / 48-channel 3x3 layers with their fp32 products as six bf16 MFMA terms (conv_split.hip); false = not eligible / DL4DS_NO_SPLIT
 bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
-// The transformed filters of a graph's Winograd layers, one batched launch per pass instead of one per layer (conv_wino.hip):
-// a pass of a graph holds a WinoPassGuard (kind 0 = forward, 1 = backward); _invalidate marks every registered filter inside
-// [lo, hi) stale, _refresh transforms the stale ones of that kind in one launch on s, _release frees them (graph destruction).
-struct WinoPassGuard { int prev_kind; explicit WinoPassGuard(int kind); ~WinoPassGuard(); WinoPassGuard(const WinoPassGuard&) = delete; };
-void wino_filters_invalidate(const float* lo, const float* hi);
-void wino_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind);
-void wino_filters_release(const float* lo, const float* hi);
-bool wino_pass_active(int& kind);                              // inside a graph pass? (kind: 0 forward, 1 backward)
-// conv_split.hip: the same three for the six-term kernel's filter fragments (called by the wino_filters_* functions)
+// The operands derived from the filters of a graph's layers -- the Winograd layers' transformed filters (conv_wino.hip), then the
+// six-term kernel's bf16 fragments (conv_split.hip) -- one batched launch each per pass instead of one per layer (conv_cache.h; a pass
+// of a graph holds a GraphPassGuard): _invalidate marks every registered filter inside [lo, hi) stale, _refresh rebuilds the stale
+// ones of that pass kind (0 = forward, 1 = backward) on s, _release frees them (graph destruction).
+void derived_filters_invalidate(const float* lo, const float* hi);
+void derived_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind);
+void derived_filters_release(const float* lo, const float* hi);
+// conv_split.hip: its share of the three (called by the derived_filters_* functions)
 void split_filters_invalidate(const float* lo, const float* hi);
 void split_filters_refresh(hipStream_t s, const float* lo, const float* hi, int kind);
 void split_filters_release(const float* lo, const float* hi);

@@ -255,6 +255,49 @@ def test_wide_model_through_the_winograd_kernels(monkeypatch, sx):
     assert_matches_reference(g_hip, ref, what='Winograd kernels')
 
 
+def test_winograd_filters_follow_the_weights(monkeypatch):
+    """The Winograd layers' transformed filters are made by one launch per pass for all the layers of a graph ('wino_filters', from
+    the second pass on: conv_wino.hip, conv_cache.h) and must never outlive the weights they were made from: after set_weights a
+    model gives the bits -- output and every gradient -- that a fresh model with those weights gives.  The model of the test above
+    (layers of 32, 48 and 64 channels: one and two channel passes).  The first pass transforms every filter with the per-layer
+    kernel, the second with the batched one: equal bits, i.e. the two launch forms share one transform."""
+    monkeypatch.setenv('DL4DS_WINO_FORCE', '1')
+    import dl4ds_amd.models as PM
+    from dl4ds_amd.training import SupervisedEngine
+    from tests.parity import kernel_tags
+    kind, cfg, xs = 'net_pin', dict(backbone_block='resnet', n_filters=16, n_blocks=4), (2, 32, 32, 2)
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal(xs).astype(np.float32)
+
+    def wino(tags):
+        return {t: n for t, n in tags.items() if t.startswith('conv_wino<')}
+
+    a = build_pair(kind, cfg, xs, None)[0]
+    y0, t0 = kernel_tags(lambda: a([x]))
+    y = rng.standard_normal(y0.shape).astype(np.float32)
+    assert wino(t0) and 'wino_filters' not in t0 and 'conv_split<3,3>' not in t0, sorted(t0)       # first pass: every layer transforms its own
+    y1, t1 = kernel_tags(lambda: a([x]))
+    assert wino(t1) == wino(t0) and t1.get('wino_filters') == 1, (t0, t1)                          # then one launch for all of them
+    assert np.array_equal(y0, y1)
+    eng = SupervisedEngine(a, loss='mae', learning_rate=1e-3)
+    eng.loss_and_grads([x], y)                                                                      # (the dgrad layers register their filters)
+    _, t2 = kernel_tags(lambda: eng.loss_and_grads([x], y))
+    assert t2.get('wino_filters') == 2, sorted(t2.items())      # the forward pass's launch + one for the dgrad filters (the Wt range, kind 1)
+
+    w2 = {k: (v * np.float32(0.75) + np.float32(0.01)).astype(np.float32) for k, v in a.get_weights().items()}
+    a.set_weights(w2)
+    y2 = a([x])
+    l2, g2 = eng.loss_and_grads([x], y)
+    b = PM.net_pin(n_channels=xs[-1], n_aux_channels=0, hr_size=xs[1:3], seed=33, **cfg)
+    b.set_weights(w2)
+    assert np.array_equal(y2, b([x]))
+    assert not np.array_equal(y2, y1)
+    lb, gb = SupervisedEngine(b, loss='mae', learning_rate=1e-3).loss_and_grads([x], y)
+    assert l2 == lb and set(g2) == set(gb)
+    for k in gb:                                  # (two fresh models agree bit for bit: every reduction has a fixed order)
+        assert np.array_equal(g2[k], gb[k]), k
+
+
 @pytest.mark.parametrize('n_aux', [0, 2])
 @pytest.mark.parametrize('ups,scale', [('spc', 4), ('spc', 2), ('rc', 2), ('spc', 5)])
 def test_folded_upsampling_tail_equals_unfolded(monkeypatch, ups, scale, n_aux):

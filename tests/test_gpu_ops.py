@@ -424,6 +424,36 @@ def test_conv2d_winograd_wgrad(ops, monkeypatch, sx, n, h, w, ci, co):
     close(got, gw)
 
 
+def test_conv_scratch_survives_growth(ops, monkeypatch):
+    """Outside a graph pass the convolutions keep their derived operands in a grow-only scratch buffer of the call's stream
+    (conv_cache.h: StreamScratch -- the Winograd kernels' transformed filter, the six-term kernel's fragments, the Winograd weight
+    gradient's slabs).  A call that needs more replaces the buffer, after the stream has drained, by a larger one: small, large,
+    small -- every result of the small shape is the same bits.  The largest shape of a sequence exceeds the buffer's first-allocation
+    minimum (2^20 floats of transformed filter, 2^18 of fragments; none for the slabs), so the buffer is replaced at least there."""
+    from tests.parity import kernel_tags
+
+    def sequence(call, tag, shapes):
+        data = {}
+        for n, h, w, ci, co in set(shapes):
+            data[n, h, w, ci, co] = (R(n, h, w, ci), R(3, 3, ci, co) * 0.2, R(co), R(n, h, w, co))
+        first = None
+        for k, shape in enumerate(shapes):
+            got, tags = kernel_tags(lambda: call(*data[shape]))
+            assert any(t.startswith(tag) for t in tags), (shape, tags)
+            if shape == shapes[0]:
+                first = got if first is None else first
+                assert np.array_equal(got, first), (tag, k)
+
+    small = (1, 16, 16, 24, 24)
+    monkeypatch.setenv('DL4DS_WINO_FORCE', 'all')
+    sequence(lambda x, wt, b, dz: ops.conv2d(x, wt, b), 'conv_wino<', [small, (2, 32, 32, 64, 64), small, (1, 16, 16, 288, 288), small])
+    sequence(lambda x, wt, b, dz: ops.conv2d_wgrad(x, dz, 3), 'conv_wino_wgrad<', [(5, 32, 16, 24, 24), (1, 35, 21, 48, 96), (5, 32, 16, 24, 24)])
+    monkeypatch.delenv('DL4DS_WINO_FORCE')
+    monkeypatch.setenv('DL4DS_SPLIT_FORCE', 'all')
+    small = (1, 16, 16, 48, 48)
+    sequence(lambda x, wt, b, dz: ops.conv2d(x, wt, b), 'conv_split<3,3>', [small, (2, 32, 32, 96, 96), small, (1, 16, 16, 144, 144), small])
+
+
 @pytest.mark.parametrize('ci,co', [(48, 192), (48, 32), (24, 32), (48, 96), (32, 128)])
 def test_conv2d_winograd_wgrad_depth_to_space(ops, monkeypatch, ci, co):
     """... with the output gradient read through a depth_to_space view (groups of 48, 8, 24 and 32 channels)."""
