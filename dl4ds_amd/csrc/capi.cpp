@@ -819,13 +819,8 @@ int dl4ds_graph_dropout_count(dl4ds_graph* g, int* n) {
 }
 int dl4ds_graph_dropout_reseed(dl4ds_graph* g, unsigned long long seed) {
     API_BEGIN
-    for (size_t i = 0; i < g->g.dropout_ops.size(); ++i) {
-        // splitmix64 of (seed, op index): neighbouring seeds and neighbouring ops get unrelated streams
-        unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(i + 1);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        g->g.dropout_ops[i]->reseed(z ^ (z >> 31));
-    }
+    // splitmix64 of (seed, op index): neighbouring seeds and neighbouring ops get unrelated streams
+    for (size_t i = 0; i < g->g.dropout_ops.size(); ++i) g->g.dropout_ops[i]->reseed(dropout_op_seed(seed, i));
     API_END
 }
 int dl4ds_graph_dropout_mc_count(dl4ds_graph* g, int* n) {

@@ -164,6 +164,23 @@ struct Graph {
     float* gp(int pid) const { return G + params[pid].offset; }
 };
 
+// Dropout noise seeds.  Op `index` (creation order) of a graph seeded with `seed` -- the built-in seed, or the one given to
+// dl4ds_graph_dropout_reseed -- draws from splitmix64(seed + GOLDEN * (index + 1)).  The hash is what keeps the ops apart:
+// dropout_mask_kernel hashes (op seed + GOLDEN * (element + 1)), so op seeds that differ by a multiple of GOLDEN (as the un-hashed
+// built-in seeds used to) make one op's mask the other's shifted by that many elements.
+// Draws of ONE op: its k-th drawing forward pass hashes (op seed + k * 0x1000003 + GOLDEN * (element + 1)) (DropoutOp::forward).  Two
+// draws k1 != k2 read the same numbers at an element shift s iff (k2 - k1) * 0x1000003 == GOLDEN * s (mod 2^64), i.e. at the ONE shift
+// s = (k2 - k1) * 0x1000003 * GOLDEN^-1.  For every distance below 2 000 000 draws |s| (as a signed 64-bit number) is at least
+// 8.9e12 elements (reached at distance 98 199; 1.9e14 below 65 536): no mask is that long, so the plain offset is kept and the
+// reseeded streams stay what they were.  tests/test_head_oracle.py recomputes the figure.
+constexpr unsigned long long DROPOUT_BUILTIN_SEED = 0x5DEECE66Dull;
+inline unsigned long long dropout_op_seed(unsigned long long seed, size_t index) {
+    unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (unsigned long long)(index + 1);
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // does the backward pass c need d(loss)/d(tensor tid)?
 inline bool wants_grad(const Graph& g, int tid, const BwdCtx& c) {
     const GTensor& t = g.tensors[tid];

@@ -336,7 +336,7 @@ struct DropoutOp : GOp {
               g.tensors[in].grad_written);
         g.tensors[in].grad_written = true;
     }
-    unsigned long long seed = 0x5DEECE66Dull;
+    unsigned long long seed = 0;       // dropout_op_seed(graph seed, op index): g_dropout, dl4ds_graph_dropout_reseed
     void reseed(unsigned long long s) override { seed = s; counter = 0; }
     bool mc_active() const override { return mc && rate > 0.f; }
 };
@@ -409,7 +409,7 @@ int g_dropout(Graph& g, int in, float rate, int variant, int mc, int spatial_dim
     const int out = g.add_tensor(ti.H, ti.W, ti.C, ti.nmul, true, false);
     DropoutOp* op = push<DropoutOp>(g);
     op->in = in; op->out = out; op->rate = rate; op->variant = variant; op->mc = mc != 0; op->spatial_dim = spatial_dim;
-    op->seed += 0x9E3779B97F4A7C15ull * (g.dropout_ops.size() + 1);
+    op->seed = dropout_op_seed(DROPOUT_BUILTIN_SEED, g.dropout_ops.size());
     g.tensors[in].n_other++;
     g.dropout_ops.push_back(op);
     op->out_tid = out; op->in_tids = {in};

@@ -531,7 +531,9 @@ class Model:
     # --- MC-dropout ensembles (the MC* dropout variants of blocks.py:658-676 stay active at inference)
     def reseed_dropout(self, seed):
         """Seed the dropout noise of this model's graph: the masks of the forward passes that follow (at a fixed batch size)
-        are a function of ``seed`` alone.  A model that is never reseeded keeps its built-in seeds."""
+        are a function of ``seed`` alone.  Dropout op i draws from splitmix64(seed + golden * (i + 1)), so the ops' streams (and those
+        of neighbouring seeds) are unrelated; the scheme is spelled out in include/dl4ds_hip.h.  A model that is never reseeded
+        draws as if it had been reseeded with the library's built-in seed: its ops get hashed seeds in the same way."""
         self.graph.reseed_dropout(seed)
 
     def predict_ensemble(self, inputs, n_members, batch_size=32, quantiles=(), seed=None, return_members=False):

@@ -468,7 +468,14 @@ int dl4ds_graph_dropout_get_mask(dl4ds_graph* g, int index, int B, float* dst_ho
 int dl4ds_graph_dropout_set_mask(dl4ds_graph* g, int index, int B, const float* src_host);
 /* reseed: every dropout op gets the seed mix(seed, op index) and its draw counter goes back to 0, so the masks drawn by the
  * forward passes that follow (fixed batch size) are a pure function of `seed`: a reproducible MC ensemble (blocks.py:658-676).
- * A graph that was never reseeded keeps its built-in seeds.  mc_count: dropout ops that are active at inference (mc != 0, rate > 0). */
+ * The scheme, all mod 2^64 with G = 0x9E3779B97F4A7C15 and splitmix64 the finaliser z ^= z >> 30, z *= 0xBF58476D1CE4E5B9,
+ * z ^= z >> 27, z *= 0x94D049BB133111EB, z ^= z >> 31:  op i (creation order) has the seed s_i = splitmix64(seed + G * (i + 1));
+ * element e of its k-th drawing forward pass (k = 1, 2, ...) takes z = splitmix64(s_i + k * 0x1000003 + G * (e + 1)),
+ * u = (z >> 40) / 2^24 and u2 = ((z >> 16) & 0xFFFFFF) / 2^24; the keep mask is 1 iff u >= rate (in fp32), the Gaussian noise
+ * 1 + sqrt(rate / (1 - rate)) * sqrt(-2 ln(1 - u)) * cos(2 pi u2).
+ * A graph that was never reseeded draws as if reseeded with the built-in seed 0x5DEECE66D: its ops' seeds are hashed the same
+ * way (they used to be 0x5DEECE66D + G * (i + 1) un-hashed, which made the mask of op i + 1 the mask of op i shifted by one
+ * element).  mc_count: dropout ops that are active at inference (mc != 0, rate > 0). */
 int dl4ds_graph_dropout_reseed(dl4ds_graph* g, unsigned long long seed);
 int dl4ds_graph_dropout_mc_count(dl4ds_graph* g, int* n);
 /* LayerNormalization(axis=-1) (batch == 0; mov_* ignored) / BatchNormalization(axis=-1, momentum=0.99) (batch != 0)
