@@ -286,6 +286,34 @@ int dl4ds_op_conv2d_epilogue(const float* x, const float* w, const float* b, con
     conv2d_forward(S(), make_view(nc(x), N, H, W, Cin), w, KS, make_view(y, N, H, W, Cout), ep);
     API_END
 }
+int dl4ds_op_conv2d_second_output(const float* x, const float* w, const float* b, const float* sum_add, float* sum_out, const float* mask,
+                                  const float* mask2, float* y2, float* partial, float* y, int N, int H, int W, int Cin, int Cout, int KS,
+                                  int relu, int* launched) {
+    API_BEGIN
+    DL4DS_REQUIRE(launched != nullptr, "conv2d_second_output: launched is null");
+    ConvEpilogue ep;
+    ep.bias = b;
+    ep.relu = relu;
+    if (sum_add) ep.sum_add = make_view(nc(sum_add), N, H, W, Cout);
+    if (sum_out) ep.sum_out = make_view(sum_out, N, H, W, Cout);
+    if (mask) ep.mask = make_view(nc(mask), N, H, W, Cout);
+    if (mask2) ep.mask2 = make_view(nc(mask2), N, H, W, Cout);
+    if (y2) ep.out2 = make_view(y2, N, H, W, Cout);
+    if (partial) ep.partial = make_view(partial, N, H, W, Cout);
+    *launched = conv2d_forward_fused(S(), make_view(nc(x), N, H, W, Cin), w, KS, make_view(y, N, H, W, Cout), ep) ? 1 : 0;
+    API_END
+}
+int dl4ds_op_add_act(const float* a, const float* b, float* out, size_t n, int relu) {
+    API_BEGIN
+    add_act(S(), a, b, out, n, relu);
+    API_END
+}
+int dl4ds_op_masked_axpy_pair(const float* dy, const float* ya, float* da, const float* yb, float* db, size_t n, int* launched) {
+    API_BEGIN
+    DL4DS_REQUIRE(launched != nullptr, "masked_axpy_pair: launched is null");
+    *launched = masked_axpy_pair(S(), dy, ya, da, 0, yb, db, 0, n) ? 1 : 0;
+    API_END
+}
 int dl4ds_op_conv2d_dgrad(const float* dz, const float* w, float* dx, int N, int H, int W, int Cin, int Cout, int KS,
                           int d2s_r, int accumulate) {
     API_BEGIN

@@ -1524,6 +1524,7 @@ void conv_splitk_combine(hipStream_t s, const float* slabs, int S, size_t slab_s
 void conv2d_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
                     const ConvEpilogue& ep) {
     DL4DS_REQUIRE(in.N == out.N && in.H == out.H && in.W == out.W, "conv2d: stride-1 SAME shapes differ");
+    DL4DS_REQUIRE(!ep.sum_out.p && !ep.out2.p, "conv2d: a second output pair goes through conv2d_forward_fused");
     if (conv2d_direct_forward(s, in, w, KS, out, ep)) return;      // a handful of channels: HBM-bound stencil
     if (!exp_env("DL4DS_NO_NARROW") && conv2d_narrow_forward(s, in, w, KS, out, ep)) return;
     DL4DS_REQUIRE(!in.sc && !ep.pool, "conv2d: channel-affine input / pooling partials are only implemented by the direct "
@@ -1551,6 +1552,18 @@ void conv2d_forward(hipStream_t s, const TView& in, const float* w, int KS, cons
         case 7: dispatch_fwd<7>(s, p, in.N); break;       // ConvNext stem / tail (sp_postups.py:121,205-210)
         default: throw Dl4dsError("conv2d: kernel size " + std::to_string(KS) + " not supported (1,3,5,7)");
     }
+}
+
+// conv2d_forward's choice among the kernels that have a second-output form, for the layers only they can get: 3x3 with at least 24
+// channels on both sides (the stencil and narrow kernels, which come first in conv2d_forward, stop at 16), no channel-affine input
+bool conv2d_forward_fused(hipStream_t s, const TView& in, const float* w, int KS, const TView& out, const ConvEpilogue& ep) {
+    DL4DS_REQUIRE(in.N == out.N && in.H == out.H && in.W == out.W, "conv2d: stride-1 SAME shapes differ");
+    DL4DS_REQUIRE((ep.sum_out.p != nullptr) != (ep.out2.p != nullptr), "conv2d_forward_fused: one second output pair");
+    if (KS != 3 || in.C < 24 || out.C < 24 || in.sc || ep.pool) return false;
+    bool refused = false;
+    if (conv2d_split_forward(s, in, w, out, ep, &refused)) return true;
+    if (refused) return false;
+    return conv2d_wino_forward(s, in, w, out, ep, &refused);
 }
 
 // the same map for large filters (deep U-Net levels: 25 x 256 x 1024): 32 x 32 tiles through LDS so that both the read

@@ -65,6 +65,9 @@ struct SplitParams {
     int nitems;             // per chunk: N * nsy * nsx
     int relu, old;          // old: the stored value is added -- 1: the earlier input-channel passes' partial sum (before bias / mask), 2: gradient accumulation (after)
     int final_pass;         // bias / residual / mask / ReLU only then
+    const float* sum_add;   // SUM form: the stored value plus this summand (laid out like the output) is stored a second time, to sum_out
+    float* sum_out;
+    size_t sum_add_ns, sum_out_ns;
     unsigned long long* trace;   // (development) [block][wave][4] cycle sums: MFMA phase, partial-sum write, barrier wait, rows
 };
 
@@ -182,8 +185,9 @@ __device__ __forceinline__ void split_fetch(const unsigned char* rb, int b1, int
 #define SPLIT_TRACE_START
 #define SPLIT_TRACE_END
 #endif
-// OLD / ADD / MASK: which epilogue operands exist (compiled apart: they stay in registers for a row)
-template <bool OLD, bool ADD, bool MASK>
+// OLD / ADD / MASK: which epilogue operands exist (compiled apart: they stay in registers for a row); SUM: the second output of
+// ConvEpilogue::sum_out
+template <bool OLD, bool ADD, bool MASK, bool SUM = false>
 __global__ void __launch_bounds__(NTHREADS) conv_split_kernel(const SplitParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned char* rowbuf = smem;                                           // [3][HPX][PIXB]: a ring -- the row in use, the next one (complete), the one being staged
@@ -246,13 +250,17 @@ __global__ void __launch_bounds__(NTHREADS) conv_split_kernel(const SplitParams 
                 const_cast<float*>(ADD ? p.add.p + (size_t)n * p.add.nstride : p.out.p), 0, 0x7fffff00, RSRC3);
             const __amdgpu_buffer_rsrc_t rs_mask = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float*>(MASK ? p.mask.p + (size_t)n * p.mask.nstride : p.out.p), 0, 0x7fffff00, RSRC3);
-            i32x4 ov = {0, 0, 0, 0}, av = {0, 0, 0, 0}, mv = {0, 0, 0, 0};
+            const __amdgpu_buffer_rsrc_t rs_sadd = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<float*>(SUM ? p.sum_add + (size_t)n * p.sum_add_ns : p.out.p), 0, 0x7fffff00, RSRC3);
+            const __amdgpu_buffer_rsrc_t rs_sout = __builtin_amdgcn_make_buffer_rsrc(SUM ? p.sum_out + (size_t)n * p.sum_out_ns : p.out.p, 0, 0x7fffff00, RSRC3);
+            i32x4 ov = {0, 0, 0, 0}, av = {0, 0, 0, 0}, mv = {0, 0, 0, 0}, sv = {0, 0, 0, 0};
             // the epilogue's operands for output row yo, requested one row ahead of their use
             auto request = [&](int yo) __attribute__((always_inline)) {
                 const int eoff = (yo >= y_lo && yo < y_hi && ooff != OOB) ? 0 : OOB;     // (one select; the operands' offsets are added to it)
                 if constexpr (OLD) ov = __builtin_amdgcn_raw_buffer_load_b128(rs_out, (eoff | ooff) + (eoff == 0 ? yo * out_ys : 0), 0, 0);
                 if constexpr (ADD) av = __builtin_amdgcn_raw_buffer_load_b128(rs_add, (eoff | aoff) + (eoff == 0 ? yo * add_ys : 0), 0, 0);
                 if constexpr (MASK) mv = __builtin_amdgcn_raw_buffer_load_b128(rs_mask, (eoff | moff) + (eoff == 0 ? yo * mask_ys : 0), 0, 0);
+                if constexpr (SUM) sv = __builtin_amdgcn_raw_buffer_load_b128(rs_sadd, (eoff | ooff) + (eoff == 0 ? yo * out_ys : 0), 0, 0);   // (the output's layout)
             };
             // output row yo from the five per-wave partial sums of every channel tile in red[buf]
             auto finish = [&](int yo, int buf) __attribute__((always_inline)) {
@@ -281,6 +289,13 @@ __global__ void __launch_bounds__(NTHREADS) conv_split_kernel(const SplitParams 
                 i32x4 vi;
                 __builtin_memcpy(&vi, &v, 16);
                 __builtin_amdgcn_raw_buffer_store_b128(vi, rs_out, (eoff | ooff) + (eoff == 0 ? yo * out_ys : 0), 0, 0);
+                if constexpr (SUM) {                                  // (one fp32 addition per element, as add_act_kernel does it)
+                    float4 sa;
+                    __builtin_memcpy(&sa, &sv, 16);
+                    const float4 t = make_float4(sa.x + v.x, sa.y + v.y, sa.z + v.z, sa.w + v.w);
+                    __builtin_memcpy(&vi, &t, 16);
+                    __builtin_amdgcn_raw_buffer_store_b128(vi, rs_sout, (eoff | ooff) + (eoff == 0 ? yo * out_ys : 0), 0, 0);
+                }
             };
             f32x4 acc[3][2];
 #pragma unroll
@@ -464,18 +479,19 @@ __global__ void __launch_bounds__(NTHREADS) conv_split_kernel(const SplitParams 
     SPLIT_TRACE_END;
 }
 
-template <bool OLD, bool ADD, bool MASK>
+template <bool OLD, bool ADD, bool MASK, bool SUM = false>
 void launch_one(hipStream_t s, const SplitParams& p, int grid) {
     static bool once = false;
     if (!once) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<OLD, ADD, MASK>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(conv_split_kernel<OLD, ADD, MASK, SUM>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)LDS_BYTES));
         once = true;
     }
-    DL4DS_LAUNCH((conv_split_kernel<OLD, ADD, MASK>), dim3(grid), dim3(NTHREADS), LDS_BYTES, s, p);
+    DL4DS_LAUNCH((conv_split_kernel<OLD, ADD, MASK, SUM>), dim3(grid), dim3(NTHREADS), LDS_BYTES, s, p);
     HIP_CHECK(hipGetLastError());
 }
 void launch_form(hipStream_t s, const SplitParams& p, int grid) {
+    if (p.sum_out) { launch_one<false, false, false, true>(s, p, grid); return; }     // (the one form with a second output: conv2d_split_forward)
     const int f = (p.old ? 4 : 0) | (p.add.p ? 2 : 0) | (p.mask.p ? 1 : 0);
     switch (f) {
         case 0: launch_one<false, false, false>(s, p, grid); break;
@@ -531,7 +547,7 @@ void split_filters_refresh(hipStream_t s, const float* lo, const float* hi, int 
         });
 }
 
-bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep) {
+bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep, bool* form_refused) {
     // Measured (round 6, profiles/conv_split_r06.txt): 10 % faster than the Winograd F(2x2,3x3) kernels on the fp32 pipe for the layers with
     // ONE pass of <= 48 input channels and <= 48 output channels (0.199 vs 0.21-0.23 ms at 64 x 128^2), slower for 48 -> 192 / 192 -> 48
     // (0.76 / 0.83 vs 0.74 / 0.84).  So: ON by default for the former (cfg2: eight of the ten <3,3> layers, 5 075 -> 5 175 samples/s in
@@ -571,10 +587,23 @@ bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const 
     if (items >= (1l << 24) || (!force && items * p.nchunk < (long)cu_count())) return false;
     p.nitems = (int)items;
     p.relu = ep.relu;
+    p.sum_add = nullptr; p.sum_out = nullptr; p.sum_add_ns = p.sum_out_ns = 0;
+    if (ep.sum_out.p || ep.out2.p) {
+        // this kernel takes the layer: a second-output form it does not have is refused, not handed to another kernel (ops.h).  It has
+        // the sum behind a single pass without residual, mask or accumulation.
+        auto like_out = [&](const TView& v) { return v.p && v.vec && v.N == out.N && v.H == out.H && v.C == out.C && v.ld == out.ld && v.d2s == out.d2s && v.W == out.W && v.cp == out.cp; };
+        if (ep.out2.p || passes > 1 || ep.add.p || ep.mask.p || ep.accumulate || !like_out(ep.sum_add) || !like_out(ep.sum_out) ||
+            span(ep.sum_add) >= (1ull << 31) || span(ep.sum_out) >= (1ull << 31)) {
+            if (form_refused) *form_refused = true;
+            return false;
+        }
+        p.sum_add = ep.sum_add.p; p.sum_out = ep.sum_out.p;
+        p.sum_add_ns = ep.sum_add.nstride; p.sum_out_ns = ep.sum_out.nstride;
+    }
     const double px = (double)in.N * in.H * in.W;
     const double fl = 2.0 * px * 9.0 * in.C * out.C;
     ProfScope ps(s, std::string("conv_split<3,3>") + (test_env("DL4DS_SPLIT_TAG_FORMS") ? std::string("f") + std::to_string((ep.accumulate ? 4 : 0) | (ep.add.p ? 2 : 0) | (ep.mask.p ? 1 : 0)) + "c" + std::to_string(in.C) + "_" + std::to_string(out.C) : std::string()), fl,
-                 4.0 * (px * (in.C + out.C * (1 + (ep.add.p ? 1 : 0) + (ep.mask.p ? 1 : 0) + (ep.accumulate ? 1 : 0))) + 9.0 * in.C * out.C), fl);
+                 4.0 * (px * (in.C + out.C * (1 + (ep.add.p ? 1 : 0) + (ep.mask.p ? 1 : 0) + (ep.accumulate ? 1 : 0) + (ep.sum_out.p ? 2 : 0))) + 9.0 * in.C * out.C), fl);
     const int per_pass = p.nchunk * (NMW + NHW) * 12 * 64;                  // uint4 entries
     bool need_frag = true;
     u32x4* frag = reinterpret_cast<u32x4*>(

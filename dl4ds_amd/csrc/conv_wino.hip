@@ -216,7 +216,7 @@ static bool conv2d_wino4_forward(hipStream_t s, const TView& in, const float* w,
 }
 
 // 3x3, stride 1, SAME.  Returns false when the layer is not eligible (the caller falls through to the direct kernels).
-bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep) {
+bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep, bool* form_refused) {
     const bool off = getenv("DL4DS_NO_WINOGRAD") != nullptr;
     const char* force = test_env("DL4DS_WINO_FORCE");          // (tests: small grids too; "<k>" = k workgroups per XCD and cout chunk)
     if (off) return false;
@@ -227,6 +227,13 @@ bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const T
     auto same_layout = [](const TView& u, const TView& v) { return u.ld == v.ld && u.d2s == v.d2s && u.W == v.W && u.cp == v.cp; };
     if (ep.add.p && !same_layout(ep.add, out)) return false;
     if (ep.mask.p && !same_layout(ep.mask, out)) return false;
+    // second output pair (ops.h): the summand and the sum, or the second mask and gradient (+ the partial sums), laid out like the output
+    const bool dual = ep.out2.p != nullptr, sum = ep.sum_out.p != nullptr;
+    const bool second = dual || sum;
+    auto like_out = [&](const TView& v) { return v.p && v.vec && v.N == out.N && v.H == out.H && v.C == out.C && same_layout(v, out); };
+    bool second_ok = !(dual && sum) && !(second && (ep.accumulate || out.d2s > 1));
+    if (sum) second_ok = second_ok && like_out(ep.sum_add) && like_out(ep.sum_out) && !ep.add.p && !ep.mask.p;
+    if (dual) second_ok = second_ok && like_out(ep.mask2) && like_out(ep.out2) && ep.mask.p && !ep.add.p && ep.out2.p != out.p;
     auto span = [](const TView& v) { const size_t r = std::max(v.d2s, 1); return (size_t)8 * v.W * r * r * v.ld * 4; };
     if (span(in) >= (1ull << 31) || span(out) >= (1ull << 31)) return false;
     // channel passes
@@ -238,11 +245,14 @@ bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const T
     else return false;
     const int passes = cdiv(in.C, cpass);
     if (passes > 1 && ep.accumulate) return false;
-    const int full_epi = (ep.add.p ? WINO_ADD : 0) | (ep.mask.p ? WINO_MASK : 0) | (ep.accumulate ? WINO_OLDA : 0);
-    if (!wino_epi_built(full_epi) || (passes > 1 && !wino_epi_built(full_epi | WINO_OLDF))) return false;
-    if (test_env("DL4DS_WINO_F44") && conv2d_wino4_forward(s, in, w, out, ep, KQ, cpass, force)) return true;
+    // (the plain forms: what decides whether this kernel takes the layer; the second-output forms are checked once it does)
+    const int plain_epi = (ep.add.p ? WINO_ADD : 0) | (ep.mask.p ? WINO_MASK : 0) | (ep.accumulate ? WINO_OLDA : 0);
+    const int full_epi = plain_epi | (dual ? WINO_MASK2 : 0) | (sum ? WINO_SUM : 0);
+    if (!wino_epi_built(plain_epi) || (passes > 1 && !wino_epi_built(plain_epi | WINO_OLDF))) return false;
+    if (!second && test_env("DL4DS_WINO_F44") && conv2d_wino4_forward(s, in, w, out, ep, KQ, cpass, force)) return true;
     // cout chunks of 32 or 48: the least padding, then the wider chunk (the input transform is paid once per chunk)
     const int NT = (cdiv(out.C, 32) * 32 < cdiv(out.C, 48) * 48) ? 2 : 3;
+    auto refuse_form = [&]() { if (form_refused) *form_refused = true; return false; };
     WinoParams wp;
     ConvParams& p = wp.c;
     p.in = in; p.out = out; p.add = ep.add; p.mask = ep.mask;
@@ -263,12 +273,23 @@ bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const T
     int SX = (SXmax / wp.nchunk) * wp.nchunk;
     if (force && atoi(force) > 0) SX = std::min(SX, atoi(force) * wp.nchunk);
     if (!force && (long)wp.per_xcd * wp.nchunk < 4l * SX) return false;       // fewer than four tile groups per workgroup
+    if (second) {
+        // this kernel takes the layer: from here on a form it cannot run is refused, not handed to another kernel
+        if (!second_ok || test_env("DL4DS_WINO_F44") || !wino_epi_built(full_epi | (passes > 1 ? WINO_OLDF : 0), KQ, NT)) return refuse_form();
+        if (dual && passes > 1 && !(like_out(ep.partial) && ep.partial.p != out.p && ep.partial.p != ep.out2.p)) return refuse_form();
+        wp.x2 = dual ? ep.mask2.p : ep.sum_add.p;
+        wp.x2_ns = dual ? ep.mask2.nstride : ep.sum_add.nstride;
+        wp.o2 = dual ? ep.out2.p : ep.sum_out.p;
+        wp.o2_ns = dual ? ep.out2.nstride : ep.sum_out.nstride;
+        wp.old = ep.partial.p;
+        wp.old_ns = ep.partial.nstride;
+    }
     const double px = (double)in.N * in.H * in.W;
     // (issued work: 16 multiply-adds per 2x2 tile and (cin, cout) pair of the padded operands, plus the transforms' additions)
     const double issued = 2.0 * (px / 4.0) * 16.0 * (16.0 * KQ * passes) * (16.0 * NT * wp.nchunk) +
                           (px / 4.0) * (32.0 * in.C * wp.nchunk + 24.0 * out.C * passes);
     ProfScope ps(s, "conv_wino<" + std::to_string(KQ) + "," + std::to_string(NT) + ">", issued,
-                 4.0 * (px * (in.C + out.C * (1 + (ep.add.p ? 1 : 0) + (ep.mask.p ? 1 : 0) + (ep.accumulate ? 1 : 0))) + 9.0 * in.C * out.C),
+                 4.0 * (px * (in.C + out.C * (1 + (ep.add.p ? 1 : 0) + (ep.mask.p ? 1 : 0) + (ep.accumulate ? 1 : 0) + (second ? 2 : 0))) + 9.0 * in.C * out.C),
                  2.0 * px * 9.0 * in.C * out.C);
     const size_t per_pass = (size_t)wp.nchunk * 4 * (16 * KQ * NT) * 64;
     const int total = (int)(per_pass * passes);
@@ -286,6 +307,8 @@ bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const T
         wp.first = ps_ == 0;
         p.relu = last ? ep.relu : 0;
         const int epi = passes == 1 ? full_epi : ((ps_ ? WINO_OLDF : 0) | (last ? full_epi : 0));
+        // two masked outputs: the earlier passes accumulate raw sums in `partial`, the last one reads them there (wp.old)
+        if (dual && passes > 1) p.out = last ? out : ep.partial;
         if (KQ == 2) {
             if (NT == 2) launch_wino_22(s, wp, SX, epi); else launch_wino_23(s, wp, SX, epi);
         } else {

@@ -49,6 +49,12 @@ struct WinoParams {
     int ntg, per_xcd;       // tile groups, and how many of them each XCD walks (a contiguous range)
     int tgx, tgy;           // tile groups per image row / column
     unsigned m_tgx, m_tgy;
+    // second output pair (WINO_SUM / WINO_MASK2; laid out like the output): x2 = the summand / the second mask, o2 = the second
+    // output, old = where a WINO_MASK2 pass finds the earlier passes' partial sums (its own outputs are the two masked gradients)
+    const float* x2 = nullptr;
+    float* o2 = nullptr;
+    const float* old = nullptr;
+    size_t x2_ns = 0, o2_ns = 0, old_ns = 0;
 #ifdef WINO_TRACE
     unsigned long long* trace;   // diagnostics build: [workgroup][wave][8] shader cycles per phase + iterations
 #endif
@@ -60,8 +66,15 @@ enum : int {
     WINO_ADD = 2,           // residual
     WINO_MASK = 4,          // result zeroed where mask <= 0 (ReLU backward)
     WINO_OLDA = 8,          // the stored value is added AFTER them (gradient accumulation)
+    WINO_MASK2 = 16,        // with WINO_MASK: the unmasked result is stored a second time, to o2, zeroed where x2 <= 0; WINO_OLDF then reads
+                            // the partial sums from `old` (an Add's backward over two ReLU outputs, ConvEpilogue::out2)
+    WINO_SUM = 32,          // the stored value plus x2 is stored a second time, to o2 (an Add behind this layer, ConvEpilogue::sum_out)
 };
-inline bool wino_epi_built(int e) { return e == 0 || e == 1 || e == 2 || e == 3 || e == 4 || e == 5 || e == 8 || e == 12; }
+// (the second-output forms exist for the <3,3> shape only: the 48-channel layers around the backbone's long skip)
+inline bool wino_epi_built(int e, int KQ = 0, int NT = 0) {
+    if (e == 20 || e == 21 || e == 32) return KQ == 3 && NT == 3;
+    return e == 0 || e == 1 || e == 2 || e == 3 || e == 4 || e == 5 || e == 8 || e == 12;
+}
 
 // one entry point per shape (conv_wino_<KQ><NT>.hip)
 void launch_wino_22(hipStream_t s, WinoParams& wp, int SX, int epi);
@@ -174,6 +187,8 @@ __global__ void __launch_bounds__(256, 2) conv_wino2_kernel(const WinoParams wp)
     constexpr int OOB = (int)0xffffff00u;
     constexpr int RSRC3 = 0x00020000;
     constexpr bool OLDF = (EPI & WINO_OLDF) != 0, ADD = (EPI & WINO_ADD) != 0, MASK = (EPI & WINO_MASK) != 0, OLDA = (EPI & WINO_OLDA) != 0;
+    constexpr bool DUAL = (EPI & WINO_MASK2) != 0, SUM = (EPI & WINO_SUM) != 0, X2 = DUAL || SUM;
+    static_assert(!(DUAL && SUM) && (!DUAL || MASK) && !(X2 && OLDA), "second-output forms");
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const raw = lds;                                         // two buffers of RAWS slots
     float* const Pb = lds + 2 * GM::RAWS * 4;
@@ -454,11 +469,24 @@ __global__ void __launch_bounds__(256, 2) conv_wino2_kernel(const WinoParams wp)
             const size_t pb_ = cur.y0 * osy + cur.x0 * osx;
             const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc(
                 reinterpret_cast<char*>(a.out.p) + ((size_t)cur.n * a.out.nstride + pb_) * 4, 0, 0x7fffff00, RSRC3);
-            i32x4_t e_old[(OLDF || OLDA) ? ND : 1], e_add[ADD ? ND : 1], e_mask[MASK ? ND : 1];
-            if (OLDF || OLDA) {
+            i32x4_t e_old[(OLDF || OLDA) ? ND : 1], e_add[ADD ? ND : 1], e_mask[MASK ? ND : 1], e_x2[X2 ? ND : 1];
+            if (OLDF && DUAL) {
+                const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<char*>(reinterpret_cast<const char*>(wp.old)) + ((size_t)cur.n * wp.old_ns + pb_) * 4, 0, 0x7fffff00, RSRC3);
+#pragma unroll
+                for (int u = 0; u < ND; ++u) e_old[u] = __builtin_amdgcn_raw_buffer_load_b128(rp, dv[u], 0, 0);
+            } else if (OLDF || OLDA) {
 #pragma unroll
                 for (int u = 0; u < ND; ++u) e_old[u] = __builtin_amdgcn_raw_buffer_load_b128(ro, dv[u], 0, 0);
             }
+            if (X2) {
+                const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+                    const_cast<char*>(reinterpret_cast<const char*>(wp.x2)) + ((size_t)cur.n * wp.x2_ns + pb_) * 4, 0, 0x7fffff00, RSRC3);
+#pragma unroll
+                for (int u = 0; u < ND; ++u) e_x2[u] = __builtin_amdgcn_raw_buffer_load_b128(rx, dv[u], 0, 0);
+            }
+            const __amdgpu_buffer_rsrc_t ro2 = __builtin_amdgcn_make_buffer_rsrc(
+                reinterpret_cast<char*>(X2 ? wp.o2 : a.out.p) + ((size_t)cur.n * (X2 ? wp.o2_ns : a.out.nstride) + pb_) * 4, 0, 0x7fffff00, RSRC3);
             if (ADD) {
                 const __amdgpu_buffer_rsrc_t ra_ = __builtin_amdgcn_make_buffer_rsrc(
                     reinterpret_cast<char*>(a.add.p) + ((size_t)cur.n * a.add.nstride + pb_) * 4, 0, 0x7fffff00, RSRC3);
@@ -483,6 +511,19 @@ __global__ void __launch_bounds__(256, 2) conv_wino2_kernel(const WinoParams wp)
                 if (OLDF) r = add4(r, __builtin_bit_cast(f32x4, e_old[u]));
                 if (ADD) r = add4(r, __builtin_bit_cast(f32x4, e_add[u]));
                 r[0] = fmaxf(r[0], floor_v); r[1] = fmaxf(r[1], floor_v); r[2] = fmaxf(r[2], floor_v); r[3] = fmaxf(r[3], floor_v);
+                if (DUAL) {
+                    const f32x4 m = __builtin_bit_cast(f32x4, e_x2[u]);
+                    f32x4 r2;
+                    r2[0] = m[0] > 0.f ? r[0] : 0.f; r2[1] = m[1] > 0.f ? r[1] : 0.f;
+                    r2[2] = m[2] > 0.f ? r[2] : 0.f; r2[3] = m[3] > 0.f ? r[3] : 0.f;
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, r2), ro2, dv[u], 0, 0);
+                }
+                if (SUM) {                                            // (one fp32 addition per element, as add_act_kernel does it)
+                    const f32x4 sv = __builtin_bit_cast(f32x4, e_x2[u]);
+                    f32x4 r2;
+                    r2[0] = sv[0] + r[0]; r2[1] = sv[1] + r[1]; r2[2] = sv[2] + r[2]; r2[3] = sv[3] + r[3];
+                    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4_t, r2), ro2, dv[u], 0, 0);
+                }
                 if (MASK) {
                     const f32x4 m = __builtin_bit_cast(f32x4, e_mask[u]);
                     r[0] = m[0] > 0.f ? r[0] : 0.f; r[1] = m[1] > 0.f ? r[1] : 0.f;
@@ -572,6 +613,14 @@ void launch_shape(hipStream_t s, WinoParams& wp, int SX, int epi) {
         case 5: launch_one<KQ, NT, 5>(s, wp, SX); break;
         case 8: launch_one<KQ, NT, 8>(s, wp, SX); break;
         case 12: launch_one<KQ, NT, 12>(s, wp, SX); break;
+        case 20: case 21: case 32:
+            if constexpr (KQ == 3 && NT == 3) {
+                if (epi == 20) launch_one<KQ, NT, 20>(s, wp, SX);
+                else if (epi == 21) launch_one<KQ, NT, 21>(s, wp, SX);
+                else launch_one<KQ, NT, 32>(s, wp, SX);
+                break;
+            }
+            [[fallthrough]];
         default: throw Dl4dsError("conv_wino: epilogue form " + std::to_string(epi) + " is not built");
     }
 }

@@ -46,6 +46,9 @@ struct GTensor {
     // ReLU backward fused into the writers: every consumer is a Conv2D (or an Add), whose dgrad epilogue zeroes the gradient
     // where this activation is <= 0 (the mask is linear, so each accumulating writer applies it independently)
     bool grad_masked = false;
+    // output of an Add of two ReLU outputs, during a backward pass: the dgrad of its one consumer has stored both operands' masked
+    // gradients itself (AddOp::plan_long_skip); this tensor's gradient buffer then holds raw partial sums only
+    bool add_grads_done = false;
     size_t per_sample() const { return (size_t)nmul * H * W * C; }
 };
 

@@ -280,7 +280,7 @@ void Graph::zero_grad_flags() {
 void Graph::backward(const BwdCtx& c) {
     GraphPassGuard graph_pass(1);
     refresh_dgrad_weights();
-    for (auto& t : tensors) { t.grad_written = false; t.pending_add = nullptr; }
+    for (auto& t : tensors) { t.grad_written = false; t.pending_add = nullptr; t.add_grads_done = false; }
     for (int o : outputs) tensors[o].grad_written = true;      // seeded by the loss
     const bool bucketed = c.param_grads && grad_ready != nullptr && !buckets.empty();
     std::vector<char> sent(bucketed ? buckets.size() : 0, 0);
@@ -351,6 +351,14 @@ struct ConvOp : GOp {
     bool add_grad_shared = false;   // the residual operand's gradient IS this op's (masked) output gradient: no copy
     AttFusion* att_after = nullptr;    // a ChannelAttention2D consumes this op's output (this op = its producer)
     AttFusion* att_before = nullptr;   // this op convolves the output of a ChannelAttention2D (this op = its consumer)
+    // The long skip `s + this layer's output` (AddOp::plan_long_skip; both reset and set there, on every prepare):
+    //   sum_add >= 0: this layer's output feeds only that Add; the Add's forward launches this convolution with the sum as a second
+    //   output (ConvEpilogue::sum_out), this op's own forward launches nothing;
+    //   dual_a / dual_b >= 0: this layer convolves the output of an Add of two ReLU outputs and nothing else reads it; its dgrad
+    //   stores both operands' masked gradients (ConvEpilogue::out2) and the Add's backward has nothing left to do.
+    int sum_add = -1, sum_out = -1, dual_a = -1, dual_b = -1;
+    // (not under a shared sub-graph: its forward copies and backward sums work on whole tensors at the ops' own positions)
+    static bool long_skip_active(const Graph& g) { return !(g.shared_groups > 1 && !g.op_shared.empty()); }
     ConvOp() { kind = "conv2d"; }
     // the convolved input: the tensor itself, or -- behind a fused attention -- the attention's INPUT seen through its scale
     TView in_view(Graph& g, int B, int bo, int bc) {
@@ -452,12 +460,29 @@ struct ConvOp : GOp {
         return make_view(base, N, ti.H, ti.W, Cout);
     }
     void forward(Graph& g, int B, bool) override {
+        if (sum_add >= 0 && long_skip_active(g)) return;           // (launched by the Add that consumes the output: forward_with_sum)
+        launch_forward(g, B, false);
+    }
+    bool launch_forward(Graph& g, int B, bool with_sum) {
         ConvEpilogue ep;
         ep.bias = (b >= 0) ? g.wp(b) : nullptr;
         if (add >= 0) ep.add = g.view(add, B, false);
         ep.relu = relu;
         if (att_after && att_after->fuse_pool) ep.pool = att_after->pool;
+        if (with_sum) {
+            ep.sum_add = g.view(sum_add, B, false);
+            ep.sum_out = g.view(sum_out, B, false);
+            return conv2d_forward_fused(g.stream, in_view(g, B, 0, -1), g.wp(w), KS, out_view(g, false, B, 0, -1), ep);
+        }
         conv2d_forward(g.stream, in_view(g, B, 0, -1), g.wp(w), KS, out_view(g, false, B, 0, -1), ep);
+        return true;
+    }
+    // out = act(conv) and the Add's s + out in one launch; false: the kernel this layer runs on has no such form -- the plain
+    // convolution was launched, the caller adds
+    bool forward_with_sum(Graph& g, int B) {
+        if (launch_forward(g, B, true)) return true;
+        launch_forward(g, B, false);
+        return false;
     }
     size_t workspace_bytes(Graph& g, int B) override {
         TView x = g.view(in, B, false);
@@ -541,7 +566,28 @@ struct ConvOp : GOp {
                 ep.add = g.tensors[in].pending_view;       // (its own pixel pitch: dZ may live inside a Concatenate's gradient buffer)
                 g.tensors[in].pending_add = nullptr;
             }
-            conv2d_forward(g.stream, dY, wt, KS, g.view(in, c.B, true, c.b_off, c.b_cnt), ep);
+            bool done = false;
+            if (dual_a >= 0 && long_skip_active(g) && !ep.accumulate && !ep.mask.p && !ep.add.p && !dY.sc && wants_grad(g, dual_a, c) &&
+                wants_grad(g, dual_b, c)) {
+                GTensor& ta = g.tensors[dual_a];
+                GTensor& tb = g.tensors[dual_b];
+                if (ta.grad_masked && tb.grad_masked && !ta.grad_written && !tb.grad_written) {
+                    // dX never leaves the kernel unmasked: both operands' gradients from the last pass over the input channels, the
+                    // earlier passes' partial sums in this tensor's own gradient buffer
+                    ep.mask = g.view(dual_a, c.B, false, c.b_off, c.b_cnt);
+                    ep.mask2 = g.view(dual_b, c.B, false, c.b_off, c.b_cnt);
+                    ep.out2 = g.view(dual_b, c.B, true, c.b_off, c.b_cnt);
+                    ep.partial = g.view(in, c.B, true, c.b_off, c.b_cnt);
+                    done = conv2d_forward_fused(g.stream, dY, wt, KS, g.view(dual_a, c.B, true, c.b_off, c.b_cnt), ep);
+                    if (done) {
+                        ta.grad_written = tb.grad_written = true;
+                        g.tensors[in].add_grads_done = true;
+                    } else {
+                        ep = ConvEpilogue();                      // (the kernel of this layer has no such form: the Add's own pass)
+                    }
+                }
+            }
+            if (!done) conv2d_forward(g.stream, dY, wt, KS, g.view(in, c.B, true, c.b_off, c.b_cnt), ep);
             g.tensors[in].grad_written = true;
         }
     }
@@ -774,12 +820,57 @@ struct ConcatOp : GOp {
 struct AddOp : GOp {
     int a, b, out, relu;
     AddOp() { kind = "add"; }
+    // The long skip of the residual backbone, out = relu(1x1(stem)) + relu(3x3(b)), without its two element-wise passes (cfg2: 603 MB
+    // forward, 1 005 MB backward per step): the 3x3 convolution that produces operand b (or a) writes the sum as a second output, and
+    // the dgrad of the output's one consumer stores both operands' masked gradients.  Every value is the one the stand-alone passes
+    // write (add_act / masked_axpy_pair stay the fall-back where a layer's kernel has no such form); no stored tensor goes away.
+    // The producing convolution is LAUNCHED from this op's forward: its output has no other reader, the other operand may be made
+    // after it in op order (it is in net_postupsampling: backbone_last, then TransitionSkip), and the op list itself stays as built.
+    // DL4DS_NO_LONG_SKIP_FUSION (test hook) keeps the two passes.
+    ConvOp* sum_conv = nullptr;
+    void on_prepare(Graph& g) override { plan_long_skip(g); }
+    void plan_long_skip(Graph& g) {
+        sum_conv = nullptr;
+        for (auto& up : g.ops)
+            if (ConvOp* cv = dynamic_cast<ConvOp*>(up.get())) {
+                if (cv->sum_out == out) cv->sum_add = cv->sum_out = -1;
+                if (cv->in == out) cv->dual_a = cv->dual_b = -1;
+            }
+        if (relu || a == b || test_env("DL4DS_NO_LONG_SKIP_FUSION")) return;
+        const GTensor& to = g.tensors[out];
+        if (g.tensors[a].per_sample() != to.per_sample() || g.tensors[b].per_sample() != to.per_sample()) return;
+        auto is_output = [&](int t) { for (int o : g.outputs) if (o == t) return true; return false; };
+        auto dense = [&](int t) { return g.tensors[t].alias_of < 0 && !g.tensors[t].galias; };
+        if (!dense(a) || !dense(b) || !dense(out)) return;
+        // forward: operand b, else a, is the output of a 3x3 Conv2D that nothing else reads
+        for (int t : {b, a}) {
+            const GTensor& tt = g.tensors[t];
+            if (is_output(t) || tt.is_input || tt.n_conv_in || tt.n_other || tt.n_masking || tt.n_add_in != 1) continue;
+            for (auto& up : g.ops) {
+                ConvOp* cv = dynamic_cast<ConvOp*>(up.get());
+                if (!cv || cv->out != t) continue;
+                if (cv->KS == 3 && cv->d2s <= 1 && cv->add < 0 && !cv->att_before && !cv->att_after) {
+                    cv->sum_add = (t == b) ? a : b;
+                    cv->sum_out = out;
+                    sum_conv = cv;
+                }
+            }
+            if (sum_conv) break;
+        }
+        // backward: the output's one reader is a plain 3x3 Conv2D (its dgrad runs on the main stream)
+        if (!is_output(out) && to.n_conv_in == 1 && to.n_other == 0 && to.n_masking == 0 && to.n_add_in == 0 && to.requires_grad)
+            for (auto& up : g.ops) {
+                ConvOp* cv = dynamic_cast<ConvOp*>(up.get());
+                if (cv && cv->in == out && cv->KS == 3 && !cv->att_before && !cv->att_after) { cv->dual_a = a; cv->dual_b = b; }
+            }
+    }
     void forward(Graph& g, int B, bool) override {
+        if (sum_conv && ConvOp::long_skip_active(g) && sum_conv->forward_with_sum(g, B)) return;
         add_act(g.stream, g.tensors[a].data, g.tensors[b].data, g.tensors[out].data,
                 g.tensors[out].per_sample() * B, relu);
     }
     void backward(Graph& g, const BwdCtx& c) override {
-        if (!g.tensors[out].grad_written) return;
+        if (!g.tensors[out].grad_written || g.tensors[out].add_grads_done) return;
         TView dY = g.view(out, c.B, true, c.b_off, c.b_cnt);
         if (relu) {
             TView none{nullptr, 0, 0, 0, 0, 0, 0, 0};

@@ -14,9 +14,21 @@ struct ConvEpilogue {
     // conv2d_narrow_pair_tiles_per_image): the pooling of a ChannelAttention2D that consumes this output.  Only the
     // narrow pair kernel emits it; callers check conv2d_narrow_pair_ok first, every other path rejects it.
     float* pool = nullptr;
+    // Second output pairs (both with the output's shape and layout; conv2d_forward_fused only, see there):
+    //   sum_out = v + sum_add, v the value stored to `out` (AFTER the activation -- not `add`, which comes before it): an Add that
+    //   consumes this layer's output, written by the layer;
+    //   out2 = the value `out` receives before ITS mask, zeroed where mask2 <= 0 (needs mask): the backward of an Add of two ReLU
+    //   outputs, written by the dgrad that produces the Add's output gradient.  With more than one pass over the input channels the
+    //   raw partial sums accumulate in `partial` (then required: the Add's output-gradient buffer), not in `out`.
+    TView sum_add{nullptr, 0, 0, 0, 0, 0, 0, 0}, sum_out{nullptr, 0, 0, 0, 0, 0, 0, 0};
+    TView mask2{nullptr, 0, 0, 0, 0, 0, 0, 0}, out2{nullptr, 0, 0, 0, 0, 0, 0, 0}, partial{nullptr, 0, 0, 0, 0, 0, 0, 0};
 };
 void conv2d_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
                     const ConvEpilogue& ep);
+// The same convolution with an epilogue that carries sum_out or out2, on the kernel conv2d_forward picks for the call without
+// them -- if that kernel has the form (conv_split: sum_out; conv_wino<3,3>: both).  false: nothing was launched, the caller runs
+// the plain convolution and the stand-alone element-wise pass (conv2d_forward itself refuses such an epilogue).
+bool conv2d_forward_fused(hipStream_t s, const TView& in, const float* w, int KS, const TView& out, const ConvEpilogue& ep);
 // wt[(KS*KS-1-tap)][co][ci] = w[tap][ci][co] : conv2d_forward(dz, wt) == dgrad
 void conv2d_dgrad_weights(hipStream_t s, const float* w, float* wt, int KS, int Cin, int Cout);
 // several of them in one launch: jobs_dev = nj x DgradWeightsJob on the device, blocks = sum of their block counts
@@ -51,9 +63,12 @@ int conv2d_narrow_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, 
 // small grids (H W <= max_hw) with many channels as a GEMM over flattened pixels (conv_gemm.hip); false = not eligible
 bool conv2d_gemm_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out, const ConvEpilogue& ep, int max_hw);
 // Winograd F(2x2, 3x3) form of the MFMA-bound 3x3 layers (conv_wino.hip); false = not eligible
-bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
+bool conv2d_wino_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep,
+                         bool* form_refused = nullptr);
+// (form_refused, both kernels: set when the layer is the kernel's but ep's sum_out / out2 form is not built -- conv2d_forward_fused)
 // the 40 / 48-channel 3x3 layers with their fp32 products as six bf16 MFMA terms (conv_split.hip); false = not eligible / DL4DS_NO_SPLIT
-bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
+bool conv2d_split_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep,
+                          bool* form_refused = nullptr);
 // The operands derived from the filters of a graph's layers -- the Winograd layers' transformed filters (conv_wino.hip), then the
 // six-term kernel's bf16 fragments (conv_split.hip) -- one batched launch each per pass instead of one per layer (conv_cache.h; a pass
 // of a graph holds a GraphPassGuard): _invalidate marks every registered filter inside [lo, hi) stale, _refresh rebuilds the stale

@@ -48,6 +48,53 @@ def conv2d_epilogue(x, w, b=None, add=None, mask=None, relu=False, accumulate_in
     return y.numpy()
 
 
+def conv2d_sum_output(x, w, b, s, relu=False):
+    """-> (y, s + y, launched) with y = [relu](conv_same(x,w)+b): the Add behind a layer written by the layer's own kernel.
+    launched False: the kernel that takes this layer has no such form (nothing was written)."""
+    n, h, wd, cin = x.shape
+    ks, _, ci, cout = w.shape
+    assert ci == cin and s.shape == (n, h, wd, cout)
+    dx, dw, db, ds = _d(x), _d(w), _d(b), _d(s)
+    y, y2 = DeviceArray.zeros((n, h, wd, cout)), DeviceArray.zeros((n, h, wd, cout))
+    ok = ctypes.c_int(0)
+    _lib.check(_lib.lib().dl4ds_op_conv2d_second_output(dx.ptr, dw.ptr, _p(db), ds.ptr, y2.ptr, None, None, None, None, y.ptr, n, h, wd,
+                                                        cin, cout, ks, int(relu), ctypes.byref(ok)))
+    return y.numpy(), y2.numpy(), bool(ok.value)
+
+
+def conv2d_dual_mask(x, w, mask, mask2):
+    """-> (conv * [mask > 0], conv * [mask2 > 0], launched) with conv = conv_same(x,w): the backward of an Add of two ReLU outputs
+    written by the dgrad that produces the Add's output gradient."""
+    n, h, wd, cin = x.shape
+    ks, _, ci, cout = w.shape
+    assert ci == cin and mask.shape == mask2.shape == (n, h, wd, cout)
+    dx, dw, dm, dm2 = _d(x), _d(w), _d(mask), _d(mask2)
+    y, y2, part = (DeviceArray.zeros((n, h, wd, cout)) for _ in range(3))
+    ok = ctypes.c_int(0)
+    _lib.check(_lib.lib().dl4ds_op_conv2d_second_output(dx.ptr, dw.ptr, None, None, None, dm.ptr, dm2.ptr, y2.ptr, part.ptr, y.ptr, n, h,
+                                                        wd, cin, cout, ks, 0, ctypes.byref(ok)))
+    return y.numpy(), y2.numpy(), bool(ok.value)
+
+
+def add_act(a, b, relu=False):
+    """[relu](a + b), the stand-alone Add pass."""
+    da, db = _d(a), _d(b)
+    out = DeviceArray.zeros(a.shape)
+    _lib.check(_lib.lib().dl4ds_op_add_act(da.ptr, db.ptr, out.ptr, a.size, int(relu)))
+    return out.numpy()
+
+
+def masked_axpy_pair(dy, ya, yb):
+    """-> (dy * [ya > 0], dy * [yb > 0]), the stand-alone backward pass of an Add of two ReLU outputs."""
+    ddy, dya, dyb = _d(dy), _d(ya), _d(yb)
+    da, db = DeviceArray.zeros(dy.shape), DeviceArray.zeros(dy.shape)
+    ok = ctypes.c_int(0)
+    _lib.check(_lib.lib().dl4ds_op_masked_axpy_pair(ddy.ptr, dya.ptr, da.ptr, dyb.ptr, db.ptr, dy.size, ctypes.byref(ok)))
+    if not ok.value:
+        raise ValueError('masked_axpy_pair: size not a multiple of four')
+    return da.numpy(), db.numpy()
+
+
 def conv2d_dgrad(dz, w, d2s=0, accumulate_into=None):
     """dx = dgrad(dz, w).  dz: gradient of the conv output (in d2s layout if d2s>1)."""
     ks, _, cin, cout = w.shape

@@ -77,6 +77,23 @@ int dl4ds_op_conv2d_fwd(const float* x_dev, const float* w_dev, const float* b_d
 int dl4ds_op_conv2d_epilogue(const float* x_dev, const float* w_dev, const float* b_dev, const float* add_dev,
                              const float* mask_dev, float* y_dev, int N, int H, int W, int Cin, int Cout, int KS, int relu,
                              int accumulate);
+/* The convolution with a second output pair, as the graph uses it around the long skip `s + relu(conv)` of the residual backbone
+ * (sp_postups.py:154-158), on the kernel dl4ds_op_conv2d_epilogue picks for the same call without the pair:
+ *   sum_add, sum_out:      y = act(conv(x, w) + b) and sum_out = sum_add + y (the Add that follows the layer);
+ *   mask, mask2, y2:       y = conv * [mask > 0], y2 = conv * [mask2 > 0] (the backward of that Add over two ReLU outputs, from the
+ *                          dgrad that makes its output gradient); `partial` (N*H*W*Cout floats) takes the raw partial sums when the
+ *                          kernel makes more than one pass over the input channels.
+ * One pair per call; all arrays (N,H,W,Cout).  *launched = 0: that kernel has no such form and nothing was written. */
+int dl4ds_op_conv2d_second_output(const float* x_dev, const float* w_dev, const float* b_dev, const float* sum_add_dev,
+                                  float* sum_out_dev, const float* mask_dev, const float* mask2_dev, float* y2_dev,
+                                  float* partial_dev, float* y_dev, int N, int H, int W, int Cin, int Cout, int KS, int relu,
+                                  int* launched);
+/* out = [relu](a + b) over n floats -- tf.keras.layers.Add (sp_postups.py:158), the stand-alone pass */
+int dl4ds_op_add_act(const float* a_dev, const float* b_dev, float* out_dev, size_t n, int relu);
+/* da = dy * [ya > 0], db = dy * [yb > 0] over n floats: the backward of an Add of two ReLU outputs, the stand-alone pass.
+ * *launched = 0: n % 4 != 0 or an operand is not 16-byte aligned, nothing was written. */
+int dl4ds_op_masked_axpy_pair(const float* dy_dev, const float* ya_dev, float* da_dev, const float* yb_dev, float* db_dev,
+                              size_t n, int* launched);
 /* dx (+)= dgrad(dz, w); dz may be given in depth_to_space(d2s_r) layout (gradient of a fused-d2s conv) */
 int dl4ds_op_conv2d_dgrad(const float* dz_dev, const float* w_dev, float* dx_dev, int N, int H, int W,
                           int Cin, int Cout, int KS, int d2s_r, int accumulate);
