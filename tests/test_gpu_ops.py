@@ -764,6 +764,9 @@ def test_maxpool(ops):
 
 @pytest.mark.parametrize('h,w,ho,wo', [(6, 7, 24, 28), (8, 8, 16, 16), (9, 5, 27, 20), (16, 16, 4, 4)])
 def test_resize_bilinear(ops, h, w, ho, wo):
+    """The DIRECT bilinear kernels (resize_fwd_kernel / resize_bwd_kernel behind ops.resize_bilinear).  A graph runs them only under
+    the experiments switch DL4DS_RESIZE_BILINEAR_DIRECT: a bilinear Resizing in a graph goes through the table-driven kernels, which
+    tests/test_gpu_resize.py covers."""
     x = R(2, h, w, 3)
     close(ops.resize_bilinear(x, ho, wo), N.resize_bilinear(x.astype(np.float64), ho, wo))
     dy = R(2, ho, wo, 3)
@@ -1038,7 +1041,7 @@ def test_resize_nearest_in_graph(shape, out):
     ref = N.resize_nearest(x.astype(np.float64), *out)
     np.testing.assert_array_equal(m([x]), ref.astype(np.float32))
     # gradient w.r.t. the identity kernel = sum over pixels of resized(x)_ci * dy_co: exercises the forward; the input
-    # gradient is exercised by the model tests (rc_interpolation='nearest')
+    # gradient (resize_nearest_bwd) is checked per element by tests/test_gpu_resize.py::test_nearest_resize
     yt = R(n, out[0], out[1], c)
     eng = SupervisedEngine(m, loss='mse', learning_rate=1e-3)
     _, grads = eng.loss_and_grads([x], yt)
