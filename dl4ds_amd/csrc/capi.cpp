@@ -26,6 +26,7 @@ void cgan_step(CganTrainer& t, const float* const* gen_inputs, int n_gen_inputs,
 Trainer* cgan_disc_trainer(CganTrainer* t);
 Trainer* cgan_gen_trainer(CganTrainer* t);
 void cgan_set_learning_rates(CganTrainer* t, float gen_lr, float disc_lr);
+void cgan_set_loss_weights(CganTrainer* t, const float* w, int w_batch, int H, int W, int w_channels, bool is_host);
 
 namespace {
 thread_local std::string g_last_error;
@@ -541,6 +542,15 @@ int dl4ds_op_loss(int kind, const float* yt, const float* yp, float* dpred, int 
     loss_forward_backward(S(), kind, yt, yp, dpred, N, H, W, C, 1.f, loss_dev, 0, scratch(ws), ws);
     API_END
 }
+int dl4ds_op_loss_weighted(int kind, const float* yt, const float* yp, float* dpred, int N, int H, int W, int C, const float* w,
+                           int w_batch, int w_channels, float* loss_dev) {
+    API_BEGIN
+    DL4DS_REQUIRE(w && w_batch >= 1 && N > 0 && N % w_batch == 0 && (w_channels == 1 || w_channels == C),
+                  "op_loss_weighted: w_batch must divide N and w_channels must be 1 or C");
+    const size_t ws = loss_workspace_bytes_weighted(kind, N, H, W, C, w_batch, w_channels);
+    loss_forward_backward_weighted(S(), kind, yt, yp, dpred, N, H, W, C, 1.f, loss_dev, 0, w, w_batch, w_channels, scratch(ws), ws);
+    API_END
+}
 int dl4ds_metrics(const float* yt, const float* yp, int N, int H, int W, int C, float* pair_out_dev, float* grid_out_dev,
                   float* range_out_dev) {
     API_BEGIN
@@ -1050,6 +1060,19 @@ int dl4ds_trainer_evaluate(dl4ds_trainer* tr, const float* const* inputs, int n_
     trainer_evaluate(*tr->t, inputs, n_inputs, y_true, B, is_host != 0);
     HIP_CHECK(hipMemcpyAsync(loss_host, tr->t->d_loss, sizeof(float), hipMemcpyDeviceToHost, S()));
     dist_stream_sync(S(), "dl4ds_trainer_evaluate");
+    API_END
+}
+int dl4ds_trainer_set_loss_weights(dl4ds_trainer* tr, const float* w, int w_batch, int H, int W, int w_channels, int is_host) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    Graph& g = *tr->t->g;
+    loss_weight_map_set(tr->t->lw, g.stream, w, w_batch, H, W, w_channels, is_host != 0, g.tensors[g.outputs[0]]);
+    API_END
+}
+int dl4ds_cgan_set_loss_weights(dl4ds_trainer* tr, const float* w, int w_batch, int H, int W, int w_channels, int is_host) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->c, "not a CGAN trainer");
+    cgan_set_loss_weights(tr->c, w, w_batch, H, W, w_channels, is_host != 0);
     API_END
 }
 int dl4ds_trainer_get_state(dl4ds_trainer* tr, float* m_host, float* v_host, long* step) {

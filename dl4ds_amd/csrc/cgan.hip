@@ -57,6 +57,7 @@ struct CganTrainer {
     size_t hr_floats = 0;
     float* loss_ws = nullptr;
     size_t loss_ws_bytes = 0;
+    LossWeightMap lw;              // weights of the pixel loss only; the adversarial terms never see them
     int shared_plan = -1;          // discriminator: conditioning branch evaluated once for [real ; fake] (-1: not decided yet)
     int ratio_plan = -1;           // pass 2 by per-sample rescaling of pass 1's gradients (-1: not decided yet)
     std::vector<int> ratio_ops;    // ops of D that read its gradient-taking input
@@ -98,6 +99,10 @@ void cgan_destroy(CganTrainer* t) {
 }
 Trainer* cgan_disc_trainer(CganTrainer* t) { return t->D; }
 Trainer* cgan_gen_trainer(CganTrainer* t) { return t->G; }
+void cgan_set_loss_weights(CganTrainer* t, const float* w, int w_batch, int H, int W, int w_channels, bool is_host) {
+    Graph& G = *t->G->g;
+    loss_weight_map_set(t->lw, G.stream, w, w_batch, H, W, w_channels, is_host, G.tensors[G.outputs[0]]);
+}
 // genlr, dislr = learning_rates (cgan.py:271-278): one Adam per model, each with its own rate
 void cgan_set_learning_rates(CganTrainer* t, float gen_lr, float disc_lr) {
     t->G->cfg.lr0 = t->G->cfg.lr1 = gen_lr;
@@ -120,7 +125,10 @@ void cgan_step(CganTrainer& t, const float* const* gen_inputs, int n_gen_inputs,
         HIP_CHECK(hipMalloc((void**)&t.hr, hr_n * sizeof(float)));
         t.hr_floats = hr_n;
     }
-    const size_t lws = loss_workspace_bytes(t.px_kind, B * go.nmul, go.H, go.W, go.C);
+    if (t.lw.set)
+        DL4DS_REQUIRE(t.lw.batch == 1 || t.lw.batch == B, "per-sample loss weights were set for another batch size than this step's");
+    const size_t lws = t.lw.set ? loss_workspace_bytes_weighted(t.px_kind, B * go.nmul, go.H, go.W, go.C, t.lw.batch, t.lw.ch)
+                                : loss_workspace_bytes(t.px_kind, B * go.nmul, go.H, go.W, go.C);
     if (lws > t.loss_ws_bytes) {
         HIP_CHECK(hipStreamSynchronize(s));
         if (t.loss_ws) HIP_CHECK(hipFree(t.loss_ws));
@@ -226,8 +234,12 @@ void cgan_step(CganTrainer& t, const float* const* gen_inputs, int n_gen_inputs,
     }
     // ---- generator backward: lambda * dpx/dgen + dgan/dgen
     G.zero_grad_flags();
-    loss_forward_backward(s, t.px_kind, t.hr, go.data, go.grad, B * go.nmul, go.H, go.W, go.C, t.lam, t.d_losses + 1, 0,
-                          t.loss_ws, t.loss_ws_bytes);
+    if (t.lw.set)
+        loss_forward_backward_weighted(s, t.px_kind, t.hr, go.data, go.grad, B * go.nmul, go.H, go.W, go.C, t.lam, t.d_losses + 1, 0,
+                                       t.lw.w, t.lw.batch, t.lw.ch, t.loss_ws, t.loss_ws_bytes);
+    else
+        loss_forward_backward(s, t.px_kind, t.hr, go.data, go.grad, B * go.nmul, go.H, go.W, go.C, t.lam, t.d_losses + 1, 0,
+                              t.loss_ws, t.loss_ws_bytes);
     TView src = make_view(dhr.grad + hr_n, B * go.nmul, go.H, go.W, go.C);
     TView dst = make_view(go.grad, B * go.nmul, go.H, go.W, go.C);
     view_axpy(s, src, dst, 1.f, 1);

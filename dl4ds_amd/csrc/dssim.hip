@@ -7,6 +7,14 @@
 // separably (row pass over the 26 halo rows into LDS, then the column pass per output: 2 x 11 taps instead of 121) to the
 // four moments -- emitting the three per-map derivatives, (3) the transposed (again separable) filter of those
 // derivatives per input pixel, (4) scalar fix-ups (drange and shift terms routed to arg-max / arg-min).
+//
+// Weighted form (dssim_forward_backward_weighted; contract in losses.hip): window weights omega = G * w over the VALID windows,
+// term = sum omega (1 - s)/2 / sum omega, windows with omega == 0 excluded by selection.  omega_kernel WRITES the omega map once per
+// call (w_batch x w_channels planes of Ho x Wo, the separable filter of the moments applied to w) together with per-tile sums, whose
+// fixed-order double sum leaves 1 / sum omega in a device scalar; the WEIGHTED instantiations of the tile kernels multiply S, the three
+// derivative maps and the c1 / c2 partials by omega at the window, and the backward and finishing kernels take their coefficient
+// from that scalar -- so the drange and min-shift fix-ups carry the weights.  minmax_kernel is the unweighted one: dynamic range and
+// positivity shift are those of the whole arrays, hence y_true must be finite everywhere.
 #include "ops.h"
 #include "prof.h"
 #include <algorithm>
@@ -138,12 +146,57 @@ __device__ __forceinline__ void sep_transposed3(const float (*s1)[PT], const flo
     }
 }
 
-// one block = one 16x16 tile of the (Ho,Wo) SSIM map of plane (n,c)
+// omega[(m, c), oy, ox] = sum_ij g[i] g[j] w[m, oy + i, ox + j, c]; one block = one 16x16 tile of plane (m, c) of the w_batch x cw
+// weight planes; partial[block] = the tile's sum of omega.  All taps and weights are >= 0: omega == 0 iff the whole window is masked.
+__global__ void __launch_bounds__(256) omega_kernel(const float* __restrict__ w, int H, int W, int cw, int Ho, int Wo, int tiles_x,
+                                                    int tiles_y, Gauss gk, float* __restrict__ omega, float* __restrict__ partial) {
+    __shared__ float sw[TL][PT], h[TL][TS];
+    __shared__ float red[256];
+    int b = blockIdx.x;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y; b /= tiles_y;
+    const int c = b % cw, m = b / cw;
+    const int oy0 = ty * TS, ox0 = tx * TS;
+    for (int i = threadIdx.x; i < TL * TL; i += 256) {
+        const int r = i / TL, cc = i % TL;
+        const int y = oy0 + r, x = ox0 + cc;
+        sw[r][cc] = (y < H && x < W) ? w[(((size_t)m * H + y) * W + x) * cw + c] : 0.f;
+    }
+    __syncthreads();
+    for (int it = threadIdx.x; it < TL * TS; it += 256) {
+        const int r = it / TS, cx = it % TS;
+        float a = 0.f;
+#pragma unroll
+        for (int j = 0; j < KF; ++j) a += gk.g[j] * sw[r][cx + j];
+        h[r][cx] = a;
+    }
+    __syncthreads();
+    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
+    const int oy = oy0 + ly, ox = ox0 + lx;
+    float om = 0.f;
+    if (oy < Ho && ox < Wo) {
+#pragma unroll
+        for (int i = 0; i < KF; ++i) om += gk.g[i] * h[ly + i][lx];
+        omega[(((size_t)m * cw + c) * Ho + oy) * Wo + ox] = om;
+    }
+    red[threadIdx.x] = om;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// one block = one 16x16 tile of the (Ho,Wo) SSIM map of plane (n,c).  WEIGHTED: S, the derivative maps and the c1 / c2 partials are
+// multiplied by omega[(n / wrep, cw == C ? c : 0), oy, ox]; a window with omega == 0 contributes exact zeros whatever it holds
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__ t, const float* __restrict__ p, int H, int W,
                                                        int C, int Ho, int Wo, int tiles_x, int tiles_y, Gauss gk,
                                                        const Stats* __restrict__ st, float* __restrict__ dmu,
                                                        float* __restrict__ da, float* __restrict__ db,
-                                                       float* __restrict__ partial) {
+                                                       float* __restrict__ partial, const float* __restrict__ omega, int wrep,
+                                                       int cw) {
     __shared__ float sx[TL][PT], sq[TL][PT], hrow[4][TL][TS];
     __shared__ float red[3][256];
     int b = blockIdx.x;
@@ -176,11 +229,19 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
         const float lum = N1 / D1, cs = N2 / D2;
         S = lum * cs;
         const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
-        dmu[o] = cs * (2.f * mx / D1 - N1 * 2.f * my / (D1 * D1)) + lum * (-2.f * mx / D2 + N2 * 2.f * my / (D2 * D2));
-        da[o] = lum * 2.f / D2;
-        db[o] = -lum * N2 / (D2 * D2);
+        float vmu = cs * (2.f * mx / D1 - N1 * 2.f * my / (D1 * D1)) + lum * (-2.f * mx / D2 + N2 * 2.f * my / (D2 * D2));
+        float va = lum * 2.f / D2;
+        float vb = -lum * N2 / (D2 * D2);
         g1 = cs * (D1 - N1) / (D1 * D1);
         g2 = lum * (D2 - N2) / (D2 * D2);
+        if (WEIGHTED) {
+            const float om = omega[(((size_t)(n / wrep) * cw + (cw == C ? c : 0)) * Ho + oy) * Wo + ox];
+            if (om > 0.f) { S *= om; vmu *= om; va *= om; vb *= om; g1 *= om; g2 *= om; }
+            else { S = 0.f; vmu = 0.f; va = 0.f; vb = 0.f; g1 = 0.f; g2 = 0.f; }
+        }
+        dmu[o] = vmu;
+        da[o] = va;
+        db[o] = vb;
     }
     red[0][threadIdx.x] = S; red[1][threadIdx.x] = g1; red[2][threadIdx.x] = g2;
     __syncthreads();
@@ -236,15 +297,18 @@ __global__ void sum3_kernel(const float* __restrict__ partial, int nb, Stats* st
     if (threadIdx.x == 0) { st->sumS = (float)red[0][0]; st->gc1 = (float)red[1][0]; st->gc2 = (float)red[2][0]; }
 }
 
-// one block = one 16x16 tile of INPUT pixels of plane (n,c): transposed 11x11 filter of the derivative maps
+// one block = one 16x16 tile of INPUT pixels of plane (n,c): transposed 11x11 filter of the derivative maps.  WEIGHTED: the maps
+// already carry omega; coef (-weight / 2 here) is completed by 1 / sum omega from the device scalar
+template <bool WEIGHTED>
 __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__ t, const float* __restrict__ p, int H, int W,
                                                        int C, int Ho, int Wo, int tiles_x, int tiles_y, Gauss gk,
                                                        const Stats* __restrict__ st, const float* __restrict__ dmu,
                                                        const float* __restrict__ da, const float* __restrict__ db,
                                                        float coef, float* __restrict__ dpred, int accumulate,
-                                                       float* __restrict__ partial) {
+                                                       float* __restrict__ partial, const float* __restrict__ inv_so) {
     __shared__ float s1[TL][PT], s2[TL][PT], s3[TL][PT], hrow[3][TL][TS];
     __shared__ float red[256];
+    if (WEIGHTED) coef *= inv_so[0];
     int b = blockIdx.x;
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y; b /= tiles_y;
@@ -283,8 +347,11 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// WEIGHTED: inv_m and the completion of coef (-weight / 2 here) are 1 / sum omega from the device scalar; a zero sum gives loss 0
+template <bool WEIGHTED>
 __global__ void dssim_finish_kernel(const float* __restrict__ partial, int nb, Stats* st, float weight, float inv_m,
-                                    float coef, float* __restrict__ dpred, float* __restrict__ loss_out, int accumulate_loss) {
+                                    float coef, float* __restrict__ dpred, float* __restrict__ loss_out, int accumulate_loss,
+                                    const float* __restrict__ inv_so) {
     __shared__ double red[256];
     double a = 0;
     for (int k = threadIdx.x; k < nb; k += 256) a += partial[k];
@@ -296,7 +363,8 @@ __global__ void dssim_finish_kernel(const float* __restrict__ partial, int nb, S
     }
     if (threadIdx.x != 0) return;
     const float sumdy = (float)red[0];
-    const float v = weight * (0.5f - 0.5f * st->sumS * inv_m);
+    if (WEIGHTED) { inv_m = inv_so[0]; coef *= inv_m; }
+    const float v = (WEIGHTED && inv_m == 0.f) ? 0.f : weight * (0.5f - 0.5f * st->sumS * inv_m);
     loss_out[0] = accumulate_loss ? loss_out[0] + v : v;
     if (!dpred) return;
     const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
@@ -596,8 +664,17 @@ MsLayout ms_layout(int N, int H, int W, int C) {
 
 size_t dssim_workspace_bytes(int N, int H, int W, int C) { return layout(N, H, W, C).total; }
 
-void dssim_forward_backward(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W, int C,
-                            float weight, float* loss_out, int accumulate_loss, float* workspace, size_t workspace_bytes) {
+void weight_sum_finish(hipStream_t s, const float* partial, int nb, double mult, float* inv_out);     // losses.hip
+
+namespace {
+// the weight side of one weighted call: maps, their batch / channel counts, the device scalar 1 / sum omega, and the extra workspace
+struct DssimWeights { const float* w; int wb, cw; float* inv_so; float* ext; };
+size_t omega_floats(int H, int W, int wb, int cw) { return ((size_t)wb * cw * (H - KF + 1) * (W - KF + 1) + 63) & ~(size_t)63; }
+size_t omega_tiles(int H, int W, int wb, int cw) { return (size_t)wb * cw * cdiv(H - KF + 1, TS) * cdiv(W - KF + 1, TS); }
+
+template <bool WEIGHTED>
+void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W, int C, float weight,
+               float* loss_out, int accumulate_loss, float* workspace, size_t workspace_bytes, const DssimWeights& dw) {
     DL4DS_REQUIRE(H >= KF && W >= KF, "dssim needs grids of at least 11x11");
     Layout l = layout(N, H, W, C);
     DL4DS_REQUIRE(workspace_bytes >= l.total, "dssim workspace too small");
@@ -619,24 +696,61 @@ void dssim_forward_backward(hipStream_t s, const float* y_true, const float* y_p
     DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, nb, st);
     const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
     const int nbf = N * C * txo * tyo;
-    DL4DS_LAUNCH(ssim_fwd_kernel, dim3(nbf), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txo, tyo, gk, st, dmu, da,
-                       db, part);
+    const float* omega = nullptr;
+    const float* inv_so = nullptr;
+    int wrep = 1, cw = 1;
+    if (WEIGHTED) {
+        float* om = dw.ext;
+        float* opart = dw.ext + omega_floats(H, W, dw.wb, dw.cw);
+        const int nbo = (int)omega_tiles(H, W, dw.wb, dw.cw);
+        DL4DS_LAUNCH(omega_kernel, dim3(nbo), dim3(256), 0, s, dw.w, H, W, dw.cw, Ho, Wo, txo, tyo, gk, om, opart);
+        // sum over samples, windows and channels = the planes' sum times how often each plane is used
+        weight_sum_finish(s, opart, nbo, (double)(N / dw.wb) * (double)(C / dw.cw), dw.inv_so);
+        omega = om; inv_so = dw.inv_so; wrep = N / dw.wb; cw = dw.cw;
+    }
+    DL4DS_LAUNCH(ssim_fwd_kernel<WEIGHTED>, dim3(nbf), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txo, tyo, gk, st, dmu, da,
+                       db, part, omega, wrep, cw);
     float* part2 = reinterpret_cast<float*>(base + l.part2);
     DL4DS_LAUNCH(compact_partials_kernel<3>, dim3(COMPACT_G), dim3(256), 0, s, part, nbf, part2);
     DL4DS_LAUNCH(sum3_kernel, dim3(1), dim3(256), 0, s, part2, COMPACT_G, st);
     const float inv_m = 1.f / (float)msz;
-    const float coef = -0.5f * weight * inv_m;
+    const float coef = WEIGHTED ? -0.5f * weight : -0.5f * weight * inv_m;      // WEIGHTED: completed on the device by 1 / sum omega
     int nbb = 0;
     if (dpred) {
         const int txi = cdiv(W, TS), tyi = cdiv(H, TS);
         nbb = N * C * txi * tyi;
-        DL4DS_LAUNCH(ssim_bwd_kernel, dim3(nbb), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txi, tyi, gk, st, dmu, da,
-                           db, coef, dpred, 1, part);
+        DL4DS_LAUNCH(ssim_bwd_kernel<WEIGHTED>, dim3(nbb), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txi, tyi, gk, st, dmu,
+                           da, db, coef, dpred, 1, part, inv_so);
     }
     if (nbb) DL4DS_LAUNCH(compact_partials_kernel<1>, dim3(COMPACT_G), dim3(256), 0, s, part, nbb, part2);
-    DL4DS_LAUNCH(dssim_finish_kernel, dim3(1), dim3(256), 0, s, part2, nbb ? COMPACT_G : 0, st, weight, inv_m, coef, dpred,
-                       loss_out, accumulate_loss);
+    DL4DS_LAUNCH(dssim_finish_kernel<WEIGHTED>, dim3(1), dim3(256), 0, s, part2, nbb ? COMPACT_G : 0, st, weight, inv_m, coef, dpred,
+                       loss_out, accumulate_loss, inv_so);
     HIP_CHECK(hipGetLastError());
+}
+}  // namespace
+
+void dssim_forward_backward(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W, int C,
+                            float weight, float* loss_out, int accumulate_loss, float* workspace, size_t workspace_bytes) {
+    dssim_run<false>(s, y_true, y_pred, dpred, N, H, W, C, weight, loss_out, accumulate_loss, workspace, workspace_bytes,
+                     DssimWeights{nullptr, 1, 1, nullptr, nullptr});
+}
+
+size_t dssim_weighted_workspace_bytes(int N, int H, int W, int C, int w_batch, int w_channels) {
+    (void)N; (void)C;
+    if (H < KF || W < KF) return 0;
+    return (omega_floats(H, W, w_batch, w_channels) + omega_tiles(H, W, w_batch, w_channels)) * sizeof(float);
+}
+
+// w: w_batch maps (H, W, w_channels) (contract in losses.hip); inv_so_dev: one device float that receives 1 / sum omega; ext: the
+// omega map and its per-tile sums (dssim_weighted_workspace_bytes)
+void dssim_forward_backward_weighted(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W,
+                                     int C, float weight, float* loss_out, int accumulate_loss, const float* w, int w_batch,
+                                     int w_channels, float* inv_so_dev, float* workspace, size_t workspace_bytes, float* ext,
+                                     size_t ext_bytes) {
+    DL4DS_REQUIRE(H >= KF && W >= KF, "dssim needs grids of at least 11x11");
+    DL4DS_REQUIRE(ext_bytes >= dssim_weighted_workspace_bytes(N, H, W, C, w_batch, w_channels), "weighted dssim workspace too small");
+    dssim_run<true>(s, y_true, y_pred, dpred, N, H, W, C, weight, loss_out, accumulate_loss, workspace, workspace_bytes,
+                    DssimWeights{w, w_batch, w_channels, inv_so_dev, ext});
 }
 
 size_t msdssim_workspace_bytes(int N, int H, int W, int C) { return ms_layout(N, H, W, C).total; }

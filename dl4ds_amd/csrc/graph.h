@@ -223,6 +223,18 @@ struct AdamCfg {
     float beta1 = 0.9f, beta2 = 0.999f, eps = 1e-7f;
 };
 
+// per-grid-cell loss weights owned by a trainer (dl4ds_trainer_set_loss_weights): `batch` maps of (H, W, ch) in HBM
+struct LossWeightMap {
+    float* w = nullptr;
+    size_t cap = 0;                // floats allocated
+    int batch = 0, H = 0, W = 0, ch = 0;
+    bool set = false;
+    ~LossWeightMap();
+};
+// copy (asynchronously, on `s`) or clear (w == nullptr); H, W, ch must match the output tensor `out`
+void loss_weight_map_set(LossWeightMap& m, hipStream_t s, const float* w, int w_batch, int H, int W, int ch, bool is_host,
+                         const GTensor& out);
+
 struct Trainer {
     Graph* g = nullptr;
     AdamCfg cfg;
@@ -235,5 +247,6 @@ struct Trainer {
     size_t loss_ws_bytes = 0;
     float* y_true = nullptr;
     size_t y_true_floats = 0;
+    LossWeightMap lw;              // in force for step, loss_and_grads and evaluate until replaced or cleared
     ~Trainer();
 };

@@ -286,6 +286,13 @@ size_t loss_workspace_bytes(int kind, int N, int H, int W, int C);
 void loss_forward_backward(hipStream_t s, int kind, const float* y_true, const float* y_pred,
                            float* dpred, int N, int H, int W, int C, float scale, float* loss_out,
                            int accumulate, float* workspace, size_t workspace_bytes);
+// The same with per-grid-cell weights w (contract at the top of losses.hip): w_batch maps of (H, W, w_channels), w_batch divides N
+// (sample row r uses map r / (N / w_batch)), w_channels in {1, C}.  The msdssim kinds are refused.  The unweighted workspace figure
+// is unchanged; the weighted call needs loss_workspace_bytes_weighted.
+size_t loss_workspace_bytes_weighted(int kind, int N, int H, int W, int C, int w_batch, int w_channels);
+void loss_forward_backward_weighted(hipStream_t s, int kind, const float* y_true, const float* y_pred, float* dpred, int N,
+                                    int H, int W, int C, float scale, float* loss_out, int accumulate, const float* w,
+                                    int w_batch, int w_channels, float* workspace, size_t workspace_bytes);
 // BCE on probabilities p[n] vs constant label; loss_out[0] (+)= scale*mean ; dp = scale*dL/dp
 void bce_forward_backward(hipStream_t s, const float* p, float label, int n, float scale,
                           float* loss_out, float* dp, int accumulate_loss);

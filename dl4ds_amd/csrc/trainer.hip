@@ -15,6 +15,41 @@ Trainer::~Trainer() {
     if (y_true) (void)hipFree(y_true);
 }
 
+LossWeightMap::~LossWeightMap() {
+    if (w) (void)hipFree(w);
+}
+
+void loss_weight_map_set(LossWeightMap& m, hipStream_t s, const float* w, int w_batch, int H, int W, int ch, bool is_host,
+                         const GTensor& out) {
+    if (!w) { m.set = false; return; }
+    DL4DS_REQUIRE(w_batch >= 1, "loss weights: w_batch must be 1 (one shared map) or the batch size of the steps to come");
+    DL4DS_REQUIRE(H == out.H && W == out.W, "loss weights: H, W must be those of output 0");
+    DL4DS_REQUIRE(ch == 1 || ch == out.C, "loss weights: w_channels must be 1 or the channels of output 0");
+    const size_t n = (size_t)w_batch * H * W * ch;
+    if (n > m.cap) {
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (m.w) HIP_CHECK(hipFree(m.w));
+        m.w = nullptr; m.cap = 0; m.set = false;
+        HIP_CHECK(hipMalloc((void**)&m.w, n * sizeof(float)));
+        m.cap = n;
+    }
+    HIP_CHECK(hipMemcpyAsync(m.w, w, n * sizeof(float), is_host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, s));
+    m.batch = w_batch; m.H = H; m.W = W; m.ch = ch; m.set = true;
+}
+
+// the trainer's loss on output 0: the weighted kernels while a weight map is in force, else exactly the unweighted call
+static void trainer_loss(Trainer& t, const float* yt, int B) {
+    Graph& g = *t.g;
+    const GTensor& o = g.tensors[g.outputs[0]];
+    if (!t.lw.set) {
+        loss_forward_backward(g.stream, t.loss_kind, yt, o.data, o.grad, B * o.nmul, o.H, o.W, o.C, 1.f, t.d_loss, 0,
+                              t.loss_ws, t.loss_ws_bytes);
+        return;
+    }
+    loss_forward_backward_weighted(g.stream, t.loss_kind, yt, o.data, o.grad, B * o.nmul, o.H, o.W, o.C, 1.f, t.d_loss, 0,
+                                   t.lw.w, t.lw.batch, t.lw.ch, t.loss_ws, t.loss_ws_bytes);
+}
+
 Trainer* trainer_create(Graph* g, int loss_kind, const AdamCfg& cfg) {
     DL4DS_REQUIRE(g->finalized, "trainer: graph not finalized");
     DL4DS_REQUIRE(g->outputs.size() >= 1, "trainer: graph has no output");
@@ -54,7 +89,10 @@ static void ensure_loss_buffers(Trainer& t, int B) {
         HIP_CHECK(hipMalloc((void**)&t.y_true, need * sizeof(float)));
         t.y_true_floats = need;
     }
-    const size_t ws = loss_workspace_bytes(t.loss_kind, B * o.nmul, o.H, o.W, o.C);
+    if (t.lw.set)
+        DL4DS_REQUIRE(t.lw.batch == 1 || t.lw.batch == B, "per-sample loss weights were set for another batch size than this step's");
+    const size_t ws = t.lw.set ? loss_workspace_bytes_weighted(t.loss_kind, B * o.nmul, o.H, o.W, o.C, t.lw.batch, t.lw.ch)
+                               : loss_workspace_bytes(t.loss_kind, B * o.nmul, o.H, o.W, o.C);
     if (ws > t.loss_ws_bytes) {
         HIP_CHECK(hipStreamSynchronize(g.stream));
         if (t.loss_ws) HIP_CHECK(hipFree(t.loss_ws));
@@ -77,8 +115,7 @@ void trainer_loss_and_grads(Trainer& t, const float* const* inputs, int n_inputs
     }
     g.forward(B, true);
     g.zero_grad_flags();
-    loss_forward_backward(g.stream, t.loss_kind, yt, o.data, o.grad, B * o.nmul, o.H, o.W, o.C, 1.f, t.d_loss, 0,
-                          t.loss_ws, t.loss_ws_bytes);
+    trainer_loss(t, yt, B);
     // (inputs created with dl4ds_graph_input_requires_grad get their gradient too: dl4ds_graph_tensor_ptr(id, grad = 1))
     bool input_grads = false;
     for (int i : g.inputs) input_grads = input_grads || g.tensors[i].requires_grad;
@@ -109,8 +146,7 @@ void trainer_evaluate(Trainer& t, const float* const* inputs, int n_inputs, cons
     }
     g.forward(B, false);
     // the fused loss kernels always emit dL/dpred; it lands in the output's gradient buffer and is never read
-    loss_forward_backward(g.stream, t.loss_kind, yt, o.data, o.grad, B * o.nmul, o.H, o.W, o.C, 1.f, t.d_loss, 0,
-                          t.loss_ws, t.loss_ws_bytes);
+    trainer_loss(t, yt, B);
 }
 
 static float current_lr(const Trainer& t) {

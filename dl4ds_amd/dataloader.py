@@ -482,6 +482,8 @@ class DeviceDataGenerator:
             st = DeviceArray((B, self.psy, self.psx, self.S)) if self.S else None
             self._bufs.append((lr, hr, st))
         self._turn = 0
+        self.last_draw = None           # (idx, cy, cx) of the latest batch: sample indices and HR crop corners (crop_field)
+        self._field_bufs = {}
         self._tap_keep, self._tab_cache = [], {}
         if self.general:
             self._plan_general()
@@ -627,6 +629,41 @@ class DeviceDataGenerator:
     def __len__(self):
         return len(self.indices) // self.batch_size
 
+    def crop_field(self, field_dev):
+        """Crops of ONE HR-grid field (a DeviceArray of shape (H, W) or (H, W, Cw), e.g. a loss-weight map) at the corners of the
+        latest batch: a (B, psy, psx, Cw) DeviceArray, valid until the second next call (two rotating buffers per channel count).
+        One `dl4ds_batch_gather` pass with a single raw, static-image group -- what the composed route does for static variables."""
+        import ctypes
+        from . import _lib
+        from .device import DeviceArray
+        if self.last_draw is None:
+            raise RuntimeError('crop_field: no batch has been drawn yet')
+        shape = tuple(field_dev.shape)
+        if len(shape) == 2:
+            shape = shape + (1,)
+        if len(shape) != 3 or shape[:2] != (self.H, self.W):
+            raise ValueError(f'crop_field: a field of shape {tuple(field_dev.shape)} is not on the {self.H} x {self.W} HR grid')
+        cw = shape[2]
+
+        class TapAxis(ctypes.Structure):
+            _fields_ = [('idx', ctypes.c_void_p), ('wt', ctypes.c_void_p), ('k', ctypes.c_int)]
+
+        class Group(ctypes.Structure):
+            _fields_ = [('src', ctypes.c_void_p), ('channels', ctypes.c_int), ('frames', ctypes.c_int), ('src_h', ctypes.c_int),
+                        ('src_w', ctypes.c_int), ('raw', ctypes.c_int), ('origin_from_crop', ctypes.c_int), ('row_div', ctypes.c_int),
+                        ('taps', TapAxis * 2)]
+        bufs = self._field_bufs.setdefault(cw, [[DeviceArray((self.batch_size, self.psy, self.psx, cw)) for _ in range(2)], 0])
+        out = bufs[0][bufs[1]]
+        bufs[1] ^= 1
+        idx, cy, cx = self.last_draw
+        arr = (Group * 1)()
+        arr[0].src, arr[0].channels, arr[0].frames = field_dev.ptr, cw, 2
+        arr[0].src_h, arr[0].src_w, arr[0].raw = self.H, self.W, 1
+        ip = lambda a: np.ascontiguousarray(a, np.int32).ctypes.data
+        _lib.check(_lib.lib().dl4ds_batch_gather(ctypes.addressof(arr), 1, ip(idx), ip(cy), ip(cx), out.ptr, self.psy, self.psx, 1,
+                                                 self.batch_size))
+        return out
+
     def _draw(self, index):
         return self._draw_for(self.indices[index * self.batch_size:(index + 1) * self.batch_size])
 
@@ -656,6 +693,7 @@ class DeviceDataGenerator:
         idx, cy, cx = self._draw_for(sample_indices)
         if len(idx) != self.batch_size:
             raise IndexError('incomplete batch')
+        self.last_draw = (idx, cy, cx)
         lr, hr, st = self._bufs[self._turn]
         self._turn ^= 1
         ip = lambda a: np.ascontiguousarray(a, np.int32).ctypes.data

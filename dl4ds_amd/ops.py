@@ -311,12 +311,38 @@ def channel_attention_bwd(x, dy, w1, b1, w2, b2):
     return dx.numpy(), g1.numpy().reshape(np.shape(w1)), gb1.numpy(), g2.numpy().reshape(np.shape(w2)), gb2.numpy()
 
 
-def loss(kind, y_true, y_pred, want_grad=True):
+def weight_form(shape, batch_shape):
+    """(w_batch, w_channels) of a loss-weight array of `shape` for a (N, H, W, C) batch: (H, W), (H, W, 1) and (H, W, C) are one map
+    shared by all samples; (M, H, W, 1) and (M, H, W, C) are M maps, M a divisor of N, sample row r using map r // (N // M) -- M = N:
+    one map per sample; M = N / nmul: one per sample of a spatio-temporal output of nmul frames.  ValueError for anything else."""
+    n, h, w, c = (int(v) for v in batch_shape)
+    shape = tuple(int(v) for v in shape)
+    if shape == (h, w):
+        return 1, 1
+    if len(shape) == 3 and shape[:2] == (h, w) and shape[2] in (1, c):
+        return 1, shape[2]
+    if len(shape) == 4 and shape[1:3] == (h, w) and shape[3] in (1, c) and shape[0] >= 1 and n % shape[0] == 0:
+        return shape[0], shape[3]
+    raise ValueError(f'loss weights of shape {shape} do not fit a batch of shape {(n, h, w, c)}: expected (H, W), (H, W, 1), '
+                     f'(H, W, C) or (M, H, W, 1 | C) with M a divisor of the batch size')
+
+
+def loss(kind, y_true, y_pred, want_grad=True, weights=None):
+    """Loss value and dloss/dpred.  weights: per-grid-cell weights, float32, finite, >= 0, in one of the forms of `weight_form`
+    (semantics: dl4ds_op_loss_weighted in include/dl4ds_hip.h -- entries with weight 0 are excluded by selection, the multi-scale
+    kinds are refused)."""
     n, h, w, c = y_true.shape
+    if weights is not None and kind.startswith('msdssim'):
+        raise ValueError(f'loss weights are not available for the multi-scale kind {kind!r}')
     dt, dp = _d(y_true), _d(y_pred)
     g = DeviceArray.zeros(y_pred.shape) if want_grad else None
     lv = DeviceArray.zeros((8,))
-    _lib.check(_lib.lib().dl4ds_op_loss(LOSS_KINDS[kind], dt.ptr, dp.ptr, _p(g), n, h, w, c, lv.ptr))
+    if weights is None:
+        _lib.check(_lib.lib().dl4ds_op_loss(LOSS_KINDS[kind], dt.ptr, dp.ptr, _p(g), n, h, w, c, lv.ptr))
+    else:
+        wb, wc = weight_form(np.shape(weights), y_true.shape)
+        dw = _d(weights)
+        _lib.check(_lib.lib().dl4ds_op_loss_weighted(LOSS_KINDS[kind], dt.ptr, dp.ptr, _p(g), n, h, w, c, dw.ptr, wb, wc, lv.ptr))
     return float(lv.numpy()[0]), (g.numpy() if want_grad else None)
 
 

@@ -18,7 +18,7 @@ class CGANTrainer(Trainer):
                  epochs=60, batch_size=16, learning_rates=(2e-4, 2e-4), device='GPU', gpu_memory_growth=True,
                  model_list=None, steps_per_epoch=None, interpolation='inter_area', static_vars=None,
                  checkpoints_frequency=0, save=False, save_path=None, save_logs=False, save_loss_history=True,
-                 generator_params={}, discriminator_params={}, verbose=True):
+                 generator_params={}, discriminator_params={}, verbose=True, loss_weights=None):
         super().__init__(backbone=backbone, upsampling=upsampling, data_train=data_train, data_train_lr=data_train_lr,
                          time_window=time_window, loss=loss, batch_size=batch_size, patch_size=patch_size, scale=scale,
                          device=device, gpu_memory_growth=gpu_memory_growth, verbose=verbose, model_list=model_list,
@@ -40,6 +40,12 @@ class CGANTrainer(Trainer):
         if self.time_window is not None and not self.model_is_spatiotemporal:
             self.time_window = None
         self.gentotal, self.gengan, self.genpxloss, self.disc = [], [], [], []
+        # loss_weights: a full-field (H, W[, C]) map of per-grid-cell weights of the PIXEL loss on the HR grid of `data_train`
+        # (losses.check_loss_weights); the adversarial terms are untouched.  With `patch_size` it is cropped at every batch's corners
+        self.loss_weights = None
+        if loss_weights is not None:
+            from ..losses import check_loss_weights
+            self.loss_weights = check_loss_weights(loss_weights, self.data_train.shape[-3:], self.lossf)
 
     def setup_model(self):
         """cgan.py:174-262."""
@@ -94,6 +100,16 @@ class CGANTrainer(Trainer):
                                       time_window=self.time_window, static_vars=self.static_vars,
                                       predictors=self.predictors_train, interpolation=self.interpolation)
             dev.rng = rng
+        lw_dev = None
+        if self.loss_weights is not None:
+            if self.patch_size is None:
+                self.engine.set_loss_weights(self.loss_weights)
+            elif dev is None:
+                raise ValueError('`loss_weights` together with `patch_size` needs the device-resident generator (static variables): '
+                                 'the host batch loop does not expose its crop corners')
+            else:
+                from ..device import DeviceArray
+                lw_dev = DeviceArray.from_numpy(self.loss_weights)
         first = True
         for epoch in range(self.epochs):
             idx = parallel.shard_indices(n_samples, self.rank, self.world, seed=17, epoch=epoch)
@@ -101,6 +117,8 @@ class CGANTrainer(Trainer):
             for i in range(steps):
                 if dev is not None:
                     (lr_dev, aux_dev), (hr_dev,) = dev.prepare(idx[i * self.batch_size:(i + 1) * self.batch_size])
+                    if lw_dev is not None:
+                        self.engine.set_loss_weights(dev.crop_field(lw_dev))
                     losses = self.engine.step_device([lr_dev.ptr, aux_dev.ptr], hr_dev.ptr, self.batch_size,
                                                      want_losses=True)
                     if first and self.world > 1:
@@ -155,14 +173,37 @@ class CGANTrainer(Trainer):
         ev = SupervisedEngine(self.generator, loss=self.lossf, learning_rate=1e-3)     # evaluate() only: no update is made
         bs = int(max_batch or self.batch_size)
         tot, cnt = 0.0, 0
+        lw = getattr(self, 'loss_weights', None)
+        if lw is not None and self.patch_size is None:
+            ev.set_loss_weights(lw)
         for i in range(0, n_test, bs):
             chunk = idx[i:i + bs]
+            if lw is not None and self.patch_size is not None:
+                # patches: the crops of the map come from the device generator, which keeps its corners
+                if len(chunk) < bs:
+                    continue
+                tg = getattr(self, '_test_gen', None)
+                if tg is None:
+                    from ..device import DeviceArray
+                    tg = self._test_gen = DeviceDataGenerator(data_test, data_test_lr, self.backbone, self.upsampling, self.scale,
+                                                              batch_size=bs, patch_size=self.patch_size,
+                                                              time_window=self.time_window, static_vars=self.static_vars,
+                                                              predictors=self.predictors_test, interpolation=self.interpolation)
+                    tg.rng = rng
+                    self._test_lw_dev = DeviceArray.from_numpy(lw)
+                (lr_dev, aux_dev), (hr_dev,) = tg.prepare(chunk)
+                ev.set_loss_weights(tg.crop_field(self._test_lw_dev))
+                tot += ev.evaluate_device([lr_dev.ptr, aux_dev.ptr], hr_dev.ptr, bs) * bs
+                cnt += bs
+                continue
             (lr_array, aux_hr), (hr_array,) = create_batch_hr_lr(
                 chunk, 0, data_test, data_test_lr, upsampling=self.upsampling, scale=self.scale, batch_size=len(chunk),
                 patch_size=self.patch_size, time_window=self.time_window, static_vars=self.static_vars, predictors=preds,
                 interpolation=self.interpolation, rng=rng)
             tot += ev.evaluate([lr_array, aux_hr], hr_array) * len(chunk)
             cnt += len(chunk)
+        if cnt == 0:
+            return
         self.test_loss = tot / cnt
         if self.verbose:
             print(f'\n{self.lossf} on the test set: {self.test_loss}')

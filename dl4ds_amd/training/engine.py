@@ -7,7 +7,7 @@ from collections import OrderedDict
 import numpy as np
 
 from .. import _lib
-from ..ops import LOSS_KINDS
+from ..ops import LOSS_KINDS, weight_form
 
 
 def _lr_schedule(learning_rate, lr_decay_after):
@@ -19,6 +19,28 @@ def _lr_schedule(learning_rate, lr_decay_after):
     return float(learning_rate), float(learning_rate), 1e30
 
 
+def _set_loss_weights(engine, setter, model, loss, w):
+    """Shared by both engines: hand a weight array (numpy or DeviceArray; None clears) to the library.  (H, W), (H, W, 1) and
+    (H, W, C) are one map for every sample; (B, H, W, 1 | C) is one map per sample of the following steps (all frames of a
+    spatio-temporal sample use their sample's map)."""
+    if w is None:
+        _lib.check(setter(engine.h, None, 0, 0, 0, 0, 0))
+        engine._loss_weights = None
+        return
+    if loss.startswith('msdssim'):
+        raise ValueError(f'loss weights are not available for the multi-scale kind {loss!r}')
+    out = tuple(model.output_shape)
+    h, wd, c = out[-3:]
+    is_dev = hasattr(w, 'ptr')
+    if not is_dev:
+        w = np.ascontiguousarray(getattr(w, 'values', w), np.float32)
+    shape = tuple(w.shape)
+    per_sample = len(shape) == 4
+    wb, wc = weight_form(shape, ((shape[0] if per_sample else 1), h, wd, c))
+    _lib.check(setter(engine.h, w.ptr if is_dev else w.ctypes.data, wb, h, wd, wc, 0 if is_dev else 1))
+    engine._loss_weights = w            # the copy is asynchronous: the source stays alive until it is replaced
+
+
 class SupervisedEngine:
     """fit() inner step of SupervisedTrainer.run (supervised.py:353,396-406)."""
 
@@ -27,6 +49,7 @@ class SupervisedEngine:
         if loss not in LOSS_KINDS:
             raise ValueError(f'loss {loss!r} not available on the MI355X path; one of {sorted(LOSS_KINDS)}')
         self.model = model
+        self.loss = loss
         self._l = _lib.lib()
         lr0, lr1, boundary = _lr_schedule(learning_rate, lr_decay_after)
         h = ctypes.c_void_p()
@@ -41,6 +64,15 @@ class SupervisedEngine:
                 self.h = None
         except Exception:
             pass
+
+    def set_loss_weights(self, w):
+        """Per-grid-cell weights of the loss (masks, area weights; semantics: dl4ds_op_loss_weighted in include/dl4ds_hip.h), numpy
+        or DeviceArray: (H, W), (H, W, 1) or (H, W, C) for one map shared by all samples, (B, H, W, 1 | C) for one map per sample of
+        the following steps.  In force for step, loss_and_grads and evaluate (and their _device forms) until replaced; None clears.
+
+        Data parallel: each rank normalises by its own sum of weights, so the average over ranks is the exact global weighted mean
+        for a shared map (equal batch sizes) and an approximation for per-sample crops, whose weight sums differ between ranks."""
+        _set_loss_weights(self, self._l.dl4ds_trainer_set_loss_weights, self.model, self.loss, w)
 
     def _host_args(self, inputs, y_true):
         inputs, b = self.model._prep_inputs(inputs)
@@ -165,6 +197,7 @@ class CGANEngine:
             raise ValueError(f'loss {loss!r} not available on the MI355X path; one of {sorted(LOSS_KINDS)}')
         genlr, dislr = cgan_learning_rates(learning_rate)
         self.generator, self.discriminator = generator, discriminator
+        self.loss = loss
         self.learning_rates = (genlr, dislr)
         self._l = _lib.lib()
         h = ctypes.c_void_p()
@@ -180,6 +213,11 @@ class CGANEngine:
                 self.h = None
         except Exception:
             pass
+
+    def set_loss_weights(self, w):
+        """Per-grid-cell weights of the generator's PIXEL loss (same forms and semantics as SupervisedEngine.set_loss_weights,
+        including the data-parallel note); the adversarial terms are untouched.  None clears."""
+        _set_loss_weights(self, self._l.dl4ds_cgan_set_loss_weights, self.generator, self.loss, w)
 
     def step(self, gen_inputs, hr_array, dropout_keep=None, apply_update=True):
         """Returns (gen_total_loss, gen_gan_loss, gen_px_loss, disc_loss).  dropout_keep: optional (2B, C) keep-mask

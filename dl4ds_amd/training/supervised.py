@@ -23,7 +23,8 @@ class SupervisedTrainer(Trainer):
                  device='GPU', gpu_memory_growth=True, use_multiprocessing=False, model_list=None,
                  learning_rate=(1e-3, 1e-4), lr_decay_after=1e5, early_stopping=False, patience=6, min_delta=0,
                  show_plot=True, save=False, save_path=None, save_bestmodel=False, trained_model=None,
-                 trained_epochs=0, verbose=True, checkpoint=None, device_data=True, **architecture_params):
+                 trained_epochs=0, verbose=True, checkpoint=None, device_data=True, loss_weights=None,
+                 **architecture_params):
         super().__init__(backbone=backbone, upsampling=upsampling, data_train=data_train, data_train_lr=data_train_lr,
                          time_window=time_window, loss=loss, batch_size=batch_size, patch_size=patch_size, scale=scale,
                          device=device, gpu_memory_growth=gpu_memory_growth, use_multiprocessing=use_multiprocessing,
@@ -43,6 +44,16 @@ class SupervisedTrainer(Trainer):
         self.architecture_params = architecture_params
         self.trained_model, self.trained_epochs, self.save_bestmodel = trained_model, trained_epochs, save_bestmodel
         self.checkpoint, self.device_data = checkpoint, device_data
+        # loss_weights: a full-field (H, W[, C]) map of per-grid-cell loss weights on the HR grid of `data_train` (a 0/1 mask, cos
+        # latitude, ...; losses.check_loss_weights); the training, validation and test losses all use it.  With `patch_size` the map is
+        # cropped on the device at every batch's corners, which only the device-resident generator keeps
+        self.loss_weights = None
+        if loss_weights is not None:
+            from ..losses import check_loss_weights
+            self.loss_weights = check_loss_weights(loss_weights, self.data_train.shape[-3:], self.lossf)
+            if not device_data and patch_size is not None:
+                raise ValueError('`loss_weights` together with `patch_size` needs device_data=True: the host generator '
+                                 '(device_data=False) does not expose its crop corners')
 
     def setup_datagen(self):
         """supervised.py:220-240."""
@@ -98,8 +109,11 @@ class SupervisedTrainer(Trainer):
         shard's val_loss would leave the epoch loop at different epochs and strand the others in the all-reduce."""
         n = len(ds) if steps is None else min(int(steps), len(ds))
         tot = 0.0
+        lw_dev = getattr(self, '_loss_weights_dev', None)
         for i in range(n):
             x, y = ds[i]
+            if lw_dev is not None and self.patch_size is not None:
+                self.engine.set_loss_weights(ds.crop_field(lw_dev))      # this batch's crops of the map, one per sample
             if isinstance(ds, DeviceDataGenerator):
                 ptrs, b = [a.ptr for a in x], ds.batch_size
                 tot += (self.engine.step_device(ptrs, y[0].ptr, b, want_loss=True) if train
@@ -129,6 +143,13 @@ class SupervisedTrainer(Trainer):
         ckpt = getattr(self, 'checkpoint', None)
         if ckpt is not None:
             self.engine.load_checkpoint(ckpt)
+        self._loss_weights_dev = None
+        if getattr(self, 'loss_weights', None) is not None:
+            if self.patch_size is None:
+                self.engine.set_loss_weights(self.loss_weights)          # one map for every batch of the run
+            else:
+                from ..device import DeviceArray
+                self._loss_weights_dev = DeviceArray.from_numpy(self.loss_weights)
         if self.world > 1:
             parallel.broadcast_trainer(self.engine)            # BroadcastGlobalVariablesCallback(0)
         steps = self.steps_per_epoch

@@ -156,6 +156,19 @@ int dl4ds_op_chatt_bwd(const float* x_dev, const float* dy_dev, float* dx_dev, i
  * loss_dev[0] = loss ; dpred_dev = dloss/dpred (may be NULL). */
 int dl4ds_op_loss(int kind, const float* y_true_dev, const float* y_pred_dev, float* dpred_dev, int N, int H,
                   int W, int C, float* loss_dev);
+/* The same with per-grid-cell weights (masks, cos(latitude) area weights).  w_dev: float32, finite, >= 0, w_batch maps of
+ * (H, W, w_channels); w_batch must DIVIDE N and sample row r of the (N, H, W, C) batch uses map r / (N / w_batch) -- 1: one map shared by
+ * all samples, N: one map per sample (patch training), N / nmul: one map per sample of a spatio-temporal output of nmul frames;
+ * w_channels is 1 (the map serves every channel) or C.  With d = p - t and sums over all N*H*W*C entries (w broadcast):
+ *   mae_w = sum w|d| / sum w,  mse_w = sum w d^2 / sum w  (gradient 0 at d == 0; w == const > 0 reproduces the unweighted loss).
+ * An entry with w == 0 is excluded by selection: neither y_true nor y_pred there enters any sum and its gradient is exactly +0.0,
+ * also where y_true is NaN or Inf (MAE and MSE terms of every kind).  sum w == 0: loss 0 and dpred all zeros, never NaN.
+ * dssim kinds (2..5): window weights omega = G * w (G: the 11x11 Gaussian of the moments) over the VALID windows,
+ * term = sum omega (1 - ssim)/2 / sum omega over samples, windows and channels, windows with omega == 0 excluded; the dynamic range and
+ * positivity shift are those of the whole arrays as in the unweighted loss, so y_true must be finite everywhere for these kinds; the
+ * mixes keep 0.8/0.2 and 0.6/0.2/0.2 over the weighted terms.  The multi-scale kinds (6..8) are refused.  Bitwise reproducible. */
+int dl4ds_op_loss_weighted(int kind, const float* y_true_dev, const float* y_pred_dev, float* dpred_dev, int N, int H,
+                           int W, int C, const float* w_dev, int w_batch, int w_channels, float* loss_dev);
 /* compute_metrics (metrics.py:166-262) without the plots, on device-resident test arrays (N,H,W,C):
  *   pair_out_dev  [N][4]       per test pair: MAE, MSE, Pearson correlation over the grid, SSIM (tf.image.ssim with the
  *                              joint dynamic range; NaN when the grid is smaller than the 11x11 window).
@@ -542,6 +555,13 @@ int dl4ds_trainer_loss_and_grads(dl4ds_trainer* tr, const float* const* inputs, 
  * BatchNormalization moving-average update, dropout inactive unless it is an MC variant */
 int dl4ds_trainer_evaluate(dl4ds_trainer* tr, const float* const* inputs, int n_inputs, const float* y_true, int B,
                            int is_host, float* loss_host);
+/* per-grid-cell weights of the trainer's loss (semantics: dl4ds_op_loss_weighted).  w: w_batch maps of (H, W, w_channels), host
+ * (is_host) or device; copied into a trainer-owned buffer asynchronously on the library stream (a host array must stay alive until the
+ * next synchronising call) and in force for dl4ds_trainer_step / _loss_and_grads / _evaluate until replaced; w == NULL clears them and
+ * the unweighted kernels run again.  H, W must be those of output 0 and w_channels 1 or its channel count.  w_batch is 1 (shared map)
+ * or the batch size B of the following steps (one map per sample, every frame of a spatio-temporal sample uses its sample's map); a
+ * step whose B differs from a per-sample w_batch fails.  Trainers of a msdssim loss fail at the step. */
+int dl4ds_trainer_set_loss_weights(dl4ds_trainer* tr, const float* w, int w_batch, int H, int W, int w_channels, int is_host);
 int dl4ds_trainer_get_state(dl4ds_trainer* tr, float* m_host, float* v_host, long* step);
 /* restore the Adam slots (arena-sized host arrays) and optimizer.iterations -- resume from a checkpoint
  * (the reference resumes through tf.train.Checkpoint, cgan.py:288-292; supervised.py:322-325 re-uses a trained model) */
@@ -556,6 +576,8 @@ int dl4ds_cgan_create(dl4ds_graph* gen, dl4ds_graph* disc, int px_loss_kind, flo
                       dl4ds_trainer** tr);
 /* genlr, dislr = learning_rates (cgan.py:271-278): one Adam(beta_1=0.5) per model, each with its own rate */
 int dl4ds_cgan_set_learning_rates(dl4ds_trainer* tr, float gen_lr, float disc_lr);
+/* dl4ds_trainer_set_loss_weights for the CGAN step's pixel loss (gen_px and its gradient) only: the adversarial terms are untouched */
+int dl4ds_cgan_set_loss_weights(dl4ds_trainer* tr, const float* w, int w_batch, int H, int W, int w_channels, int is_host);
 int dl4ds_cgan_step(dl4ds_trainer* tr, const float* const* gen_inputs, int n_gen_inputs, const float* hr, int B,
                     int is_host, const float* dropout_keep_host, int apply_update, float* losses_host);
 /* Adam slots + optimizer.iterations of the generator (which = 0) / discriminator (which = 1) optimiser -- the contents of
