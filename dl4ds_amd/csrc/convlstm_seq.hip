@@ -687,7 +687,16 @@ static void trace_end(const char* what, const SeqParams& p, int grid, hipStream_
 static int seq_grid(const SeqParams& p) {
     static const int reserve = [] { const char* e = getenv("DL4DS_SEQ_RESERVE_CUS"); return e ? atoi(e) : 32; }();
     const int cus = std::max(cu_count() - (dist_active() ? reserve : 0), 8);
-    return std::min(p.ntiles, cus);
+    int grid = std::min(p.ntiles, cus);
+    // (tests: DL4DS_SEQ_GRID=<n> caps the grid -- several tiles per workgroup on small shapes.  It only ever LOWERS the grid, so
+    // co-residency holds as before; read at every launch, so that one graph can run under several caps)
+    if (const char* e = test_env("DL4DS_SEQ_GRID")) { const int n = atoi(e); if (n >= 1) grid = std::min(grid, n); }
+    return grid;
+}
+// DL4DS_SEQ_TAG_FORMS=1 (tests): the profiler tag also names the form that ran -- rows per wave, grid and number of tiles
+static std::string seq_form_tag(const SeqParams& p, int grid) {
+    if (!test_env("DL4DS_SEQ_TAG_FORMS")) return std::string();
+    return "tr" + std::to_string(p.tr) + "g" + std::to_string(grid) + "n" + std::to_string(p.ntiles);
 }
 
 // rows per wave.  Backward: 8 x 16 tiles while 16 x 16 tiles would give a workgroup fewer than two of them (see Geom; its
@@ -695,7 +704,8 @@ static int seq_grid(const SeqParams& p) {
 // (its hand-off is 8 KB and the smaller tiles' extra halo costs more than it hides).  Measured at 16 x 8 x 64^2, F = 8:
 // backward 5x5 184 -> 173 us, 3x3 123 -> 109 us per launch with two 8 x 16 tiles; forward 87 / 62 us with 16 x 16, 95 / 68 with 8 x 16.
 static int seq_tr(int H, int W, int B, bool backward) {
-    if (const char* e = exp_env("DL4DS_CONVLSTM_SEQ_TR")) return atoi(e) == 2 ? 2 : 4;
+    // (tests: either tiling for both directions, read at every launch; the flag area is sized for the finer one, graph_ops2.hip)
+    if (const char* e = test_env("DL4DS_CONVLSTM_SEQ_TR")) return atoi(e) == 2 ? 2 : 4;
     const long t16 = (long)cdiv(H, 16) * cdiv(W, 16) * B;
     return (backward && t16 < 2l * std::max(cu_count(), 8) && H > 8) ? 2 : 4;
 }
@@ -739,9 +749,9 @@ void convlstm_seq_forward(hipStream_t s, const float* U_il, float* Z_il, float* 
                           int B, int T, int H, int W, int KS, int F, int relu) {
     SeqParams p = seq_params(U_il, Z_il, C, Hrec, out, nullptr, nullptr, nullptr, flags, B, T, H, W, relu, false);
     const double px = (double)B * T * H * W;
-    ProfScope ps(s, "convlstm_seq_fwd<" + std::to_string(KS) + "," + std::to_string(F) + ">",
-                 2.0 * (double)B * (T - 1) * H * W * KS * KS * F * 4 * F, 4.0 * px * (4 * F * 2 + F * 4));
     const int grid = seq_grid(p);
+    ProfScope ps(s, "convlstm_seq_fwd<" + std::to_string(KS) + "," + std::to_string(F) + ">" + seq_form_tag(p, grid),
+                 2.0 * (double)B * (T - 1) * H * W * KS * KS * F * 4 * F, 4.0 * px * (4 * F * 2 + F * 4));
     trace_begin(p, grid, s);
 #define DL4DS_SEQ_CASE(K_, F_) if (KS == K_ && F == F_) { if (p.tr == 2) launch_fwd<K_, F_, 2>(s, p, grid); else launch_fwd<K_, F_, 4>(s, p, grid); trace_end("convlstm_seq_fwd", p, grid, s); return; }
     DL4DS_SEQ_CASE(3, 4) DL4DS_SEQ_CASE(3, 8) DL4DS_SEQ_CASE(3, 16) DL4DS_SEQ_CASE(5, 4) DL4DS_SEQ_CASE(5, 8)
@@ -754,9 +764,9 @@ void convlstm_seq_backward(hipStream_t s, const float* U_il, const float* Z_il, 
     SeqParams p = seq_params(U_il, const_cast<float*>(Z_il), const_cast<float*>(C), nullptr, const_cast<float*>(out), dout, dZ_il, dc,
                              flags, B, T, H, W, relu, true);
     const double px = (double)B * T * H * W;
-    ProfScope ps(s, "convlstm_seq_bwd<" + std::to_string(KS) + "," + std::to_string(F) + ">",
-                 2.0 * (double)B * (T - 1) * H * W * KS * KS * F * 4 * F, 4.0 * px * (4 * F * 2 + F * 6));
     const int grid = seq_grid(p);
+    ProfScope ps(s, "convlstm_seq_bwd<" + std::to_string(KS) + "," + std::to_string(F) + ">" + seq_form_tag(p, grid),
+                 2.0 * (double)B * (T - 1) * H * W * KS * KS * F * 4 * F, 4.0 * px * (4 * F * 2 + F * 6));
     trace_begin(p, grid, s);
 #define DL4DS_SEQ_CASE(K_, F_) if (KS == K_ && F == F_) { if (p.tr == 2) launch_bwd<K_, F_, 2>(s, p, grid); else launch_bwd<K_, F_, 4>(s, p, grid); trace_end("convlstm_seq_bwd", p, grid, s); return; }
     DL4DS_SEQ_CASE(3, 4) DL4DS_SEQ_CASE(3, 8) DL4DS_SEQ_CASE(3, 16) DL4DS_SEQ_CASE(5, 4) DL4DS_SEQ_CASE(5, 8)

@@ -1217,17 +1217,11 @@ def test_conv_lstm2d(B, Tn, H, W, C, F, KS, relu):
     """ConvLSTM2D(F, k, 'same', return_sequences=True) [+ ReLU] as ONE op (blocks.py:350-355; gates i, f, c, o,
     hard-sigmoid recurrent activation, h0 = c0 = 0): output and -- through an MSE loss -- dX, dK (input kernel), dU
     (recurrent kernel) and db against the fp64 torch oracle, every gradient at its own scale."""
-    import ctypes
-    from dl4ds_amd import _lib
-    from dl4ds_amd.graph import GraphBuilder, Model
-    from dl4ds_amd.training import SupervisedEngine
-    from tests.parity import assert_matches_reference, banded_reference
+    from tests.convlstm_op import OneOp, assert_against_fp64
+    from tests.parity import banded_reference
     r = np.random.default_rng(1000 * KS + 10 * F + C + H)
-    gb = GraphBuilder()
-    xin = gb.input(H, W, C, nmul=Tn, requires_grad=True)
-    out = gb.convlstm(xin, 'lstm', F, KS, Tn, activation='relu' if relu else None)
-    gb.finalize(out, seed=1)
-    model = Model(gb, 'convlstm_only', [(Tn, H, W, C)])
+    op = OneOp(Tn, H, W, C, F, KS, relu)          # (the graph and the three assertions are shared with tests/test_gpu_convlstm.py)
+    model = op.model
     w = model.get_weights()
     w['lstm/bias'] = (w['lstm/bias'] + 0.1 * r.standard_normal(4 * F)).astype(np.float32)
     # inputs large enough that the hard sigmoids saturate in places (both clip branches of the backward pass run)
@@ -1255,16 +1249,9 @@ def test_conv_lstm2d(B, Tn, H, W, C, F, KS, relu):
         return float(loss), {'x': gx, 'lstm/kernel': gk, 'lstm/recurrent_kernel': gu, 'lstm/bias': gb_}, out.detach()
     # reference = mid-point of the evaluations with the hard-sigmoid / ReLU kinks displaced by +/- 4e-6, tests/parity.py
     ref = banded_reference(call)
-    got = model([x])
-    close(got, ref['pred'])
-    eng = SupervisedEngine(model, loss='mse', learning_rate=1e-3)
-    l_hip, g_hip = eng.loss_and_grads([x], y)
-    assert l_hip == pytest.approx(ref['loss'], rel=1e-4)
-    p = ctypes.c_void_p()
-    _lib.check(_lib.lib().dl4ds_graph_tensor_ptr(gb.h, xin.id, 1, ctypes.byref(p)))
-    dx = np.empty(x.shape, np.float32)
-    _lib.check(_lib.lib().dl4ds_memcpy_d2h(dx.ctypes.data, p, dx.nbytes))
-    assert_matches_reference(dict(g_hip, x=dx), ref, what=(B, Tn, H, W, C, F, KS, relu))
+    got, l_hip, grads = op.run(x, y)
+    # close(got, ref['pred']); l_hip == approx(ref['loss'], rel=1e-4); assert_matches_reference(grads incl. dX, ref)
+    assert_against_fp64(got, l_hip, grads, ref, what=(B, Tn, H, W, C, F, KS, relu))
 
 
 def test_device_side_error_word_fails_the_next_host_wait_once():
