@@ -18,6 +18,11 @@ void trainer_evaluate(Trainer& t, const float* const* inputs, int n_inputs, cons
 void trainer_loss_and_grads(Trainer& t, const float* const* inputs, int n_inputs, const float* y_true, int B, bool is_host,
                             bool reduce_across_ranks);
 void trainer_step(Trainer& t, const float* const* inputs, int n_inputs, const float* y_true, int B, bool is_host, float* loss_host);
+void trainer_set_optimizer_ext(Trainer& t, float clipnorm, float weight_decay, const int* decay_param_ids, int n_ids, float ema_momentum);
+void trainer_optimizer_stats(Trainer& t, float* norm, float* factor, long* skipped);
+void trainer_ema_swap(Trainer& t);
+void trainer_ema_get(Trainer& t, float* host);
+void trainer_ema_set(Trainer& t, const float* host);
 struct CganTrainer;
 CganTrainer* cgan_create(Graph* gen, Graph* disc, int px_loss_kind, float lr, float beta1, float lam);
 void cgan_destroy(CganTrainer* t);
@@ -682,6 +687,34 @@ int dl4ds_op_adam(float* w, const float* g, float* m, float* v, size_t n, int t,
     adam_update(S(), w, g, m, v, n, lr_t, beta1, beta2, eps, grad_scale, device_error_word_if_any());       // (skips the update once the sticky word is set)
     API_END
 }
+int dl4ds_op_adam_ext(float* w, const float* g, float* m, float* v, float* ema, size_t n, int t, float lr, float beta1, float beta2,
+                      float eps, float grad_scale, float global_clipnorm, float weight_decay, const size_t* decay_ranges_host,
+                      int n_ranges, float ema_momentum, float* stats_out_dev) {
+    API_BEGIN
+    DL4DS_REQUIRE(global_clipnorm >= 0.f && std::isfinite(global_clipnorm), "global_clipnorm must be finite and > 0 (0: off)");
+    DL4DS_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), "weight_decay must be finite and >= 0");
+    DL4DS_REQUIRE(!ema || (ema_momentum >= 0.f && ema_momentum < 1.f), "ema_momentum must be in [0, 1)");
+    DL4DS_REQUIRE(stats_out_dev, "stats_out_dev is required");
+    DL4DS_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || decay_ranges_host), "decay_ranges_host missing");
+    const float lr_t = (float)((double)lr * std::sqrt(1.0 - std::pow((double)beta2, (double)t)) /
+                               (1.0 - std::pow((double)beta1, (double)t)));
+    static std::vector<size_t> b;              // (static: the upload below is asynchronous, as in upload_index_lists)
+    b = decay_bounds(decay_ranges_host, n_ranges, n);
+    // one scratch carve: the norm's fp64 partials, then the table
+    const size_t part_bytes = (size_t)sqnorm_blocks(n) * sizeof(double);
+    char* base = reinterpret_cast<char*>(scratch(part_bytes + std::max<size_t>(b.size(), 1) * sizeof(size_t)));
+    size_t* bounds_dev = reinterpret_cast<size_t*>(base + part_bytes);
+    if (!b.empty()) HIP_CHECK(hipMemcpyAsync(bounds_dev, b.data(), b.size() * sizeof(size_t), hipMemcpyHostToDevice, S()));
+    adam_ext_update(S(), w, g, m, v, ema, n, lr_t, beta1, beta2, eps, grad_scale, global_clipnorm, lr, weight_decay,
+                    b.empty() ? nullptr : bounds_dev, (int)b.size(), ema_momentum, reinterpret_cast<double*>(base), stats_out_dev,
+                    device_error_word_if_any());
+    API_END
+}
+int dl4ds_op_arena_swap(float* a, float* b, size_t n) {
+    API_BEGIN
+    arena_swap(S(), a, b, n);
+    API_END
+}
 
 // ------------------------------------------------------------------------------------------------ graph
 int dl4ds_graph_create(dl4ds_graph** g) {
@@ -1124,6 +1157,65 @@ int dl4ds_cgan_set_state(dl4ds_trainer* tr, int which, const float* m_host, cons
     t.step = step;
     API_END
 }
+int dl4ds_trainer_set_optimizer_ext(dl4ds_trainer* tr, float global_clipnorm, float weight_decay, const int* decay_param_ids, int n_ids,
+                                    float ema_momentum) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    trainer_set_optimizer_ext(*tr->t, global_clipnorm, weight_decay, decay_param_ids, n_ids, ema_momentum);
+    API_END
+}
+int dl4ds_trainer_optimizer_stats(dl4ds_trainer* tr, float* norm, float* factor, long* skipped) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    trainer_optimizer_stats(*tr->t, norm, factor, skipped);
+    API_END
+}
+int dl4ds_trainer_ema_swap(dl4ds_trainer* tr) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    trainer_ema_swap(*tr->t);
+    API_END
+}
+int dl4ds_trainer_ema_get(dl4ds_trainer* tr, float* host) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    trainer_ema_get(*tr->t, host);
+    API_END
+}
+int dl4ds_trainer_ema_set(dl4ds_trainer* tr, const float* host) {
+    API_BEGIN
+    DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
+    trainer_ema_set(*tr->t, host);
+    API_END
+}
+int dl4ds_cgan_set_optimizer_ext(dl4ds_trainer* tr, int which, float global_clipnorm, float weight_decay, const int* decay_param_ids,
+                                 int n_ids, float ema_momentum) {
+    API_BEGIN
+    Trainer& t = cgan_side(tr, which);
+    DL4DS_REQUIRE(which == 0 || ema_momentum < 0.f, "the weight average belongs to the generator: pass a negative ema_momentum for the discriminator");
+    trainer_set_optimizer_ext(t, global_clipnorm, weight_decay, decay_param_ids, n_ids, ema_momentum);
+    API_END
+}
+int dl4ds_cgan_optimizer_stats(dl4ds_trainer* tr, int which, float* norm, float* factor, long* skipped) {
+    API_BEGIN
+    trainer_optimizer_stats(cgan_side(tr, which), norm, factor, skipped);
+    API_END
+}
+int dl4ds_cgan_ema_swap(dl4ds_trainer* tr) {
+    API_BEGIN
+    trainer_ema_swap(cgan_side(tr, 0));
+    API_END
+}
+int dl4ds_cgan_ema_get(dl4ds_trainer* tr, float* host) {
+    API_BEGIN
+    trainer_ema_get(cgan_side(tr, 0), host);
+    API_END
+}
+int dl4ds_cgan_ema_set(dl4ds_trainer* tr, const float* host) {
+    API_BEGIN
+    trainer_ema_set(cgan_side(tr, 0), host);
+    API_END
+}
 int dl4ds_trainer_last_loss(dl4ds_trainer* tr, float* loss_host) {
     API_BEGIN
     DL4DS_REQUIRE(tr && tr->t, "not a supervised trainer");
@@ -1191,6 +1283,7 @@ int dl4ds_dist_broadcast_trainer(dl4ds_trainer* tr, int root) {
         dist_broadcast(t->g->W, t->g->n_params, root, S());
         dist_broadcast(t->m, t->g->n_params, root, S());
         dist_broadcast(t->v, t->g->n_params, root, S());
+        if (t->ext.ema_on) dist_broadcast(t->ext.ema, t->g->n_params, root, S());
     }
     HIP_CHECK(hipStreamSynchronize(S()));
     for (Trainer* t : ts) dist_broadcast_i64(&t->step, root);     // optimizer.iterations (a resumed rank 0)

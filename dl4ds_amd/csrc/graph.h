@@ -235,9 +235,25 @@ struct LossWeightMap {
 void loss_weight_map_set(LossWeightMap& m, hipStream_t s, const float* w, int w_batch, int H, int W, int ch, bool is_host,
                          const GTensor& out);
 
+// The optimiser's extensions (adam_ext.hip; trainer_set_optimizer_ext).  All off: trainer_apply_adam calls adam_update as before.
+struct OptExt {
+    float clipnorm = 0.f;          // global_clipnorm; 0: off
+    float weight_decay = 0.f;      // decoupled (AdamW); applies inside `bounds`
+    bool ema_on = false;
+    float ema_momentum = 0.f;
+    float* ema = nullptr;          // shadow arena (the averages), allocated while ema_on
+    size_t* bounds = nullptr;      // device copy of decay_bounds()
+    int n_bounds = 0;
+    double* partials = nullptr;    // sqnorm_blocks(n_params) fp64 partials of the norm launch
+    float* stats = nullptr;        // device words: norm, clip factor, skipped steps (unsigned)
+    bool any() const { return clipnorm > 0.f || (weight_decay > 0.f && n_bounds > 0) || ema_on; }
+    ~OptExt();
+};
+
 struct Trainer {
     Graph* g = nullptr;
     AdamCfg cfg;
+    OptExt ext;
     float* m = nullptr;
     float* v = nullptr;
     long step = 0;                 // optimizer.iterations

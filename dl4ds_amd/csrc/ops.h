@@ -1,6 +1,7 @@
 // Internal C++ launch API of the gfx950 kernels (one stream argument everywhere; no hidden syncs).
 #pragma once
 #include "common.h"
+#include <vector>
 
 // ----------------------------------------------------------------------------- conv (conv.hip)
 // y = epilogue(conv_same_stride1(x, w)) ; w is HWIO flattened [KS*KS][Cin][Cout]
@@ -301,6 +302,18 @@ void bce_forward_backward(hipStream_t s, const float* p, float label, int n, flo
 // Keras Adam on a flat arena. lr_t = lr*sqrt(1-b2^t)/(1-b1^t) computed by the caller.
 void adam_update(hipStream_t s, float* w, const float* g, float* m, float* v, size_t n, float lr_t,
                  float beta1, float beta2, float eps, float grad_scale, const unsigned* err_word = nullptr);   // err_word: see runtime.h
+// The same step with global-norm clipping, decoupled weight decay and a weight average (adam_ext.hip; at most two launches).
+//   clipnorm 0: no clipping (no norm launch, factor 1);  weight_decay applies inside the table `bounds_dev` (decay_bounds, uploaded by
+//   the caller; null or n_bounds 0: nowhere) with the plain scheduled `lr`;  ema null: no average.
+//   partials_dev: sqnorm_blocks(n) doubles (clipping only);  stats_dev: [0] fl32 norm (0 without clipping) [1] clip factor
+//   [2] count of steps skipped for a non-finite norm, a 32-bit unsigned integer that the kernel increments in place.
+void adam_ext_update(hipStream_t s, float* w, const float* g, float* m, float* v, float* ema, size_t n, float lr_t, float beta1,
+                     float beta2, float eps, float grad_scale, float clipnorm, float lr, float weight_decay, const size_t* bounds_dev,
+                     int n_bounds, float ema_momentum, double* partials_dev, float* stats_dev, const unsigned* err_word = nullptr);
+int sqnorm_blocks(size_t n);                  // blocks (= fp64 partials) of the norm launch: a function of n alone, at most 1024
+// [begin, end) element ranges of an arena of n (any order, may touch or overlap) -> the sorted bounds b0 < e0 < b1 < e1 < ...
+std::vector<size_t> decay_bounds(const size_t* ranges, int n_ranges, size_t n);
+void arena_swap(hipStream_t s, float* a, float* b, size_t n);         // exchanges two arenas element by element (exact)
 
 // ------------------------------------------------------------- batch preparation (batchprep.hip), "next" row f1
 // Gathers one training batch from a device-resident dataset: block-mean coarsening (cv2 INTER_AREA at an integer

@@ -5,6 +5,7 @@
 #include "runtime.h"
 #include "dist.h"
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 Trainer::~Trainer() {
@@ -13,6 +14,13 @@ Trainer::~Trainer() {
     if (d_loss) (void)hipFree(d_loss);
     if (loss_ws) (void)hipFree(loss_ws);
     if (y_true) (void)hipFree(y_true);
+}
+
+OptExt::~OptExt() {
+    if (ema) (void)hipFree(ema);
+    if (bounds) (void)hipFree(bounds);
+    if (partials) (void)hipFree(partials);
+    if (stats) (void)hipFree(stats);
 }
 
 LossWeightMap::~LossWeightMap() {
@@ -167,8 +175,92 @@ void trainer_apply_adam(Trainer& t) {
                                (1.0 - std::pow((double)t.cfg.beta1, tt)));
     int rank = 0, world = 1;
     dist_world(rank, world);
-    adam_update(g.stream, g.W, g.G, t.m, t.v, g.n_params, lr_t, t.cfg.beta1, t.cfg.beta2, t.cfg.eps,
-                1.f / (float)world, device_error_word_if_any());
+    if (!t.ext.any()) {
+        adam_update(g.stream, g.W, g.G, t.m, t.v, g.n_params, lr_t, t.cfg.beta1, t.cfg.beta2, t.cfg.eps,
+                    1.f / (float)world, device_error_word_if_any());
+        return;
+    }
+    // clipping / weight decay / weight average (adam_ext.hip).  Data parallel: this runs behind dist_allreduce_wait, so the norm is
+    // that of the SUMMED arena, the same bits on every rank, and 1/world reaches it through grad_scale.  t.step above counts
+    // ATTEMPTED steps: a step the kernel skips for a non-finite norm still advances the schedule and the bias correction.
+    OptExt& x = t.ext;
+    adam_ext_update(g.stream, g.W, g.G, t.m, t.v, x.ema_on ? x.ema : nullptr, g.n_params, lr_t, t.cfg.beta1, t.cfg.beta2, t.cfg.eps,
+                    1.f / (float)world, x.clipnorm, lr, x.weight_decay, x.bounds, x.n_bounds, x.ema_momentum, x.partials, x.stats,
+                    device_error_word_if_any());
+}
+
+// dl4ds_trainer_set_optimizer_ext / dl4ds_cgan_set_optimizer_ext: between steps, any number of times.  ema_momentum < 0: no average.
+void trainer_set_optimizer_ext(Trainer& t, float clipnorm, float weight_decay, const int* decay_param_ids, int n_ids,
+                               float ema_momentum) {
+    Graph& g = *t.g;
+    OptExt& x = t.ext;
+    DL4DS_REQUIRE(clipnorm >= 0.f && std::isfinite(clipnorm), "global_clipnorm must be finite and > 0 (0: off)");
+    DL4DS_REQUIRE(weight_decay >= 0.f && std::isfinite(weight_decay), "weight_decay must be finite and >= 0");
+    DL4DS_REQUIRE(ema_momentum < 1.f, "ema_momentum must be in [0, 1) (negative: no average)");
+    DL4DS_REQUIRE(n_ids >= 0 && (n_ids == 0 || decay_param_ids), "decay_param_ids missing");
+    std::vector<size_t> ranges;
+    for (int k = 0; k < n_ids; ++k) {
+        const GParam& p = g.params.at(decay_param_ids[k]);
+        ranges.push_back(p.offset);
+        ranges.push_back(p.offset + p.n);
+    }
+    const std::vector<size_t> b = decay_bounds(ranges.data(), n_ids, g.n_params);
+    HIP_CHECK(hipStreamSynchronize(g.stream));               // a step in flight still reads the old table / average
+    if (x.bounds) { HIP_CHECK(hipFree(x.bounds)); x.bounds = nullptr; }
+    x.n_bounds = 0;
+    if (!b.empty()) {
+        HIP_CHECK(hipMalloc((void**)&x.bounds, b.size() * sizeof(size_t)));
+        HIP_CHECK(hipMemcpy(x.bounds, b.data(), b.size() * sizeof(size_t), hipMemcpyHostToDevice));
+        x.n_bounds = (int)b.size();
+    }
+    if (!x.partials) HIP_CHECK(hipMalloc((void**)&x.partials, (size_t)sqnorm_blocks(g.n_params) * sizeof(double)));
+    if (!x.stats) {
+        const float init[4] = {0.f, 1.f, 0.f, 0.f};          // norm, factor, skipped (the integer 0), spare
+        HIP_CHECK(hipMalloc((void**)&x.stats, sizeof(init)));
+        HIP_CHECK(hipMemcpy(x.stats, init, sizeof(init), hipMemcpyHostToDevice));
+    }
+    x.clipnorm = clipnorm;
+    x.weight_decay = weight_decay;
+    const bool want_ema = ema_momentum >= 0.f;
+    const size_t bytes = std::max<size_t>(g.n_params, 4) * sizeof(float);
+    if (want_ema && !x.ema_on) {
+        // the Keras optimiser's `average` slots start as copies of the variables
+        HIP_CHECK(hipMalloc((void**)&x.ema, bytes));
+        HIP_CHECK(hipMemcpy(x.ema, g.W, bytes, hipMemcpyDeviceToDevice));
+    } else if (!want_ema && x.ema_on) {
+        HIP_CHECK(hipFree(x.ema));
+        x.ema = nullptr;
+    }
+    x.ema_on = want_ema;
+    x.ema_momentum = want_ema ? ema_momentum : 0.f;
+}
+
+void trainer_optimizer_stats(Trainer& t, float* norm, float* factor, long* skipped) {
+    float h[3] = {0.f, 1.f, 0.f};
+    if (t.ext.stats) {
+        HIP_CHECK(hipMemcpyAsync(h, t.ext.stats, sizeof(h), hipMemcpyDeviceToHost, t.g->stream));
+        dist_stream_sync(t.g->stream, "optimizer_stats");
+    }
+    unsigned k = 0;
+    std::memcpy(&k, &h[2], sizeof(k));
+    if (norm) *norm = h[0];
+    if (factor) *factor = h[1];
+    if (skipped) *skipped = (long)k;
+}
+
+void trainer_ema_swap(Trainer& t) {
+    DL4DS_REQUIRE(t.ext.ema_on, "the weight average is off (set ema_momentum first)");
+    arena_swap(t.g->stream, t.g->W, t.ext.ema, t.g->n_params);
+}
+void trainer_ema_get(Trainer& t, float* host) {
+    DL4DS_REQUIRE(t.ext.ema_on && host, "the weight average is off (set ema_momentum first)");
+    HIP_CHECK(hipMemcpyAsync(host, t.ext.ema, t.g->n_params * sizeof(float), hipMemcpyDeviceToHost, t.g->stream));
+    HIP_CHECK(hipStreamSynchronize(t.g->stream));
+}
+void trainer_ema_set(Trainer& t, const float* host) {
+    DL4DS_REQUIRE(t.ext.ema_on && host, "the weight average is off (set ema_momentum first)");
+    HIP_CHECK(hipMemcpyAsync(t.ext.ema, host, t.g->n_params * sizeof(float), hipMemcpyHostToDevice, t.g->stream));
+    HIP_CHECK(hipStreamSynchronize(t.g->stream));
 }
 
 void trainer_step(Trainer& t, const float* const* inputs, int n_inputs, const float* y_true, int B, bool is_host,

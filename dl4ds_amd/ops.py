@@ -360,3 +360,51 @@ def adam(w, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0):
                                         float(beta2), float(eps), float(grad_scale)))
     sh = np.shape(w)
     return dw.numpy().reshape(sh), dm.numpy().reshape(sh), dv.numpy().reshape(sh)
+
+
+def merge_ranges(ranges):
+    """[begin, end) element ranges in any order -> the sorted list with touching and overlapping ranges merged and empty ones
+    dropped (what the library makes of a decayed set; csrc/adam_ext.hip: decay_bounds)."""
+    out = []
+    for b, e in sorted((int(b), int(e)) for b, e in ranges):
+        if b < 0 or e < b:
+            raise ValueError(f'not a range: [{b}, {e})')
+        if b == e:
+            continue
+        if out and b <= out[-1][1]:
+            out[-1][1] = max(out[-1][1], e)
+        else:
+            out.append([b, e])
+    return [(b, e) for b, e in out]
+
+
+def adam_ext(w, g, m, v, t, lr, beta1=0.9, beta2=0.999, eps=1e-7, grad_scale=1.0, global_clipnorm=None, weight_decay=0.0,
+             decay_ranges=(), ema=None, ema_momentum=0.0, skipped=0):
+    """dl4ds_op_adam_ext -> (w', m', v', ema' or None, {'grad_norm', 'clip_factor', 'skipped_steps'}); `skipped`: the count the
+    statistics words start with."""
+    dw, dg, dm, dv = (_d(np.asarray(a).reshape(-1)) for a in (w, g, m, v))
+    de = None if ema is None else _d(np.asarray(ema).reshape(-1))
+    n = dw.shape[0]
+    r = np.asarray(merge_ranges(decay_ranges), np.uint64).reshape(-1, 2)
+    if r.size and int(r.max()) > n:
+        raise ValueError(f'decay range beyond the {n} elements')
+    r = np.ascontiguousarray(r)
+    words = np.zeros(3, np.float32)
+    words.view(np.uint32)[2] = int(skipped)
+    st = DeviceArray.from_numpy(words)
+    _lib.check(_lib.lib().dl4ds_op_adam_ext(dw.ptr, dg.ptr, dm.ptr, dv.ptr, _p(de), n, int(t), float(lr), float(beta1), float(beta2),
+                                            float(eps), float(grad_scale), float(global_clipnorm or 0.0), float(weight_decay),
+                                            r.ctypes.data if len(r) else None, len(r), float(ema_momentum), st.ptr))
+    sh = np.shape(w)
+    words = st.numpy()
+    stats = dict(grad_norm=np.float32(words[0]), clip_factor=np.float32(words[1]), skipped_steps=int(words.view(np.uint32)[2]))
+    return (dw.numpy().reshape(sh), dm.numpy().reshape(sh), dv.numpy().reshape(sh), None if de is None else de.numpy().reshape(sh),
+            stats)
+
+
+def arena_swap(a, b):
+    """dl4ds_op_arena_swap (the kernel of the engines' swap_ema) -> (a', b') = (b, a)."""
+    da, db = _d(np.asarray(a).reshape(-1)), _d(np.asarray(b).reshape(-1))
+    assert da.shape == db.shape
+    _lib.check(_lib.lib().dl4ds_op_arena_swap(da.ptr, db.ptr, da.shape[0]))
+    return da.numpy().reshape(np.shape(a)), db.numpy().reshape(np.shape(b))

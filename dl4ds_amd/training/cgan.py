@@ -9,7 +9,7 @@ from ..dataloader import create_batch_hr_lr, DeviceDataGenerator
 from .. import models as M
 from .. import parallel
 from .base import Trainer
-from .engine import CGANEngine
+from .engine import CGANEngine, check_optimizer_args, cgan_optimizer_pair
 
 
 class CGANTrainer(Trainer):
@@ -18,7 +18,8 @@ class CGANTrainer(Trainer):
                  epochs=60, batch_size=16, learning_rates=(2e-4, 2e-4), device='GPU', gpu_memory_growth=True,
                  model_list=None, steps_per_epoch=None, interpolation='inter_area', static_vars=None,
                  checkpoints_frequency=0, save=False, save_path=None, save_logs=False, save_loss_history=True,
-                 generator_params={}, discriminator_params={}, verbose=True, loss_weights=None):
+                 generator_params={}, discriminator_params={}, verbose=True, loss_weights=None, global_clipnorm=None,
+                 weight_decay=None, ema_momentum=None):
         super().__init__(backbone=backbone, upsampling=upsampling, data_train=data_train, data_train_lr=data_train_lr,
                          time_window=time_window, loss=loss, batch_size=batch_size, patch_size=patch_size, scale=scale,
                          device=device, gpu_memory_growth=gpu_memory_growth, verbose=verbose, model_list=model_list,
@@ -42,6 +43,13 @@ class CGANTrainer(Trainer):
         self.gentotal, self.gengan, self.genpxloss, self.disc = [], [], [], []
         # loss_weights: a full-field (H, W[, C]) map of per-grid-cell weights of the PIXEL loss on the HR grid of `data_train`
         # (losses.check_loss_weights); the adversarial terms are untouched.  With `patch_size` it is cropped at every batch's corners
+        # Keras optimiser arguments of the same names: global_clipnorm and weight_decay take a number or a (generator, discriminator)
+        # pair, ema_momentum averages the GENERATOR's weights.  With the average on, the test loss and the generator-weight files use
+        # the averaged weights and the generator holds them when run() returns
+        for i in (0, 1):
+            check_optimizer_args(cgan_optimizer_pair('global_clipnorm', global_clipnorm)[i],
+                                 cgan_optimizer_pair('weight_decay', weight_decay)[i], ema_momentum)
+        self.global_clipnorm, self.weight_decay, self.ema_momentum = global_clipnorm, weight_decay, ema_momentum
         self.loss_weights = None
         if loss_weights is not None:
             from ..losses import check_loss_weights
@@ -84,7 +92,12 @@ class CGANTrainer(Trainer):
         self.setup_model()
         # genlr, dislr = learning_rates; a float / 1-tuple sets both (cgan.py:271-278)
         self.engine = CGANEngine(self.generator, self.discriminator, loss=self.lossf,
-                                 learning_rate=self.learning_rates, beta_1=0.5)
+                                 learning_rate=self.learning_rates, beta_1=0.5,
+                                 global_clipnorm=getattr(self, 'global_clipnorm', None),
+                                 weight_decay=getattr(self, 'weight_decay', None),
+                                 ema_momentum=getattr(self, 'ema_momentum', None))
+        ema = getattr(self, 'ema_momentum', None) is not None
+        ext = ema or getattr(self, 'global_clipnorm', None) is not None or getattr(self, 'weight_decay', None) is not None
         n_samples = self.data_train.shape[0] - (self.time_window or 0)
         if self.steps_per_epoch is None:
             self.steps_per_epoch = n_samples // self.batch_size
@@ -142,10 +155,17 @@ class CGANTrainer(Trainer):
             if self.checkpoints_frequency > 0 and self.running_on_first_worker and (epoch + 1) % self.checkpoints_frequency == 0:
                 self._save_checkpoint(epoch + 1)
             if self.verbose and self.running_on_first_worker and steps:
-                print(f'Epoch {epoch + 1}/{self.epochs} - gen_total {self.gentotal[-1]:.4f} gen_gan {self.gengan[-1]:.4f} '
-                      f'gen_px {self.genpxloss[-1]:.4f} disc {self.disc[-1]:.4f}')
+                line = (f'Epoch {epoch + 1}/{self.epochs} - gen_total {self.gentotal[-1]:.4f} gen_gan {self.gengan[-1]:.4f} '
+                        f'gen_px {self.genpxloss[-1]:.4f} disc {self.disc[-1]:.4f}')
+                if ext:
+                    sg, sd = self.engine.optimizer_stats('generator'), self.engine.optimizer_stats('discriminator')
+                    line += (f' - grad_norm {sg["grad_norm"]:.4g} / {sd["grad_norm"]:.4g} - skipped_steps '
+                             f'{sg["skipped_steps"]} / {sd["skipped_steps"]}')
+                print(line)
         if self.checkpoints_frequency > 0 and self.running_on_first_worker:          # cgan.py:379-382: the last state
             self._save_checkpoint(self.epochs)
+        if ema:
+            self.engine.swap_ema()               # from here on the generator holds the averages (test loss, saved model, Predictor)
         self._test_loss()
         self.running_time = time.time() - t0
         if self.save_loss_history and self.save and self.running_on_first_worker:
@@ -212,7 +232,11 @@ class CGANTrainer(Trainer):
         import os
         d = os.path.join(getattr(self, 'savecheckpoint_path', None) or self.save_path or './', 'checkpoints')
         os.makedirs(d, exist_ok=True)
-        self.engine.save_checkpoint(os.path.join(d, f'checkpoint_epoch-{epoch}.npz'))
+        self.engine.save_checkpoint(os.path.join(d, f'checkpoint_epoch-{epoch}.npz'))      # training weights (+ the averages)
+        if getattr(self, 'ema_momentum', None) is not None:
+            with self.engine.ema_weights():
+                np.savez(os.path.join(d, f'save_epoch{epoch}_generator_weights.npz'), **self.generator.get_weights())
+            return
         np.savez(os.path.join(d, f'save_epoch{epoch}_generator_weights.npz'), **self.generator.get_weights())
 
     fit = run

@@ -2,6 +2,7 @@
 compile/fit/evaluate become an explicit epoch/step loop around libdl4ds_hip's fused train step; Horovod's
 DistributedOptimizer / BroadcastGlobalVariablesCallback become one RCCL all-reduce per step and one
 broadcast before the first step."""
+import contextlib
 import os
 import time
 
@@ -12,7 +13,7 @@ from ..dataloader import DataGenerator, DeviceDataGenerator
 from .. import models as M
 from .. import parallel
 from .base import Trainer
-from .engine import SupervisedEngine
+from .engine import SupervisedEngine, check_optimizer_args
 
 
 class SupervisedTrainer(Trainer):
@@ -24,7 +25,7 @@ class SupervisedTrainer(Trainer):
                  learning_rate=(1e-3, 1e-4), lr_decay_after=1e5, early_stopping=False, patience=6, min_delta=0,
                  show_plot=True, save=False, save_path=None, save_bestmodel=False, trained_model=None,
                  trained_epochs=0, verbose=True, checkpoint=None, device_data=True, loss_weights=None,
-                 **architecture_params):
+                 global_clipnorm=None, weight_decay=None, ema_momentum=None, **architecture_params):
         super().__init__(backbone=backbone, upsampling=upsampling, data_train=data_train, data_train_lr=data_train_lr,
                          time_window=time_window, loss=loss, batch_size=batch_size, patch_size=patch_size, scale=scale,
                          device=device, gpu_memory_growth=gpu_memory_growth, use_multiprocessing=use_multiprocessing,
@@ -47,6 +48,11 @@ class SupervisedTrainer(Trainer):
         # loss_weights: a full-field (H, W[, C]) map of per-grid-cell loss weights on the HR grid of `data_train` (a 0/1 mask, cos
         # latitude, ...; losses.check_loss_weights); the training, validation and test losses all use it.  With `patch_size` the map is
         # cropped on the device at every batch's corners, which only the device-resident generator keeps
+        # Keras optimiser arguments of the same names (check_optimizer_args): clipping by the global gradient norm, decoupled weight
+        # decay on the kernels, and an exponential moving average of the weights.  With the average on, the validation and test
+        # losses and the best-model files use the AVERAGED weights (Keras' fit validates with the training weights and only swaps
+        # the averages in when training ends), and the model holds the averages when run() returns
+        self.global_clipnorm, self.weight_decay, self.ema_momentum = check_optimizer_args(global_clipnorm, weight_decay, ema_momentum)
         self.loss_weights = None
         if loss_weights is not None:
             from ..losses import check_loss_weights
@@ -136,7 +142,13 @@ class SupervisedTrainer(Trainer):
             lr = tuple(float(v) * self.world for v in lr)
         else:
             lr = float(lr) * self.world
-        self.engine = SupervisedEngine(self.model, loss=self.lossf, learning_rate=lr, lr_decay_after=self.lr_decay_after)
+        self.engine = SupervisedEngine(self.model, loss=self.lossf, learning_rate=lr, lr_decay_after=self.lr_decay_after,
+                                       global_clipnorm=getattr(self, 'global_clipnorm', None),
+                                       weight_decay=getattr(self, 'weight_decay', None),
+                                       ema_momentum=getattr(self, 'ema_momentum', None))
+        ema = getattr(self, 'ema_momentum', None) is not None
+        ext = ema or getattr(self, 'global_clipnorm', None) is not None or getattr(self, 'weight_decay', None) is not None
+        averaged = self.engine.ema_weights if ema else contextlib.nullcontext
         # resume: `checkpoint` (a file written by SupervisedEngine.save_checkpoint / a previous run with save=True)
         # restores weights, Adam slots and the iteration count, so that trained_epochs + remaining epochs continues the
         # same optimisation (the reference only re-loads the weights of `trained_model`, supervised.py:322-325)
@@ -159,19 +171,25 @@ class SupervisedTrainer(Trainer):
         best, wait = np.inf, 0
         for epoch in range(self.trained_epochs, self.epochs):
             tl, n = self._epoch_loss(self.ds_train, steps, True)
-            vl, _ = self._epoch_loss(self.ds_val, self.validation_steps, False)
+            with averaged():
+                vl, _ = self._epoch_loss(self.ds_val, self.validation_steps, False)
             hist['loss'].append(tl)
             hist['val_loss'].append(vl)
             if self.verbose and self.running_on_first_worker:
-                print(f'Epoch {epoch + 1}/{self.epochs} - {n} steps - loss: {tl:.6f} - val_loss: {vl:.6f}')
+                line = f'Epoch {epoch + 1}/{self.epochs} - {n} steps - loss: {tl:.6f} - val_loss: {vl:.6f}'
+                if ext:
+                    st = self.engine.optimizer_stats()
+                    line += f' - grad_norm: {st["grad_norm"]:.4g} - skipped_steps: {st["skipped_steps"]}'
+                print(line)
             # ModelCheckpoint(savecheckpoint_path/best_model, monitor='val_loss', save_best_only=False), first worker only
             # (supervised.py:379-390): with save_best_only=False Keras rewrites the file at the end of EVERY epoch; the
             # native format is the named-weights .npz + optimiser state of SupervisedEngine.save_checkpoint
             if self.save_bestmodel and self.running_on_first_worker:
                 d = os.path.join(self.savecheckpoint_path, 'best_model')
                 os.makedirs(d, exist_ok=True)
-                self.engine.save_checkpoint(os.path.join(d, 'checkpoint.npz'))
-                np.savez(os.path.join(d, 'model_weights.npz'), **self.model.get_weights())
+                self.engine.save_checkpoint(os.path.join(d, 'checkpoint.npz'))      # training weights (+ the averages)
+                with averaged():
+                    np.savez(os.path.join(d, 'model_weights.npz'), **self.model.get_weights())
                 np.savetxt(os.path.join(d, 'epoch_val_loss.txt'), [epoch + 1, vl])
             if self.early_stopping:                            # EarlyStopping(monitor='val_loss', mode='min'); vl is rank-averaged
                 if vl < best - self.min_delta:
@@ -185,13 +203,19 @@ class SupervisedTrainer(Trainer):
         self.fithist = hist
         # model.evaluate(ds_test) -- the reference scores on the first worker only (supervised.py:409-411); here every rank
         # scores its shard of the test set and the mean over ranks is reported (all ranks must enter the collective)
-        self.test_loss, _ = self._epoch_loss(self.ds_test, self.test_steps, False)
+        with averaged():
+            self.test_loss, _ = self._epoch_loss(self.ds_test, self.test_steps, False)
         if self.verbose and self.running_on_first_worker:
             print(f'\nScore on the test set: {self.test_loss}')
         self.running_time = time.time() - t0
+        if ema:
+            # Keras finalises the variable values the same way: the model (saved below, handed to Predictor) holds the averages.
+            # The engine then holds the training weights where its averages were, and the checkpoint says which is which
+            self.engine.swap_ema()
         self.save_results(self.model)
         if self.save and self.running_on_first_worker and self.save_path is not None:
-            self.engine.save_checkpoint(os.path.join(self.save_path, 'checkpoint.npz'))
+            with averaged():                                   # (back to the training weights for the file)
+                self.engine.save_checkpoint(os.path.join(self.save_path, 'checkpoint.npz'))
         return self
 
     fit = run     # BASELINE.json calls it fit(); the reference method is run()

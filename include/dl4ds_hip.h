@@ -422,6 +422,19 @@ int dl4ds_op_bce(const float* p_dev, float label, int n, float* loss_dev, float*
 /* tf.keras.optimizers.Adam step t (1-based) -- supervised.py:353; cgan.py:277-278 */
 int dl4ds_op_adam(float* w_dev, const float* g_dev, float* m_dev, float* v_dev, size_t n, int t, float lr,
                   float beta1, float beta2, float eps, float grad_scale);
+/* dl4ds_op_adam with clipping by the global gradient norm (Keras global_clipnorm = tf.clip_by_global_norm; 0: off), decoupled weight
+ * decay (Keras weight_decay / AdamW: w <- w - lr * weight_decay * w with the plain lr, before the gradient update) on the n_ranges
+ * [begin, end) element ranges decay_ranges_host[2 * n_ranges] (any order, any element boundaries; merged where they touch) and an
+ * exponential moving average ema <- ema_momentum * ema + (1 - ema_momentum) * w_new (ema_dev NULL: none).  At most two launches.
+ * norm = fl32(grad_scale * sqrt(sum g^2)) with the sum in fp64 in a fixed order (bit-reproducible); the gradient is scaled by
+ * c = clip / max(norm, clip), exactly 1 when norm <= clip.  A NON-FINITE norm skips the step: w, m, v, ema stay untouched.
+ * stats_out_dev[3] (device, kept by the caller across calls): [0] norm (0 without clipping) [1] c [2] the count of skipped steps,
+ * a 32-bit UNSIGNED INTEGER in that word, incremented in place.  With everything off the results equal dl4ds_op_adam's bit for bit. */
+int dl4ds_op_adam_ext(float* w_dev, const float* g_dev, float* m_dev, float* v_dev, float* ema_dev, size_t n, int t, float lr,
+                      float beta1, float beta2, float eps, float grad_scale, float global_clipnorm, float weight_decay,
+                      const size_t* decay_ranges_host, int n_ranges, float ema_momentum, float* stats_out_dev);
+/* exchanges two device arrays element by element in one kernel (what dl4ds_trainer_ema_swap runs) */
+int dl4ds_op_arena_swap(float* a_dev, float* b_dev, size_t n);
 
 /* ---------------------------------------------------------------- model graph
  * replaces the tf.keras functional graphs assembled by dl4ds/models/{sp_postups,sp_preups,spt_postups,
@@ -567,6 +580,21 @@ int dl4ds_trainer_get_state(dl4ds_trainer* tr, float* m_host, float* v_host, lon
  * (the reference resumes through tf.train.Checkpoint, cgan.py:288-292; supervised.py:322-325 re-uses a trained model) */
 int dl4ds_trainer_set_state(dl4ds_trainer* tr, const float* m_host, const float* v_host, long step);
 int dl4ds_trainer_last_loss(dl4ds_trainer* tr, float* loss_host);   /* synchronises */
+/* Optimiser extensions (semantics: dl4ds_op_adam_ext), between steps, any number of times.  global_clipnorm 0: no clipping.
+ * weight_decay applies to the parameters decay_param_ids[n_ids] (dl4ds_graph_param ids).  ema_momentum in [0, 1) switches the weight
+ * average on -- the first time it allocates a shadow arena initialised as a copy of the current weights (the Keras optimiser's
+ * `average` slots), later calls keep it -- and a negative value switches it off and frees the arena.  With all three off the step is
+ * the plain Adam launch.  The step counter counts attempted steps: a step skipped for a non-finite gradient norm still advances the
+ * learning-rate schedule and the bias correction.  Data parallel: the norm is taken on the all-reduced arena, 1/world folded in. */
+int dl4ds_trainer_set_optimizer_ext(dl4ds_trainer* tr, float global_clipnorm, float weight_decay, const int* decay_param_ids,
+                                    int n_ids, float ema_momentum);
+/* the last step's gradient norm (0 without clipping) and clip factor, and the count of skipped steps; synchronises */
+int dl4ds_trainer_optimizer_stats(dl4ds_trainer* tr, float* norm, float* factor, long* skipped);
+/* exchanges the weights and their averages in one kernel (exact; twice = identity); the average must be on */
+int dl4ds_trainer_ema_swap(dl4ds_trainer* tr);
+/* the averages as one arena-sized host array (layout: dl4ds_graph_param_info) -- checkpoints; synchronise */
+int dl4ds_trainer_ema_get(dl4ds_trainer* tr, float* ema_host);
+int dl4ds_trainer_ema_set(dl4ds_trainer* tr, const float* ema_host);
 
 /* CGAN step -- cgan.py:575-639 with generator_loss (:525-553, lambda) and discriminator_loss (:556-572).
  * gen: generator graph (inputs: lr[, static]); disc: discriminator graph (inputs: lr, hr/generated).
@@ -585,6 +613,14 @@ int dl4ds_cgan_step(dl4ds_trainer* tr, const float* const* gen_inputs, int n_gen
  * (cgan.py:288-292) and what load_checkpoint restores (cgan.py:447-522) */
 int dl4ds_cgan_get_state(dl4ds_trainer* tr, int which, float* m_host, float* v_host, long* step);
 int dl4ds_cgan_set_state(dl4ds_trainer* tr, int which, const float* m_host, const float* v_host, long step);
+/* the optimiser extensions of the generator (which = 0) / discriminator (which = 1) optimiser; the weight average exists for the
+ * generator only (ema_momentum must be negative for which = 1) and dl4ds_cgan_ema_* act on it */
+int dl4ds_cgan_set_optimizer_ext(dl4ds_trainer* tr, int which, float global_clipnorm, float weight_decay, const int* decay_param_ids,
+                                 int n_ids, float ema_momentum);
+int dl4ds_cgan_optimizer_stats(dl4ds_trainer* tr, int which, float* norm, float* factor, long* skipped);
+int dl4ds_cgan_ema_swap(dl4ds_trainer* tr);
+int dl4ds_cgan_ema_get(dl4ds_trainer* tr, float* ema_host);
+int dl4ds_cgan_ema_set(dl4ds_trainer* tr, const float* ema_host);
 int dl4ds_cgan_get_disc_grad(dl4ds_trainer* tr, int param_id, float* dst_host);
 
 /* ---------------------------------------------------------------- batch preparation (SURVEY section 8 "next" row f1)
