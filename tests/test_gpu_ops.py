@@ -801,8 +801,6 @@ def test_channel_attention(ops, shape):
     class P(dict):
         def get(self, ops_, name, shape, init='glorot'):
             return self[name]
-    for backend, conv in ((N, np.asarray), (T, lambda a: torch.tensor(a, dtype=torch.float64, requires_grad=True))):
-        pass
     pn = P({'a/conv1/kernel': w1.astype(np.float64), 'a/conv1/bias': b1.astype(np.float64),
             'a/conv2/kernel': w2.astype(np.float64), 'a/conv2/bias': b2.astype(np.float64)})
     ref = M.channel_attention(N, pn, 'a', x.astype(np.float64), c)
