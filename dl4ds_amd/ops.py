@@ -188,8 +188,27 @@ def maxpool2_bwd(x, y, dy):
     return dx.numpy()
 
 
-def dwconv(x, k, bias=None, dy=None, accumulate_into=None):
-    """DepthwiseConv2D(7, 'same')(x); with ``dy`` also (dx, dk, db).  k: (7,7,C,1) or (7,7,C)."""
+CANARY = -777.25          # fills a gradient buffer that the kernels must leave alone (``want_dw='canary'``)
+
+
+def _grad_buffers(accumulate_into, shapes):
+    """-> (DeviceArrays, accumulate): zeros, or the preloads of ``accumulate_into`` (None entries stay zero)."""
+    if accumulate_into is None:
+        return [DeviceArray.zeros(s) for s in shapes], 0
+    assert len(accumulate_into) == len(shapes)
+    return [DeviceArray.zeros(s) if a is None else _d(np.asarray(a, np.float32).reshape(s))
+            for a, s in zip(accumulate_into, shapes)], 1
+
+
+def _np(d):
+    return None if d is None else d.numpy()
+
+
+def dwconv(x, k, bias=None, dy=None, accumulate_into=None, want_dx=True, want_dk=True, want_db=True):
+    """DepthwiseConv2D(7, 'same')(x); with ``dy`` also (dx, dk, db).  k: (7,7,C,1) or (7,7,C).
+    ``accumulate_into``: an array preloads dx alone (dk, db add to zeros); a tuple (dx0, dk0, db0) preloads all three.
+    ``want_dx`` / ``want_db`` False pass a null pointer and return None in that place; ``want_dk`` False passes a null dk (no
+    weight-gradient pass at all), ``want_dk='canary'`` a null dk with a db filled with CANARY, which must come back as it went."""
     n, h, w, c = x.shape
     ks = k.shape[0]
     dx_, dk_ = _d(x), _d(np.ascontiguousarray(k, np.float32).reshape(ks, ks, c))
@@ -199,15 +218,31 @@ def dwconv(x, k, bias=None, dy=None, accumulate_into=None):
     if dy is None:
         return y.numpy()
     ddy = _d(dy)
-    gx = DeviceArray.zeros(x.shape) if accumulate_into is None else _d(accumulate_into)
-    gk, gb = DeviceArray.zeros((ks, ks, c)), DeviceArray.zeros((c,))
-    _lib.check(_lib.lib().dl4ds_op_dwconv_bwd(dx_.ptr, dk_.ptr, ddy.ptr, gx.ptr, gk.ptr, gb.ptr, n, h, w, c, ks,
-                                              int(accumulate_into is not None)))
-    return y.numpy(), gx.numpy(), gk.numpy().reshape(k.shape), gb.numpy()
+    if accumulate_into is not None and not isinstance(accumulate_into, (tuple, list)):
+        accumulate_into = (accumulate_into, None, None)
+    (gx, gk, gb), acc = _grad_buffers(accumulate_into, [x.shape, (ks, ks, c), (c,)])
+    if want_dk == 'canary':
+        gb = _d(np.full((c,), CANARY, np.float32))
+    gx = gx if want_dx else None
+    gk = gk if want_dk is True else None
+    gb = gb if want_db else None
+    _lib.check(_lib.lib().dl4ds_op_dwconv_bwd(dx_.ptr, dk_.ptr, ddy.ptr, _p(gx), _p(gk), _p(gb), n, h, w, c, ks, acc))
+    gk_host = None if gk is None else gk.numpy().reshape(k.shape)
+    return y.numpy(), _np(gx), gk_host, _np(gb)
 
 
-def layernorm(x, gamma, beta, eps=1e-3, relu=False, dy=None):
-    """LayerNormalization(axis=-1)(x) [+ ReLU]; with ``dy`` also (dx, dgamma, dbeta)."""
+def _norm_grads(x, c, accumulate_into, want_dx, want_dw):
+    (dx, dgam, dbet), acc = _grad_buffers(accumulate_into, [x.shape, (c,), (c,)])
+    if want_dw == 'canary':
+        dbet = _d(np.full((c,), CANARY, np.float32))
+    return (dx if want_dx else None), (dgam if want_dw is True else None), (dbet if want_dw else None), acc
+
+
+def layernorm(x, gamma, beta, eps=1e-3, relu=False, dy=None, accumulate_into=None, want_dx=True, want_dw=True):
+    """LayerNormalization(axis=-1)(x) [+ ReLU]; with ``dy`` also (dx, dgamma, dbeta).
+    ``accumulate_into=(dx0, dgamma0, dbeta0)``: the gradients are added to these (accumulate = 1).  ``want_dx=False`` passes a null
+    dx, ``want_dw=False`` null dgamma and dbeta (None is returned in their places); ``want_dw='canary'`` a null dgamma with a dbeta
+    filled with CANARY, which must come back as it went."""
     c = x.shape[-1]
     npix = x.size // c
     dx_, dg_, db_ = _d(x), _d(gamma), _d(beta)
@@ -216,27 +251,31 @@ def layernorm(x, gamma, beta, eps=1e-3, relu=False, dy=None):
     if dy is None:
         return y.numpy()
     ddy = _d(dy)
-    dx, dgam, dbet = DeviceArray.zeros(x.shape), DeviceArray.zeros((c,)), DeviceArray.zeros((c,))
-    _lib.check(_lib.lib().dl4ds_op_layernorm_bwd(dx_.ptr, y.ptr, ddy.ptr, dg_.ptr, dx.ptr, dgam.ptr, dbet.ptr, npix, c,
-                                                 float(eps), int(relu), 0))
-    return y.numpy(), dx.numpy(), dgam.numpy(), dbet.numpy()
+    dx, dgam, dbet, acc = _norm_grads(x, c, accumulate_into, want_dx, want_dw)
+    _lib.check(_lib.lib().dl4ds_op_layernorm_bwd(dx_.ptr, y.ptr, ddy.ptr, dg_.ptr, _p(dx), _p(dgam), _p(dbet), npix, c,
+                                                 float(eps), int(relu), acc))
+    return y.numpy(), _np(dx), _np(dgam), _np(dbet)
 
 
-def batchnorm(x, gamma, beta, moving_mean, moving_var, eps=1e-3, momentum=0.99, training=True, relu=False, dy=None):
-    """BatchNormalization(axis=-1)(x, training) [+ ReLU] -> (y, new moving_mean, new moving_var[, dx, dgamma, dbeta])."""
+def batchnorm(x, gamma, beta, moving_mean, moving_var, eps=1e-3, momentum=0.99, training=True, relu=False, dy=None,
+              accumulate_into=None, want_dx=True, want_dw=True, return_saved=False):
+    """BatchNormalization(axis=-1)(x, training) [+ ReLU] -> (y, new moving_mean, new moving_var[, dx, dgamma, dbeta][, saved]).
+    ``accumulate_into``, ``want_dx``, ``want_dw``: as for ``layernorm``.  ``return_saved``: append the (2, C) array of the batch
+    mean and 1 / sqrt(var + eps) that the training-mode forward hands to the backward."""
     c = x.shape[-1]
     npix = x.size // c
     dx_, dg_, db_, dmm, dmv = _d(x), _d(gamma), _d(beta), _d(moving_mean), _d(moving_var)
     y, saved = DeviceArray.zeros(x.shape), DeviceArray.zeros((2 * c,))
     _lib.check(_lib.lib().dl4ds_op_batchnorm_fwd(dx_.ptr, dg_.ptr, db_.ptr, dmm.ptr, dmv.ptr, y.ptr, saved.ptr, npix, c,
                                                  float(eps), float(momentum), int(training), int(relu)))
+    tail = (saved.numpy().reshape(2, c),) if return_saved else ()
     if dy is None:
-        return y.numpy(), dmm.numpy(), dmv.numpy()
+        return (y.numpy(), dmm.numpy(), dmv.numpy()) + tail
     ddy = _d(dy)
-    dx, dgam, dbet = DeviceArray.zeros(x.shape), DeviceArray.zeros((c,)), DeviceArray.zeros((c,))
-    _lib.check(_lib.lib().dl4ds_op_batchnorm_bwd(dx_.ptr, y.ptr, ddy.ptr, dg_.ptr, saved.ptr, dx.ptr, dgam.ptr, dbet.ptr,
-                                                 npix, c, int(relu), 0))
-    return y.numpy(), dmm.numpy(), dmv.numpy(), dx.numpy(), dgam.numpy(), dbet.numpy()
+    dx, dgam, dbet, acc = _norm_grads(x, c, accumulate_into, want_dx, want_dw)
+    _lib.check(_lib.lib().dl4ds_op_batchnorm_bwd(dx_.ptr, y.ptr, ddy.ptr, dg_.ptr, saved.ptr, _p(dx), _p(dgam), _p(dbet),
+                                                 npix, c, int(relu), acc))
+    return (y.numpy(), dmm.numpy(), dmv.numpy(), _np(dx), _np(dgam), _np(dbet)) + tail
 
 
 def resize_bilinear(x, ho, wo):
