@@ -547,6 +547,13 @@ int dl4ds_op_loss(int kind, const float* yt, const float* yp, float* dpred, int 
     loss_forward_backward(S(), kind, yt, yp, dpred, N, H, W, C, 1.f, loss_dev, 0, scratch(ws), ws);
     API_END
 }
+int dl4ds_op_loss_scaled(int kind, const float* yt, const float* yp, float* dpred, int N, int H, int W, int C, float scale,
+                         int accumulate, float* loss_dev) {
+    API_BEGIN
+    const size_t ws = loss_workspace_bytes(kind, N, H, W, C);
+    loss_forward_backward(S(), kind, yt, yp, dpred, N, H, W, C, scale, loss_dev, accumulate, scratch(ws), ws);
+    API_END
+}
 int dl4ds_op_loss_weighted(int kind, const float* yt, const float* yp, float* dpred, int N, int H, int W, int C, const float* w,
                            int w_batch, int w_channels, float* loss_dev) {
     API_BEGIN

@@ -856,9 +856,12 @@ __global__ void __launch_bounds__(256) met_pair_partial_kernel(const float* __re
     const size_t e0 = (size_t)blockIdx.x * chunk, e1 = min(e0 + chunk, per);
     const float* a = t + (size_t)n * per;
     const float* b = p + (size_t)n * per;
+    // the moments are those of (x - x0, y - y0), the pair's first elements (exact in double): Pearson does not see the shift, and the
+    // float partials of data with a large mean (Kelvin, Pascal) would otherwise lose the covariance in cov = E[xy] - E[x] E[y]
+    const double x0 = a[0], y0 = b[0];
     double s[MET_K] = {0, 0, 0, 0, 0, 0, 0};
     for (size_t e = e0 + threadIdx.x; e < e1; e += 256) {
-        const double x = a[e], y = b[e], d = y - x;
+        const double x = (double)a[e] - x0, y = (double)b[e] - y0, d = (double)b[e] - (double)a[e];
         s[0] += fabs(d); s[1] += d * d; s[2] += x; s[3] += y; s[4] += x * y; s[5] += x * x; s[6] += y * y;
     }
     for (int k = 0; k < MET_K; ++k) red[k][threadIdx.x] = s[k];
@@ -870,7 +873,8 @@ __global__ void __launch_bounds__(256) met_pair_partial_kernel(const float* __re
     }
     if (threadIdx.x < MET_K) partial[((size_t)n * gridDim.x + blockIdx.x) * MET_K + threadIdx.x] = (float)red[threadIdx.x][0];
 }
-// out[n] = (mae, mse, pearson over the grid)
+// out[n] = (mae, mse, pearson over the grid); a pair with a constant side has exact zero moments on that side (the shift above) and
+// reports a correlation of 0
 __global__ void met_pair_finish_kernel(const float* __restrict__ partial, int nchunks, int N, double per, float* __restrict__ out) {
     const int n = blockIdx.x * blockDim.x + threadIdx.x;
     if (n >= N) return;

@@ -58,7 +58,10 @@ def _device_spearman(dy, dp, shape, over):
 
 def image_metrics(y_test, y_test_hat):
     """Raw device reductions -> dict of arrays: per pair ``mae``, ``mse``, ``rmse``, ``psnr``, ``ssim``, ``pearson``; per grid
-    point ``rmse_map``, ``bias_map``, ``pearson_map``; ``drange``."""
+    point ``rmse_map``, ``bias_map``, ``pearson_map``; ``drange``.  ``pearson`` of a pair one side of which is constant is 0.0
+    (scipy.stats.pearsonr: NaN); ``pearson_map`` is NaN where either side of a grid point is constant over the pairs, hence
+    everywhere for a single pair; ``ssim`` is NaN on grids below the 11x11 window.  The per-pair moments are taken about the pair's
+    first elements, so data with a large mean (Kelvin, Pascal) keeps its correlation."""
     y, _, dy, dp = _upload(y_test, y_test_hat)
     return _device_metrics(dy, dp, y.shape)
 

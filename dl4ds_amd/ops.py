@@ -366,17 +366,28 @@ def weight_form(shape, batch_shape):
                      f'(H, W, C) or (M, H, W, 1 | C) with M a divisor of the batch size')
 
 
-def loss(kind, y_true, y_pred, want_grad=True, weights=None):
+def loss(kind, y_true, y_pred, want_grad=True, weights=None, scale=1.0, accumulate_into=None):
     """Loss value and dloss/dpred.  weights: per-grid-cell weights, float32, finite, >= 0, in one of the forms of `weight_form`
     (semantics: dl4ds_op_loss_weighted in include/dl4ds_hip.h -- entries with weight 0 are excluded by selection, the multi-scale
-    kinds are refused)."""
+    kinds are refused).  scale multiplies the loss and its gradient (the trainers' lambda); accumulate_into: an array of y_pred's
+    shape that the gradient is ADDED to (dl4ds_op_loss_scaled; unweighted kinds only)."""
     n, h, w, c = y_true.shape
     if weights is not None and kind.startswith('msdssim'):
         raise ValueError(f'loss weights are not available for the multi-scale kind {kind!r}')
+    scaled = scale != 1.0 or accumulate_into is not None
+    if scaled and (weights is not None or (accumulate_into is not None and not want_grad)):
+        raise ValueError('scale / accumulate_into go with the unweighted loss, accumulate_into with want_grad')
     dt, dp = _d(y_true), _d(y_pred)
     g = DeviceArray.zeros(y_pred.shape) if want_grad else None
     lv = DeviceArray.zeros((8,))
-    if weights is None:
+    if scaled:
+        if accumulate_into is not None:
+            if np.shape(accumulate_into) != tuple(y_pred.shape):
+                raise ValueError(f'accumulate_into of shape {np.shape(accumulate_into)} for a prediction of shape {tuple(y_pred.shape)}')
+            g = _d(np.ascontiguousarray(accumulate_into, np.float32))
+        _lib.check(_lib.lib().dl4ds_op_loss_scaled(LOSS_KINDS[kind], dt.ptr, dp.ptr, _p(g), n, h, w, c, float(scale),
+                                                   int(accumulate_into is not None), lv.ptr))
+    elif weights is None:
         _lib.check(_lib.lib().dl4ds_op_loss(LOSS_KINDS[kind], dt.ptr, dp.ptr, _p(g), n, h, w, c, lv.ptr))
     else:
         wb, wc = weight_form(np.shape(weights), y_true.shape)

@@ -156,7 +156,12 @@ int dl4ds_op_chatt_bwd(const float* x_dev, const float* dy_dev, float* dx_dev, i
  * loss_dev[0] = loss ; dpred_dev = dloss/dpred (may be NULL). */
 int dl4ds_op_loss(int kind, const float* y_true_dev, const float* y_pred_dev, float* dpred_dev, int N, int H,
                   int W, int C, float* loss_dev);
-/* The same with per-grid-cell weights (masks, cos(latitude) area weights).  w_dev: float32, finite, >= 0, w_batch maps of
+/* The same as the trainers call it: loss_dev[0] = scale * loss (the cGAN's lambda); dpred_dev = scale * dloss/dpred, ADDED to what
+ * dpred_dev holds when accumulate != 0 (the drange and min-shift terms of the SSIM kinds included).  scale = 1, accumulate = 0 is
+ * dl4ds_op_loss bit for bit. */
+int dl4ds_op_loss_scaled(int kind, const float* y_true_dev, const float* y_pred_dev, float* dpred_dev, int N, int H,
+                         int W, int C, float scale, int accumulate, float* loss_dev);
+/* dl4ds_op_loss with per-grid-cell weights (masks, cos(latitude) area weights).  w_dev: float32, finite, >= 0, w_batch maps of
  * (H, W, w_channels); w_batch must DIVIDE N and sample row r of the (N, H, W, C) batch uses map r / (N / w_batch) -- 1: one map shared by
  * all samples, N: one map per sample (patch training), N / nmul: one map per sample of a spatio-temporal output of nmul frames;
  * w_channels is 1 (the map serves every channel) or C.  With d = p - t and sums over all N*H*W*C entries (w broadcast):

@@ -575,7 +575,7 @@ def piecewise_lr(step, boundary, lr0, lr1):
 def image_metrics(y, p):
     """dl4ds/metrics.py:166-262 restated (TEST INFRASTRUCTURE): joint range, per-pair PSNR (tf.image.psnr), SSIM
     (tf.image.ssim with max_val = range, no shift), MAE, RMSE, Pearson over the grid; per-grid-point RMSE, mean bias and
-    Pearson over the pairs."""
+    Pearson over the pairs.  A grid below the 11x11 window has no SSIM (tf.image.ssim refuses it): NaN, as the product reports."""
     y = np.asarray(y, np.float64)
     p = np.asarray(p, np.float64)
     n = y.shape[0]
@@ -583,7 +583,8 @@ def image_metrics(y, p):
     d = p - y
     mse = (d ** 2).reshape(n, -1).mean(1)
     out = dict(drange=drange, mse=mse, rmse=np.sqrt(mse), mae=np.abs(d).reshape(n, -1).mean(1),
-               psnr=20 * np.log10(drange) - 10 * np.log10(mse), ssim=ssim(y, p, drange))
+               psnr=20 * np.log10(drange) - 10 * np.log10(mse),
+               ssim=ssim(y, p, drange) if min(y.shape[1:3]) >= 11 else np.full(n, np.nan))
     yf, pf = y.reshape(n, -1), p.reshape(n, -1)
     yc, pc = yf - yf.mean(1, keepdims=True), pf - pf.mean(1, keepdims=True)
     out['pearson'] = (yc * pc).sum(1) / np.sqrt((yc ** 2).sum(1) * (pc ** 2).sum(1))
