@@ -42,6 +42,7 @@ def __getattr__(name):
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'QuantileMapper': '.postprocessing', 'quantile_map': '.postprocessing', 'check_qmap_args': '.postprocessing',
+            'predict_tiled': '.inference', 'TiledPredictor': '.inference', 'plan_tiles': '.tiling',
             'climate_indices': '.indices', 'precipitation_indices': '.indices', 'temperature_indices': '.indices',
             'percentile_threshold': '.indices', 'index_scores': '.indices', 'check_index_args': '.indices',
             'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',

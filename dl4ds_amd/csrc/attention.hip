@@ -292,13 +292,17 @@ size_t chatt_workspace_bytes(const AttShape& sh) {
 
 void chatt_forward(hipStream_t s, const float* x, float* y, const AttShape& sh, const float* w1, const float* b1,
                    const float* w2, const float* b2, float* mean, float* hidden, float* scale, float* workspace,
-                   const float* pool_partial, int pool_tiles) {
+                   const float* pool_partial, int pool_tiles, const float* given_mean) {
     const int Q = sh.P * sh.C;
     const int ninst = sh.G * sh.P;
     // algorithmic traffic: one read of x for the pooling unless the producer supplied it, one read + one write for the scale
     // unless the consumer applies it while loading (y == nullptr)
     ProfScope ps(s, "chatt_fwd", 0.0, 4.0 * (double)sh.G * sh.R * Q * ((pool_partial ? 0 : 1) + (y ? 2 : 0)));
-    if (pool_partial) {
+    if (given_mean) {
+        // tiled prediction: the mean over the whole FIELD, of which this tensor is one tile
+        DL4DS_REQUIRE(sh.P == 1, "chatt: a given mean needs the 4-D form");
+        HIP_CHECK(hipMemcpyAsync(mean, given_mean, (size_t)sh.G * sh.C * sizeof(float), hipMemcpyDeviceToDevice, s));
+    } else if (pool_partial) {
         DL4DS_REQUIRE(sh.P == 1 && sh.C <= 8, "chatt: pooling partials come from the 8-channel pair convolution");
         DL4DS_LAUNCH(pool_finish_kernel, dim3(cdiv(sh.G, 4)), dim3(256), 0, s, pool_partial, mean, pool_tiles,
                            sh.C, sh.G, 1.f / (float)sh.R);

@@ -429,6 +429,75 @@ int dl4ds_batch_gather(const dl4ds_gather_group* groups, int n_groups, const int
                  out_h, out_w, T, B);
     API_END
 }
+// k lists of n host ints -> one persistent device buffer [k][n], grown on demand; ordered on the library stream like
+// upload_index_lists
+static const int* upload_tile_lists(const int* const* src, int k, int n) {
+    static int* d_lists = nullptr;
+    static size_t cap = 0;
+    static std::vector<int> h_lists;
+    const size_t need = (size_t)k * n;
+    if (need > cap) {
+        if (d_lists) HIP_CHECK(hipFree(d_lists));
+        d_lists = nullptr;
+        cap = std::max<size_t>(need, 5 * 256);
+        HIP_CHECK(hipMalloc((void**)&d_lists, cap * sizeof(int)));
+    }
+    h_lists.resize(need);
+    for (int i = 0; i < k; ++i) std::copy(src[i], src[i] + n, h_lists.begin() + (size_t)i * n);
+    HIP_CHECK(hipMemcpyAsync(d_lists, h_lists.data(), need * sizeof(int), hipMemcpyHostToDevice, S()));
+    return d_lists;
+}
+int dl4ds_tile_pool(const float* tiles_dev, int n, int th, int tw, int C, const int* sample_host, const int* wy_row_host,
+                    const int* wx_row_host, const float* wy_dev, int wy_rows, const float* wx_dev, int wx_rows, double* sums_dev,
+                    int N) {
+    API_BEGIN
+    DL4DS_REQUIRE(tiles_dev && wy_dev && wx_dev && sums_dev, "tile_pool: null device pointer");
+    DL4DS_REQUIRE(sample_host && wy_row_host && wx_row_host, "tile_pool: null host list");
+    DL4DS_REQUIRE(n > 0 && th > 0 && tw > 0 && C > 0 && N > 0 && wy_rows > 0 && wx_rows > 0, "tile_pool: bad sizes");
+    DL4DS_REQUIRE(n <= 65535 && (long long)th * tw < (1ll << 31), "tile_pool: at most 65535 tiles per call, 2^31 pixels per tile");
+    for (int t = 0; t < n; ++t) {
+        DL4DS_REQUIRE(sample_host[t] >= 0 && sample_host[t] < N, "tile_pool: sample index outside the sums");
+        DL4DS_REQUIRE(wy_row_host[t] >= 0 && wy_row_host[t] < wy_rows && wx_row_host[t] >= 0 && wx_row_host[t] < wx_rows,
+                      "tile_pool: weight-table row outside the table");
+    }
+    DL4DS_REQUIRE(!g_err_host || *reinterpret_cast<volatile unsigned*>(g_err_host) == 0u,
+                  "tile_pool: device error word set (dl4ds_sync reports and clears it)");
+    const int* src[3] = {sample_host, wy_row_host, wx_row_host};
+    const int* d = upload_tile_lists(src, 3, n);
+    double* partial = reinterpret_cast<double*>(scratch((size_t)n * C * sizeof(double)));
+    tile_pool(S(), tiles_dev, wy_dev, wx_dev, d, d + n, d + 2 * n, n, th, tw, C, partial, sums_dev);
+    API_END
+}
+int dl4ds_tile_merge(const float* tiles_dev, int n, int th, int tw, int C, const int* oy_host, const int* ox_host,
+                     const int* sample_host, const int* wy_row_host, const int* wx_row_host, const float* wy_dev, int wy_rows,
+                     const float* wx_dev, int wx_rows, float* out_dev, int N, int H, int W) {
+    API_BEGIN
+    DL4DS_REQUIRE(tiles_dev && wy_dev && wx_dev && out_dev, "tile_merge: null device pointer");
+    DL4DS_REQUIRE(oy_host && ox_host && sample_host && wy_row_host && wx_row_host, "tile_merge: null host list");
+    DL4DS_REQUIRE(n > 0 && th > 0 && tw > 0 && C > 0 && N > 0 && H > 0 && W > 0 && wy_rows > 0 && wx_rows > 0, "tile_merge: bad sizes");
+    // the kernel keeps the tiles that share a row in an LDS list of 256 entries (tiles.hip)
+    DL4DS_REQUIRE(n <= 256 && th <= 65535, "tile_merge: at most 256 tiles per call (split the batch: the result does not depend on it) and 65535 rows per tile");
+    DL4DS_REQUIRE((long long)W * C < (1ll << 31) && (long long)tw * C < (1ll << 31), "tile_merge: a row of more than 2^31 floats");
+    DL4DS_REQUIRE(th <= H && tw <= W, "tile_merge: tile larger than the output");
+    bool vec = (tw * C) % 4 == 0 && ((long long)W * C) % 4 == 0 && (((uintptr_t)tiles_dev | (uintptr_t)out_dev) & 15) == 0;
+    for (int t = 0; t < n; ++t) {
+        DL4DS_REQUIRE(sample_host[t] >= 0 && sample_host[t] < N, "tile_merge: sample index outside the output");
+        DL4DS_REQUIRE(oy_host[t] >= 0 && ox_host[t] >= 0 && oy_host[t] <= H - th && ox_host[t] <= W - tw,
+                      "tile_merge: tile outside the output");
+        DL4DS_REQUIRE(wy_row_host[t] >= 0 && wy_row_host[t] < wy_rows && wx_row_host[t] >= 0 && wx_row_host[t] < wx_rows,
+                      "tile_merge: weight-table row outside the table");
+        vec = vec && ((long long)ox_host[t] * C) % 4 == 0;
+    }
+    // a kernel of an earlier call raised the device error word: what this merge would read is invalid.  The word stays set; the next
+    // host-side wait (dl4ds_sync) reports and clears it.
+    DL4DS_REQUIRE(!g_err_host || *reinterpret_cast<volatile unsigned*>(g_err_host) == 0u,
+                  "tile_merge: device error word set (dl4ds_sync reports and clears it)");
+    const int* src[5] = {oy_host, ox_host, sample_host, wy_row_host, wx_row_host};
+    const int* d_lists = upload_tile_lists(src, 5, n);
+    tile_merge(S(), tiles_dev, wy_dev, wx_dev, out_dev, d_lists, d_lists + n, d_lists + 2 * n, d_lists + 3 * n, d_lists + 4 * n, n, th,
+               tw, C, H, W, vec);
+    API_END
+}
 int dl4ds_op_depth_to_space(const float* x, float* y, int N, int H, int W, int C, int r) {
     API_BEGIN
     depth_to_space(S(), x, y, N, H, W, C, r);
@@ -766,6 +835,18 @@ int dl4ds_graph_conv2d(dl4ds_graph* g, int in, int w, int b, int add, int KS, in
 int dl4ds_graph_conv2d_transpose(dl4ds_graph* g, int in, int w, int KS, int stride, int Cout, int relu, int* out) {
     API_BEGIN
     *out = g_conv2d_transpose(g->g, in, w, KS, stride, Cout, relu);
+    API_END
+}
+int dl4ds_graph_chatt_info(dl4ds_graph* g, int index, int* tensor_in, int* channels, int* contiguous) {
+    API_BEGIN
+    DL4DS_REQUIRE(g && tensor_in && channels && contiguous, "graph_chatt_info: null argument");
+    g_chatt_info(g->g, index, tensor_in, channels, contiguous);
+    API_END
+}
+int dl4ds_graph_chatt_set_mean(dl4ds_graph* g, int index, const float* mean_dev) {
+    API_BEGIN
+    DL4DS_REQUIRE(g, "graph_chatt_set_mean: null graph");
+    g_chatt_set_mean(g->g, index, mean_dev);
     API_END
 }
 int dl4ds_graph_chatt(dl4ds_graph* g, int in, int w1, int b1, int w2, int b2, int Cr, int T5, int* out) {

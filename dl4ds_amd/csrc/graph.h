@@ -196,6 +196,8 @@ inline bool wants_grad(const Graph& g, int tid, const BwdCtx& c) {
 int g_conv2d(Graph& g, int in, int w, int b, int add, int KS, int Cout, int relu, int d2s);
 int g_conv2d_transpose(Graph& g, int in, int w, int KS, int stride, int Cout, int relu);
 int g_chatt(Graph& g, int in, int w1, int b1, int w2, int b2, int Cr, int mode5d_T);
+void g_chatt_info(Graph& g, int index, int* tensor_in, int* channels, int* contiguous);
+void g_chatt_set_mean(Graph& g, int index, const float* mean_dev);
 int g_concat(Graph& g, const int* ins, int n);
 int g_add(Graph& g, int a, int b, int relu);
 int g_act(Graph& g, int in, int kind);

@@ -607,6 +607,7 @@ struct ChAttOp : GOp {
     AttFusion fz;
     ConvOp* producer = nullptr;            // ConvOp writing `in` (found at finalize), ConvOp reading `out`
     ConvOp* consumer = nullptr;
+    const float* given_mean = nullptr;     // [B * nmul][C] device: forward uses it instead of pooling (g_chatt_set_mean; inference only)
     ChAttOp() { kind = "chatt"; }
     AttShape shape(Graph& g, int B) {
         const GTensor& t = g.tensors[in];
@@ -698,7 +699,7 @@ struct ChAttOp : GOp {
         ptrs(g, B, mean, hidden, scale, dmean, pool);
         chatt_forward(g.stream, g.tensors[in].data, fz.fuse_scale ? nullptr : g.tensors[out].data, shape(g, B), g.wp(w1),
                       g.wp(b1), g.wp(w2), g.wp(b2), mean, hidden, scale, g.workspace, fz.fuse_pool ? pool : nullptr,
-                      fz.pool_tiles);
+                      fz.pool_tiles, given_mean);
     }
     std::string describe_fusion(Graph&) override {
         return std::string("{\"op\":\"chatt\",\"in\":") + std::to_string(in) + ",\"pool_from_producer\":" +
@@ -1213,6 +1214,26 @@ int g_conv2d(Graph& g, int in, int w, int b, int add, int KS, int Cout, int relu
     op->out_tid = out; op->in_tids = {in, add};
     g.tensors[out].dep_grad_input = g.tensors[in].dep_grad_input || (add >= 0 && g.tensors[add].dep_grad_input);
     return out;
+}
+
+// the ChannelAttention2D ops of a graph in op order, for tiled prediction (Model.predict_tiled supplies the field's mean)
+static std::vector<ChAttOp*> chatt_ops(Graph& g) {
+    std::vector<ChAttOp*> v;
+    for (auto& op : g.ops)
+        if (ChAttOp* c = dynamic_cast<ChAttOp*>(op.get())) v.push_back(c);
+    return v;
+}
+void g_chatt_info(Graph& g, int index, int* tensor_in, int* channels, int* contiguous) {
+    auto v = chatt_ops(g);
+    DL4DS_REQUIRE(index >= 0 && index < (int)v.size(), "chatt op index out of range");
+    const GTensor& t = g.tensors[v[index]->in];
+    *tensor_in = v[index]->in; *channels = t.C; *contiguous = (t.alias_of < 0 && v[index]->T5 == 0) ? 1 : 0;
+}
+void g_chatt_set_mean(Graph& g, int index, const float* mean_dev) {
+    auto v = chatt_ops(g);
+    DL4DS_REQUIRE(index >= 0 && index < (int)v.size(), "chatt op index out of range");
+    DL4DS_REQUIRE(!mean_dev || v[index]->T5 == 0, "chatt: a given mean needs the 4-D form");
+    v[index]->given_mean = mean_dev;
 }
 
 int g_chatt(Graph& g, int in, int w1, int b1, int w2, int b2, int Cr, int mode5d_T) {

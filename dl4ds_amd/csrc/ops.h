@@ -231,6 +231,14 @@ size_t spectrum_workspace_bytes(int N, int H, int W, int C, int sides, int B);
 void spectrum_check_args(int N, int H, int W, int C, const int* bin_host, int B);
 void spectrum(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
               int B, double* power, long long* valid, double* mean, void* workspace, size_t workspace_bytes);
+// Merge of a batch of tile outputs into the output field (tiles.hip): out[smp[t]][oy[t] + y][ox[t] + x][c] +=
+// wy[ry[t]][y] * wx[rx[t]][x] * tiles[t][y][x][c], taps in ascending t, zero weights skipped.  The five lists are DEVICE ints; nothing
+// is checked here (capi.cpp does); `vec`: 16-byte accesses are legal for this batch.
+void tile_merge(hipStream_t s, const float* tiles, const float* wy, const float* wx, float* out, const int* oy, const int* ox,
+                const int* smp, const int* ry, const int* rx, int n, int th, int tw, int C, int H, int W, bool vec);
+// sums[smp[t]][c] += sum_yx wy * wx * tiles[t][y][x][c] in fp64, fixed order (tiles.hip); partial: [n][C] doubles of scratch
+void tile_pool(hipStream_t s, const float* tiles, const float* wy, const float* wx, const int* smp, const int* ry, const int* rx,
+               int n, int th, int tw, int C, double* partial, double* sums);
 // LayerNormalization / BatchNormalization over the channel axis of [npix][C] (norm.hip), optional fused ReLU
 size_t norm_workspace_bytes(int C);
 void layernorm_forward(hipStream_t s, const float* x, const float* gamma, const float* beta, float* y, size_t npix, int C,
@@ -269,7 +277,8 @@ struct AttShape { int G, R, P, C, Cr; };
 // -> no pooling pass over x.  y == nullptr: the scale is not applied here (the consumer reads x through TView::sc = scale).
 void chatt_forward(hipStream_t s, const float* x, float* y, const AttShape& sh, const float* w1,
                    const float* b1, const float* w2, const float* b2, float* mean, float* hidden,
-                   float* scale, float* workspace, const float* pool_partial = nullptr, int pool_tiles = 0);
+                   float* scale, float* workspace, const float* pool_partial = nullptr, int pool_tiles = 0,
+                   const float* given_mean = nullptr);      // given_mean [G][C] (P == 1): used instead of the pooled mean (tiles.hip)
 // dx == nullptr: dX = dY * scale + dmean is not materialised; dmean is left in dmean_out ([G*P*C], caller-owned) for the
 // producer's lazy dY view (TView::sc = scale, TView::sh = dmean)
 void chatt_backward(hipStream_t s, const float* x, const float* dy, float* dx, int accumulate_dx,

@@ -3,23 +3,30 @@ the result in a Keras-like ``Model`` (the surface the reference uses: ``model(in
 ``.predict``, ``.name``, ``.count_params``, ``.get_weights/.set_weights``, ``.summary`` --
 dl4ds/training/supervised.py:320,396-409; cgan.py:597-600; inference.py:172-173,238)."""
 import ctypes
+import math
 from collections import OrderedDict
+from fractions import Fraction
 
 import numpy as np
 
 from . import _lib
 from ._chunks import check_batch_size, is_int
-from .device import Buffers
+from .device import Buffers, DeviceArray
 from .ensemble_score import ExceedanceScorer, Scorer, check_exceedance_args, check_score_args
 
 ACT_KINDS = {'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'leaky_relu': 5, 'selu': 6, 'gelu': 7}
 
 
 class Tensor:
-    __slots__ = ('id', 'H', 'W', 'C', 'nmul')
+    """``px``, ``reach``, ``local_reach`` and ``align`` are the tile-planning quantities GraphBuilder tracks (``_track``), all in pixels of
+    the first graph input: the width of one pixel of this tensor, how far one of its values can depend on the inputs (None: on the
+    whole field), the same without the ops that look at the whole field, and the lattice tile origins have to lie on."""
+    __slots__ = ('id', 'H', 'W', 'C', 'nmul', 'px', 'reach', 'local_reach', 'align', 'stats')
 
     def __init__(self, id, H, W, C, nmul=1):
         self.id, self.H, self.W, self.C, self.nmul = id, H, W, C, nmul
+        self.px, self.reach, self.local_reach, self.align = Fraction(1), Fraction(0), Fraction(0), 1
+        self.stats = frozenset()             # the channel-attention ops upstream: (op index, pixel width of its input, 5-D form)
 
     @property
     def shape(self):
@@ -47,6 +54,7 @@ class GraphBuilder:
         self.outputs = []
         self.layers = []                     # (kind, name, out_shape) for summary()
         self.finalized = False
+        self._n_chatt = 0                    # channel-attention ops so far (their order in the graph)
 
     def __del__(self):
         try:
@@ -63,8 +71,32 @@ class GraphBuilder:
         if requires_grad:
             _lib.check(self._l.dl4ds_graph_input_requires_grad(self.h, tid.value))
         t = Tensor(tid.value, int(H), int(W), int(C), int(nmul))
+        if self.inputs:                      # a later input on a finer (or coarser) grid, e.g. the HR static variables
+            t.px = Fraction(self.inputs[0].H, t.H)
         self.inputs.append(t)
         return t
+
+    # ---------------------------------------------------------------- reach and alignment
+    RESIZE_SUPPORT = {'nearest': 0, 'bilinear': 1, 'bicubic': 2, 'lanczos3': 3, 'lanczos5': 5, 'gaussian': 2, 'mitchellcubic': 2}
+
+    @staticmethod
+    def _track(y, srcs, add=0, px=None, unbounded=False, phase=False):
+        """Reach and alignment of the op output ``y`` from those of its operands ``srcs``.  ``add``: what the op adds to the reach, in
+        pixels of the first input (the caller scales by the operand's pixel width); ``px``: the output's pixel width where the op
+        changes it; ``unbounded``: the output depends on the whole field; ``phase``: the op shrinks the grid by a factor whose
+        groups start at pixel 0 (max-pool, a stride, a stepped slice), so tile origins must be multiples of the output's pixel width.
+        An op that makes pixels wider also reads the whole footprint of the wider pixel: px_out - px_in is added."""
+        y.px = Fraction(srcs[0].px if px is None else px)
+        grow = max(y.px - srcs[0].px, 0)
+        y.local_reach = max(s.local_reach for s in srcs) + Fraction(add) + grow
+        y.reach = None if unbounded or any(s.reach is None for s in srcs) else max(s.reach for s in srcs) + Fraction(add) + grow
+        align, stats = 1, frozenset()                          # (y may be one of its own operands: conv2d_folded's second call)
+        for s in srcs:
+            align, stats = math.lcm(align, s.align), stats | s.stats
+        y.align, y.stats = align, stats
+        if phase and y.px.denominator == 1:                    # (a group inside one input pixel never straddles a tile origin)
+            y.align = math.lcm(y.align, y.px.numerator)
+        return y
 
     def param(self, name, shape, init='glorot', trainable=True):
         shape = tuple(int(s) for s in shape)
@@ -96,6 +128,8 @@ class GraphBuilder:
         _lib.check(self._l.dl4ds_graph_conv2d(self.h, x.id, w, b, -1 if add is None else add.id, int(ks),
                                               int(filters), int(activation == 'relu'), int(d2s), ctypes.byref(out)))
         y = self._out(out.value, 'conv2d', name)
+        self._track(y, [x] + ([add] if add is not None else []), Fraction(int(ks) - 1, 2) * x.px,
+                    x.px / int(d2s) if d2s and d2s > 1 else None)
         if activation not in (None, 'relu'):
             y = self.act(y, activation, name + '/act')
         return y
@@ -121,6 +155,9 @@ class GraphBuilder:
             _lib.check(self._l.dl4ds_graph_conv2d_folded(self.h, x.id, w1, b1, w2, b2, int(ks), int(filters), int(filters2),
                                                          int(activation == 'relu'), int(d2s or 0), ctypes.byref(out)))
         y = self._out(out.value, 'conv2d+conv1x1 (folded)', name + ' -> ' + name2)
+        self._track(y, [x], Fraction(int(ks) - 1, 2) * x.px, x.px / int(d2s) if r2 > 1 else None)
+        if aux is not None:
+            self._track(y, [y, aux])
         if activation not in (None, 'relu'):
             y = self.act(y, activation, name2 + '/act')
         return y
@@ -131,7 +168,7 @@ class GraphBuilder:
         b = self.param(name + '/bias', (x.C,), 'zeros') if use_bias else -1
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_dwconv(self.h, x.id, w, b, int(ks), ctypes.byref(out)))
-        return self._out(out.value, 'depthwise_conv2d', name)
+        return self._track(self._out(out.value, 'depthwise_conv2d', name), [x], Fraction(int(ks) - 1, 2) * x.px)
 
     def conv2d_transpose(self, x, name, filters, ks, stride, activation=None):
         activation = _check_activation(activation)
@@ -140,6 +177,12 @@ class GraphBuilder:
         _lib.check(self._l.dl4ds_graph_conv2d_transpose(self.h, x.id, w, int(ks), int(stride), int(filters),
                                                         int(activation == 'relu'), ctypes.byref(out)))
         y = self._out(out.value, 'conv2d_transpose', name)
+        # y[i s + k - pb] += x[i] w[k], pb = (ks - s) // 2: output pixel Y = m s + f reads inputs ceil((f + pb - ks + 1) / s) ..
+        # floor((f + pb) / s) around m
+        ks_, s_ = int(ks), int(stride)
+        pb = max(ks_ - s_, 0) // 2
+        taps = max(max((ks_ - 1 - f - pb) // s_ if f + pb - ks_ + 1 < 0 else 0, (f + pb) // s_) for f in range(s_))
+        self._track(y, [x], taps * x.px, x.px / s_)
         if activation not in (None, 'relu'):
             y = self.act(y, activation, name + '/act')
         return y
@@ -154,18 +197,23 @@ class GraphBuilder:
         b2 = self.param(name + '/conv2/bias', (nf,), 'zeros')
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_chatt(self.h, x.id, w1, b1, w2, b2, cr, int(time_window_5d), ctypes.byref(out)))
-        return self._out(out.value, 'channel_attention', name)
+        # the output depends on the rest of the field through the C channel means only: the reach stays that of the local ops and the op
+        # is recorded, so that Model.receptive_halo / predict_tiled can decide whether those means can be supplied
+        y = self._track(self._out(out.value, 'channel_attention', name), [x])
+        y.stats = y.stats | {(self._n_chatt, x.px, bool(time_window_5d))}
+        self._n_chatt += 1
+        return y
 
     def concat(self, xs, name='concat'):
         ids = (ctypes.c_int * len(xs))(*[t.id for t in xs])
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_concat(self.h, ids, len(xs), ctypes.byref(out)))
-        return self._out(out.value, 'concat', name)
+        return self._track(self._out(out.value, 'concat', name), list(xs))
 
     def add(self, a, b, relu=False, name='add'):
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_add(self.h, a.id, b.id, int(relu), ctypes.byref(out)))
-        return self._out(out.value, 'add', name)
+        return self._track(self._out(out.value, 'add', name), [a, b])
 
     def act(self, x, kind, name='act'):
         kind = _check_activation(kind)
@@ -173,12 +221,12 @@ class GraphBuilder:
             return x
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_act(self.h, x.id, ACT_KINDS[kind], ctypes.byref(out)))
-        return self._out(out.value, 'activation:' + kind, name)
+        return self._track(self._out(out.value, 'activation:' + kind, name), [x])
 
     def maxpool2(self, x, name='maxpool'):
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_maxpool2(self.h, x.id, ctypes.byref(out)))
-        return self._out(out.value, 'maxpool2', name)
+        return self._track(self._out(out.value, 'maxpool2', name), [x], px=2 * x.px, phase=True)
 
     def resize(self, x, ho, wo, name='resize', interpolation='bilinear'):
         methods = {'bilinear': 0, 'nearest': 1, 'bicubic': 2, 'lanczos3': 3, 'lanczos5': 4, 'gaussian': 5, 'mitchellcubic': 6}
@@ -189,14 +237,19 @@ class GraphBuilder:
             raise ValueError(f'unknown Resizing interpolation {interpolation!r}; one of {sorted(methods)}')
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_resize_method(self.h, x.id, int(ho), int(wo), methods[interpolation], ctypes.byref(out)))
-        return self._out(out.value, 'resize_' + interpolation, name)
+        y = self._out(out.value, 'resize_' + interpolation, name)
+        fy, fx = Fraction(int(ho), x.H), Fraction(int(wo), x.W)
+        # an integer enlargement samples every source pixel at the same sub-pixel offsets wherever a tile starts; any other ratio ties
+        # the sampling positions to the size of the grid
+        whole = fy == fx and fy.denominator == 1
+        return self._track(y, [x], self.RESIZE_SUPPORT[interpolation] * x.px, x.px / fy if whole else None, unbounded=not whole)
 
     def localconv(self, x, name, filters=2, use_bias=True):
         w = self.param(name + '/kernel', (x.H, x.W, x.C, filters))
         b = self.param(name + '/bias', (x.H, x.W, filters), 'zeros') if use_bias else -1
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_localconv(self.h, x.id, w, b, int(filters), ctypes.byref(out)))
-        return self._out(out.value, 'locally_connected', name)
+        return self._track(self._out(out.value, 'locally_connected', name), [x], unbounded=True)      # (weights per grid point)
 
     def rec_tail_supported(self, cx, cs, co):
         yes = ctypes.c_int(0)
@@ -215,12 +268,12 @@ class GraphBuilder:
         b = self.param(tl_name + '/conv/bias', (co,), 'zeros')
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_rec_tail(self.h, x.id, s.id, wt, bt, wl, bl, w, b, int(T), int(co), ctypes.byref(out)))
-        return self._out(out.value, 'rec_tail', tl_name)
+        return self._track(self._out(out.value, 'rec_tail', tl_name), [x, s], unbounded=True)           # (holds a localconv)
 
     def repeat_time(self, x, T, name='repeat_time'):
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_repeat_time(self.h, x.id, int(T), ctypes.byref(out)))
-        return self._out(out.value, 'repeat_time', name)
+        return self._track(self._out(out.value, 'repeat_time', name), [x])
 
     def convlstm(self, x, name, filters, ks, T, activation=None):
         activation = _check_activation(activation)
@@ -231,6 +284,7 @@ class GraphBuilder:
         _lib.check(self._l.dl4ds_graph_convlstm(self.h, x.id, wk, wr, b, int(ks), int(filters), int(T),
                                                 int(activation == 'relu'), ctypes.byref(out)))
         y = self._out(out.value, 'convlstm2d', name)
+        self._track(y, [x], Fraction(int(ks) - 1, 2) * int(T) * x.px)       # (the recurrent kernel is applied once per time step)
         if activation not in (None, 'relu'):
             y = self.act(y, activation, name + '/act')
         return y
@@ -239,17 +293,18 @@ class GraphBuilder:
         out = ctypes.c_int()
         fn = self._l.dl4ds_graph_gap3d if over_time else self._l.dl4ds_graph_gap
         _lib.check(fn(self.h, x.id, ctypes.byref(out)))
-        return self._out(out.value, 'global_avg_pool', name)
+        return self._track(self._out(out.value, 'global_avg_pool', name), [x], unbounded=True)
 
     def slice2d(self, x, oy, ox, step, ho, wo, name='slice'):
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_slice(self.h, x.id, int(oy), int(ox), int(step), int(ho), int(wo), ctypes.byref(out)))
-        return self._out(out.value, 'slice', name)
+        return self._track(self._out(out.value, 'slice', name), [x], max(abs(int(oy)), abs(int(ox))) * x.px, x.px * int(step),
+                           phase=int(step) > 1)
 
     def pad_bottom_right(self, x, ho, wo, name='zero_padding'):
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_pad(self.h, x.id, int(ho), int(wo), ctypes.byref(out)))
-        return self._out(out.value, 'zero_padding', name)
+        return self._track(self._out(out.value, 'zero_padding', name), [x])
 
     def conv2d_strided(self, x, name, filters, ks, stride, padding='same'):
         """Conv2D(filters, ks, strides=stride, padding=...) as the stride-1 'same' convolution (MFMA path) followed by
@@ -275,7 +330,7 @@ class GraphBuilder:
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_dense(self.h, x.id, w, b, int(units), ACT_KINDS.get(activation, 0),
                                              ctypes.byref(out)))
-        return self._out(out.value, 'dense', name)
+        return self._track(self._out(out.value, 'dense', name), [x], unbounded=True)
 
     def dropout(self, x, rate, name='dropout', variant=None, dim=2):
         """get_dropout_layer -- blocks.py:679-706: identity for rate 0; 'vanilla' / 'gaussian' / 'spatial' and their
@@ -289,7 +344,7 @@ class GraphBuilder:
         kind, mc = kinds[variant]
         out = ctypes.c_int()
         _lib.check(self._l.dl4ds_graph_dropout_variant(self.h, x.id, float(rate), kind, mc, int(dim), ctypes.byref(out)))
-        return self._out(out.value, 'dropout' if variant is None else variant, name)
+        return self._track(self._out(out.value, 'dropout' if variant is None else variant, name), [x])
 
     def norm(self, x, name, kind, activation=None, epsilon=1e-3):
         """LayerNormalization() ('ln') / BatchNormalization() ('bn') with Keras variable names; a ReLU that follows is
@@ -307,6 +362,7 @@ class GraphBuilder:
         _lib.check(self._l.dl4ds_graph_norm(self.h, x.id, gamma, beta, mm, mv, int(kind == 'bn'), float(epsilon),
                                             int(activation == 'relu'), ctypes.byref(out)))
         y = self._out(out.value, 'batch_norm' if kind == 'bn' else 'layer_norm', name)
+        self._track(y, [x])               # (both normalise over the channel axis of one pixel; BatchNormalization predicts with moving statistics)
         if activation not in (None, 'relu'):
             y = self.act(y, activation, name + '/act')
         return y
@@ -435,6 +491,18 @@ def check_ensemble_args(n_members, quantiles, seed=None, batch_size=None):
     return int(n_members), q.astype(np.float32)
 
 
+def _gather_group_type():
+    """ctypes mirror of dl4ds_gather_group (include/dl4ds_hip.h)."""
+    class TapAxis(ctypes.Structure):
+        _fields_ = [('idx', ctypes.c_void_p), ('wt', ctypes.c_void_p), ('k', ctypes.c_int)]
+
+    class Group(ctypes.Structure):
+        _fields_ = [('src', ctypes.c_void_p), ('channels', ctypes.c_int), ('frames', ctypes.c_int), ('src_h', ctypes.c_int),
+                    ('src_w', ctypes.c_int), ('raw', ctypes.c_int), ('origin_from_crop', ctypes.c_int), ('row_div', ctypes.c_int),
+                    ('taps', TapAxis * 2)]
+    return Group
+
+
 class Model:
     """What a dl4ds builder returns (stands in for tf.keras.Model on the hot path)."""
 
@@ -527,6 +595,213 @@ class Model:
             if pinned:
                 lib.dl4ds_host_unregister(out.ctypes.data)
         return out
+
+    # --- tiled prediction
+    def _field_mean_op(self):
+        """The index of the model's ChannelAttention2D op whose channel means ``predict_tiled`` supplies from a first pass over the
+        tiles; None without one; False when the attention ops cannot be served: more than one (each would need a pass of its own
+        behind the previous one's), the 5-D form, or one that pools a tensor on another grid than the output's."""
+        t = self.graph.outputs[0]
+        if not t.stats:
+            return None
+        if len(t.stats) > 1:
+            return False
+        (index, px, five_d), = t.stats
+        return False if five_d or px != t.px else index
+
+    @property
+    def receptive_halo(self):
+        """How far, in pixels of the first input (rounded up), an output value can depend on the inputs other than through the
+        channel means of ONE ChannelAttention2D layer on the output grid: that is what every builder of ``dl4ds_amd.models`` ends in
+        (ConvBlock_att, sp_postups.py:204), and ``predict_tiled`` computes those means over the whole field in a first pass, so they
+        cost no halo.  None when the output depends on the whole field in any other way: global pooling, dense and locally connected
+        layers, or more than one channel attention (``attention=True``).  Farther than this from every tile edge that is not an edge
+        of the domain, a tile's output (given the field's channel means) equals the full grid's."""
+        t = self.graph.outputs[0]
+        return None if t.reach is None or self._field_mean_op() is False else int(math.ceil(t.reach))
+
+    @property
+    def local_halo(self):
+        """The same count with every op that looks at the whole field left out: the halo to hand to ``predict_tiled`` when
+        ``receptive_halo`` is None and per-tile statistics in those ops are acceptable."""
+        return int(math.ceil(self.graph.outputs[0].local_reach))
+
+    @property
+    def tile_align(self):
+        """Tile origins (and sizes) must be multiples of this many first-input pixels, so that max-pooling and strides group the same
+        pixels in a tile as on the full grid."""
+        return int(self.graph.outputs[0].align)
+
+    def predict_tiled(self, inputs, tile, halo=None, blend='crop', batch_size=32):
+        """``predict`` for grids whose full-grid graph does not fit (or is not wanted) in device memory: the network runs on
+        overlapping tiles of ``tile`` pixels (an int or a (rows, columns) pair, in pixels of the first input) and the tile outputs are
+        merged on the device (csrc/tiles.hip).  One sibling graph, planned for the tile, is all that is allocated (``resized``).
+
+        ``halo``: how many pixels inside each tile edge are discarded; None takes ``receptive_halo``.  With ``halo >=
+        receptive_halo`` every merged value comes from a position where the tile sees all the input it depends on, and the result
+        is the full-grid prediction up to the rounding of a different kernel schedule and of the channel means.  A model with one
+        ChannelAttention2D on the output grid (every builder's tail) takes TWO passes over the tiles: the first sums the attention's
+        input over the cores of the tiles (dl4ds_tile_pool, fp64, fixed order), the second runs with the field's means in place of
+        the tile's (dl4ds_graph_chatt_set_mean); that doubles the forward work and is skipped when one tile covers the domain.
+        When ``receptive_halo`` is None, ``halo`` MUST be given and the result is an APPROXIMATION: the ops that look at the whole
+        field then see one tile.  ``local_halo`` is the natural choice there.  ``blend``: 'crop' (each pixel from one tile), 'linear'
+        or 'hann' (a ramp across the overlap of the tiles' cores), see ``dl4ds_amd.tiling``.  ``tile`` must be a multiple of
+        ``tile_align``.
+
+        Per chunk of samples the inputs are uploaded once, tile batches of ``batch_size`` are cropped on the device
+        (dl4ds_batch_gather), run (dl4ds_graph_forward on device pointers) and merged (dl4ds_tile_merge), and the finished samples
+        come back into a page-locked result.  Sums and merge take the tiles in plan order whatever the batch size.  Every input's
+        grid must be an integer multiple of the first input's (the HR static variables of a post-upsampling model).
+
+        Out of scope (ValueError): models with ``localcon_layer=True`` (tied to their grid, as in ``resized``) and spatio-temporal
+        models (5-D inputs)."""
+        from .tiling import BLENDS, plan_tiles, tile_list, _pair
+        if isinstance(inputs, np.ndarray):
+            inputs = [inputs]
+        if len(self.input_shapes[0]) == 4 or np.ndim(inputs[0]) == 5:
+            raise ValueError('predict_tiled: spatio-temporal (5-D input) models are out of scope of tiled prediction; use predict')
+        rb = getattr(self, '_rebuild', None)
+        if rb is not None and rb[1].get('localcon_layer'):
+            raise ValueError('predict_tiled: a model with localcon_layer=True is tied to the grid it was built for and is out of '
+                             'scope of tiled prediction')
+        if blend not in BLENDS:
+            raise ValueError(f'unknown blend {blend!r}: use one of {BLENDS}')
+        check_batch_size(batch_size, integers_only=True)
+        if len(inputs) != len(self.graph.inputs):
+            raise ValueError(f'model {self.name} expects {len(self.graph.inputs)} inputs, got {len(inputs)}')
+        inputs = [np.ascontiguousarray(a, np.float32) for a in inputs]
+        first = inputs[0]
+        if first.ndim != 4:
+            raise ValueError(f'predict_tiled: inputs must be (N, H, W, C) arrays, got shape {first.shape}')
+        n, grid = first.shape[0], (first.shape[1], first.shape[2])
+        ratios = []
+        for a, ks in zip(inputs, self.input_shapes):
+            ry, rx = Fraction(a.shape[1], grid[0]), Fraction(a.shape[2], grid[1])
+            if a.ndim != 4 or a.shape[0] != n or a.shape[3] != ks[-1] or ry != rx or ry.denominator != 1 or \
+                    ry != Fraction(ks[0], self.input_shapes[0][0]):
+                raise ValueError(f'predict_tiled: input of shape {a.shape} does not go with a first input of shape {first.shape} (model '
+                                 f'inputs {self.input_shapes}): grids must be the integer multiple of the first input\'s that the '
+                                 'model was built with')
+            ratios.append(int(ry))
+        out_scale = Fraction(self.output_shape[0], self.input_shapes[0][0])
+        if out_scale.denominator != 1:
+            raise ValueError(f'predict_tiled: the output grid is {out_scale} times the first input\'s; only integer ratios can be tiled')
+        out_scale, c_out = int(out_scale), self.output_shape[-1]
+        if halo is None:
+            halo = self.receptive_halo
+            if halo is None:
+                raise ValueError(f'predict_tiled: the output of model {self.name} depends on the whole field (receptive_halo is None: '
+                                 'global pooling / channel attention / dense layers), so `halo` must be given and the result is an '
+                                 f'approximation; the reach of the convolutional part is local_halo = {self.local_halo}')
+        if int(halo) != halo or halo < 0:
+            raise ValueError(f'`halo` must be a non-negative integer, got {halo!r}')
+        plan = plan_tiles(grid, _pair(tile, 'tile'), int(halo), self.tile_align, blend, out_scale)
+        th, tw = plan[0].tile, plan[1].tile
+        sib = self if (th, tw) == tuple(self.input_shapes[0][:2]) else self.resized((th, tw))
+        iy, ix = tile_list(plan)
+        nt = len(iy)
+        oy, ox = plan[0].origins[iy], plan[1].origins[ix]
+        ho, wo = grid[0] * out_scale, grid[1] * out_scale
+        out = np.empty((n, ho, wo, c_out), np.float32)
+        if n == 0:
+            return out
+        lib = self.graph._l
+        per_sample = 4 * (sum(int(np.prod(a.shape[1:])) for a in inputs) + ho * wo * c_out)
+        chunk = int(max(1, min(n, self.TILED_CHUNK_BYTES // per_sample)))
+        bmax = int(max(1, min(int(batch_size), chunk * nt)))
+        i32 = lambda a: np.ascontiguousarray(a, np.int32)
+        Group = _gather_group_type()
+        # one channel attention on the output grid: its means over the FIELD come from a first pass (not needed when a tile is the field)
+        att = self._field_mean_op()
+        att = None if att is False or nt == 1 else att
+        if att is not None:
+            tid, c_att, plain = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+            _lib.check(lib.dl4ds_graph_chatt_info(sib.graph.h, att, ctypes.byref(tid), ctypes.byref(c_att), ctypes.byref(plain)))
+            if not plain.value:
+                raise ValueError('predict_tiled: the input of the channel attention is not a plain array in this graph')
+            c_att = c_att.value
+            crop = plan if blend == 'crop' else plan_tiles(grid, _pair(tile, 'tile'), int(halo), self.tile_align, 'crop', out_scale)
+        pinned = out.nbytes >= (1 << 22) and lib.dl4ds_host_register(out.ctypes.data, out.nbytes) == 0
+        try:
+            with Buffers() as buf:
+                dev_in = [buf.alloc((chunk,) + tuple(a.shape[1:])) for a in inputs]
+                dev_out = buf.alloc((chunk, ho, wo, c_out))
+                tiles_in = [buf.alloc((bmax, th * r, tw * r, a.shape[3])) for a, r in zip(inputs, ratios)]
+                tiles_out = buf.alloc((bmax, th * out_scale, tw * out_scale, c_out))
+                wy, wx = buf.own(DeviceArray.from_numpy(plan[0].weights)), buf.own(DeviceArray.from_numpy(plan[1].weights))
+                if att is not None:
+                    cwy, cwx = (buf.own(DeviceArray.from_numpy(p.weights)) for p in crop)
+                    sums, dev_mean = buf.alloc((chunk, c_att), np.float64), buf.alloc((chunk, 1, 1, c_att))
+                    tile_mean = buf.alloc((bmax, c_att))
+                in_ptrs = (ctypes.c_void_p * len(inputs))(*[d.ptr for d in tiles_in])
+                groups = (Group * 1)()
+
+                def gather(src_ptr, shape, s_, cy, cx, dst, h, w, b):
+                    g = groups[0]
+                    g.src, g.channels, g.frames, g.src_h, g.src_w = src_ptr, shape[3], 0, shape[1], shape[2]
+                    g.raw, g.origin_from_crop, g.row_div = 1, 0, 0
+                    _lib.check(lib.dl4ds_batch_gather(ctypes.addressof(groups), 1, s_.ctypes.data, None if cy is None else cy.ctypes.data,
+                                                      None if cx is None else cx.ctypes.data, dst.ptr, h, w, 1, b))
+
+                for i in range(0, n, chunk):
+                    m = min(chunk, n - i)
+                    for d, a in zip(dev_in, inputs):                               # the only upload of this chunk
+                        d.upload(a[i:i + m])
+                    _lib.check(lib.dl4ds_memset(dev_out.ptr, 0, m * ho * wo * c_out * 4))
+                    # the chunk's tiles, sample by sample in plan order, in batches of bmax
+                    smp = np.repeat(np.arange(m), nt)
+                    t_iy, t_ix, t_oy, t_ox = (np.tile(v, m) for v in (iy, ix, oy, ox))
+
+                    def run(each):
+                        for j in range(0, m * nt, bmax):
+                            b = min(bmax, m * nt - j)
+                            s_ = i32(smp[j:j + b])
+                            for d, a, r, dst in zip(dev_in, inputs, ratios, tiles_in):
+                                gather(d.ptr, a.shape, s_, i32(t_oy[j:j + b] * r), i32(t_ox[j:j + b] * r), dst, th * r, tw * r, b)
+                            each(j, b, s_)
+
+                    def pool(j, b, s_):
+                        _lib.check(lib.dl4ds_graph_forward(sib.graph.h, in_ptrs, len(inputs), b, 0, 0, tiles_out.ptr))
+                        p = ctypes.c_void_p()
+                        _lib.check(lib.dl4ds_graph_tensor_ptr(sib.graph.h, tid.value, 0, ctypes.byref(p)))
+                        ry, rx = i32(t_iy[j:j + b]), i32(t_ix[j:j + b])
+                        _lib.check(lib.dl4ds_tile_pool(p, b, th * out_scale, tw * out_scale, c_att, s_.ctypes.data, ry.ctypes.data,
+                                                       rx.ctypes.data, cwy.ptr, crop[0].weights.shape[0], cwx.ptr,
+                                                       crop[1].weights.shape[0], sums.ptr, m))
+
+                    def merge(j, b, s_):
+                        if att is not None:                                        # each tile gets the means of its sample's field
+                            gather(dev_mean.ptr, (m, 1, 1, c_att), s_, None, None, tile_mean, 1, 1, b)
+                        _lib.check(lib.dl4ds_graph_forward(sib.graph.h, in_ptrs, len(inputs), b, 0, 0, tiles_out.ptr))
+                        my, mx = i32(t_oy[j:j + b] * out_scale), i32(t_ox[j:j + b] * out_scale)
+                        ry, rx = i32(t_iy[j:j + b]), i32(t_ix[j:j + b])
+                        per_tile = th * out_scale * tw * out_scale * c_out
+                        for k in range(0, b, self.MERGE_MAX_TILES):                # (the entry takes 256 tiles; the split changes no bit)
+                            e = min(b, k + self.MERGE_MAX_TILES)
+                            parts = [v[k:e] for v in (my, mx, s_, ry, rx)]         # (contiguous int32 views, alive during the call)
+                            _lib.check(lib.dl4ds_tile_merge(tiles_out.ptr + 4 * k * per_tile, e - k, th * out_scale, tw * out_scale,
+                                                            c_out, *[v.ctypes.data for v in parts], wy.ptr, plan[0].weights.shape[0],
+                                                            wx.ptr, plan[1].weights.shape[0], dev_out.ptr, m, ho, wo))
+
+                    if att is not None:
+                        _lib.check(lib.dl4ds_memset(sums.ptr, 0, sums.nbytes))
+                        run(pool)
+                        total = sums.numpy()[:m]                                   # (m x C doubles: the only thing that comes back early)
+                        dev_mean.upload(np.ascontiguousarray((total / float(ho * wo)).astype(np.float32)))
+                        _lib.check(lib.dl4ds_graph_chatt_set_mean(sib.graph.h, att, tile_mean.ptr))
+                    try:
+                        run(merge)
+                    finally:
+                        if att is not None:                # (the sibling graph is cached: it must pool again; an error here must not
+                            lib.dl4ds_graph_chatt_set_mean(sib.graph.h, att, None)   # hide the one that is already on its way)
+                    dev_out.download(out[i:i + m])
+        finally:
+            if pinned:
+                lib.dl4ds_host_unregister(out.ctypes.data)
+        return out
+
+    MERGE_MAX_TILES = 256                  # tiles per dl4ds_tile_merge call (include/dl4ds_hip.h)
+    TILED_CHUNK_BYTES = 1 << 30            # device-resident inputs + output of one chunk of samples (predict_tiled)
 
     # --- MC-dropout ensembles (the MC* dropout variants of blocks.py:658-676 stay active at inference)
     def reseed_dropout(self, seed):

@@ -60,6 +60,27 @@ def predict(trainer, array, scale, array_in_hr=True, static_vars=None, predictor
     return (y, np.asarray(inputs[0])) if return_lr else y
 
 
+def predict_tiled(trainer, array, scale, tile, halo=None, blend='crop', array_in_hr=True, static_vars=None, predictors=None,
+                  time_window=None, time_metadata=None, interpolation='inter_area', batch_size=32, scaler=None, save_path=None,
+                  save_fname='y_hat.npy', return_lr=False, device='GPU'):
+    """``predict`` on a grid that is run tile by tile (``Model.predict_tiled``): the inputs are prepared as
+    ``predict`` prepares them, the network runs on overlapping tiles of ``tile`` pixels of its first input (the LR grid of a
+    post-upsampling model, the HR grid of a 'pin' model) and the tile outputs are merged on the device.  ``halo``, ``blend``: see
+    ``Model.predict_tiled`` (None: the model's ``receptive_halo``; a model whose reach is unbounded needs an explicit halo and
+    gives an approximation).  ``batch_size``: tiles per forward pass.  Scaler, saving and ``return_lr`` as in ``predict``.
+    Spatio-temporal models are out of scope (ValueError)."""
+    if time_window is not None:
+        raise ValueError('predict_tiled: spatio-temporal models (`time_window`) are out of scope of tiled prediction; use predict')
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    y = model.predict_tiled(inputs, tile, halo=halo, blend=blend, batch_size=batch_size)
+    if scaler is not None:
+        y = scaler.inverse_transform(y)
+    y = np.asarray(y, np.float32)
+    if save_path is not None and save_fname is not None:
+        np.save(save_path + ('' if save_path.endswith('/') else '/') + save_fname, y)
+    return (y, np.asarray(inputs[0])) if return_lr else y
+
+
 def _slope(scaler, shape):
     one = np.asarray(scaler.inverse_transform(np.ones(tuple(shape), np.float64)), np.float64)
     zero = np.asarray(scaler.inverse_transform(np.zeros(tuple(shape), np.float64)), np.float64)
@@ -296,6 +317,21 @@ class Predictor:
 
     def run(self):
         return predict(**self.kw)
+
+
+class TiledPredictor:
+    """``Predictor`` for tiled prediction: same constructor-then-``.run()`` shape, runs ``predict_tiled``."""
+
+    def __init__(self, trainer, array, scale, tile, halo=None, blend='crop', array_in_hr=False, static_vars=None, predictors=None,
+                 time_window=None, time_metadata=None, interpolation='inter_area', batch_size=32, scaler=None, save_path=None,
+                 save_fname='y_hat.npy', return_lr=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, tile=tile, halo=halo, blend=blend, array_in_hr=array_in_hr,
+                       static_vars=static_vars, predictors=predictors, time_window=time_window, time_metadata=time_metadata,
+                       interpolation=interpolation, batch_size=batch_size, scaler=scaler, save_path=save_path,
+                       save_fname=save_fname, return_lr=return_lr, device=device)
+
+    def run(self):
+        return predict_tiled(**self.kw)
 
 
 class EnsemblePredictor:

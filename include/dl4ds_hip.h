@@ -679,6 +679,40 @@ typedef struct dl4ds_gather_group {
 int dl4ds_batch_gather(const dl4ds_gather_group* groups, int n_groups, const int* idx_host, const int* cy_host,
                        const int* cx_host, float* out_dev, int out_h, int out_w, int T, int B);
 
+/* ---------------------------------------------------------------- tiled prediction
+ * The reference predicts a whole field in one call (inference.py:238, `model.predict(x_test_lr)`), with every activation of the full
+ * grid alive; Model.predict_tiled runs the network on overlapping tiles (dl4ds_batch_gather -> dl4ds_graph_forward with device
+ * pointers) and this entry merges a batch of tile outputs into the output field on the device:
+ *   out[sample[t]][oy[t] + y][ox[t] + x][c] += wy[wy_row[t]][y] * wx[wx_row[t]][x] * tiles[t][y][x][c]      t < n, y < th, x < tw
+ *   tiles_dev [n][th][tw][C], out_dev [N][H][W][C], wy_dev [wy_rows][th], wx_dev [wx_rows][tw] (fp32, device); the five lists are
+ *   host arrays of n ints: output origin of each tile, the sample it belongs to, its row in either weight table.
+ * Summation order: an output element is owned by one thread per call, which walks the covering tiles of the call in ascending t
+ * and applies acc = fmaf(w, v, acc) with w = wy * wx rounded to fp32, starting from the stored value; calls are ordered on the
+ * library stream.  Tiles handed over in ascending order therefore give the same bits however they are split into calls.  No
+ * floating-point atomics.  A tap whose wy or wx is exactly 0 is skipped (not multiplied): non-finite values under a zero weight
+ * never reach the output, and 0/1 weights copy the tile value.  16-byte accesses where tw * C, W * C and every ox * C are
+ * multiples of 4 and both pointers are 16-byte aligned, 4-byte accesses otherwise.  Cost beyond the streaming: each workgroup (one row
+ * of one tile) scans the n tiles of the call once and keeps those that share its row in LDS, which is why n is limited to 256; a
+ * longer batch is split into calls, which does not change a bit.  Refused before anything is launched: null
+ * pointers, sizes < 1, n > 256 or th > 65535, a tile that leaves the output, a sample or table row out of range, and a call made while
+ * the device error word is set (it stays set for dl4ds_sync to report).  Asynchronous on the library stream. */
+int dl4ds_tile_merge(const float* tiles_dev, int n, int th, int tw, int C, const int* oy_host, const int* ox_host,
+                     const int* sample_host, const int* wy_row_host, const int* wx_row_host, const float* wy_dev, int wy_rows,
+                     const float* wx_dev, int wx_rows, float* out_dev, int N, int H, int W);
+
+/* The field mean that ChannelAttention2D (blocks.py:585-593) needs when its input exists only tile by tile.  tile_pool adds, in fp64 and
+ * in a fixed order (no floating-point atomics), sum_yx wy[wy_row[t]][y] * wx[wx_row[t]][x] * tiles[t][y][x][c] to
+ * sums_dev[sample[t]][c] ([N][C] doubles): with the 0/1 weights of a 'crop' plan every pixel of the field counts once.  chatt_info:
+ * the graph's channel-attention ops in op order (an index past the last one is an error), the tensor each one pools (dl4ds_graph_tensor_ptr gives its data after a
+ * forward pass), its channel count, and whether that tensor is a plain contiguous [B][H][W][C] array of a 4-D model.  chatt_set_mean:
+ * the forward passes that follow use mean_dev [B][C] (device, read at each pass) instead of pooling over the op's input; NULL
+ * restores the pooling.  Inference only. */
+int dl4ds_tile_pool(const float* tiles_dev, int n, int th, int tw, int C, const int* sample_host, const int* wy_row_host,
+                    const int* wx_row_host, const float* wy_dev, int wy_rows, const float* wx_dev, int wx_rows, double* sums_dev,
+                    int N);
+int dl4ds_graph_chatt_info(dl4ds_graph* g, int index, int* tensor_in, int* channels, int* contiguous);
+int dl4ds_graph_chatt_set_mean(dl4ds_graph* g, int index, const float* mean_dev);
+
 /* ---------------------------------------------------------------- data parallelism (RCCL over xGMI)
  * replaces Horovod: hvd.init/rank/size (base.py:97-107), DistributedOptimizer / DistributedGradientTape
  * gradient averaging (supervised.py:365; cgan.py:608-611), broadcast of variables + optimiser slots from
