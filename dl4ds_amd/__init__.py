@@ -45,6 +45,8 @@ def __getattr__(name):
             'predict_tiled': '.inference', 'TiledPredictor': '.inference', 'plan_tiles': '.tiling',
             'climate_indices': '.indices', 'precipitation_indices': '.indices', 'temperature_indices': '.indices',
             'percentile_threshold': '.indices', 'index_scores': '.indices', 'check_index_args': '.indices',
+            'temporal_statistics': '.temporal', 'temporal_scores': '.temporal', 'temporal_from_sums': '.temporal',
+            'mann_kendall': '.temporal', 'trend_scores': '.temporal', 'check_temporal_args': '.temporal',
             'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',

@@ -741,6 +741,20 @@ int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long l
                     sum_dev, scratch(ws), ws);
     API_END
 }
+int dl4ds_temporal(const float* y_dev, const float* p_dev, size_t N, size_t per, const long long* period_starts_host, int P,
+                   const int* lags_host, int L, const float* thr_dev, int T, int thr_per_cell, int op, int spell_bins,
+                   int* valid_dev, double* moment_dev, int* pair_dev, double* lag_dev, int* trans_dev, int* spell_dev) {
+    API_BEGIN
+    const size_t ws = temporal_workspace_bytes(N, per, period_starts_host, P, lags_host, L, T, op, spell_bins);   // (refuses a bad request)
+    temporal(S(), y_dev, p_dev, N, per, period_starts_host, P, lags_host, L, thr_dev, T, thr_per_cell, op, spell_bins, valid_dev,
+             moment_dev, pair_dev, lag_dev, trans_dev, spell_dev, scratch(ws), ws);
+    API_END
+}
+int dl4ds_trend(const double* v_dev, int P, size_t per, int* valid_dev, long long* mk_dev, double* sen_dev) {
+    API_BEGIN
+    trend(S(), v_dev, P, per, valid_dev, mk_dev, sen_dev);
+    API_END
+}
 int dl4ds_spectrum(const float* y_dev, const float* p_dev, int N, int H, int W, int C, int detrend, int window, const int* bin_host,
                    int B, double* power_dev, long long* valid_dev, double* mean_dev) {
     API_BEGIN

@@ -222,6 +222,24 @@ size_t climate_indices_workspace_bytes(size_t N, size_t per, const long long* pe
 void climate_indices(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
                      int T, int thr_per_cell, int op, int window, int* valid, int* event, float* ext, double* sum, void* workspace,
                      size_t workspace_bytes);
+// Temporal verification (temporal.hip) of y and, when p is not null, of p on common validity (N samples of per
+// cells, S = 1 or 2 series) over the P periods of the HOST array period_starts [P + 1], at the L <= 4 lags of the HOST array lags
+// (strictly increasing, 1..32) and at T <= 4 thresholds (thr [T] or, thr_per_cell, [T][per]; DEVICE) under one comparison op:
+// valid [P][per], moment [P][S][2][per] (sum x, sum x^2), pair [P][L][per], lag [P][S][L][3][per] (sum a, sum b, sum a*b over the
+// pairs), trans [P][S][T][4][per] (n00, n01, n10, n11), spell [P][S][T][2][B][per] (run-length histograms of event and non-event
+// runs, B = spell_bins in 1..32).  Outputs may be null (not all; pair / lag need L > 0, trans / spell T > 0) and are overwritten;
+// fp64 sums in sample order.  temporal_workspace_bytes throws on a request the entry refuses, before anything is sized; the
+// workspace takes the period starts and the lags.  Synchronises the stream once, after their upload.
+constexpr int TMP_MAX_LAGS = 4, TMP_MAX_THRESHOLDS = 4, TMP_MAX_BINS = 32;
+size_t temporal_workspace_bytes(size_t N, size_t per, const long long* period_starts, int P, const int* lags, int L, int T, int op,
+                                int spell_bins);
+void temporal(hipStream_t s, const float* y, const float* p, size_t N, size_t per, const long long* period_starts, int P,
+              const int* lags, int L, const float* thr, int T, int thr_per_cell, int op, int spell_bins, int* valid, double* moment,
+              int* pair, double* lag, int* trans, int* spell, void* workspace, size_t workspace_bytes);
+// Trend per cell over the P <= 128 periods of v [P][per] (fp64, DEVICE; trend.hip): valid [per] the number of
+// finite values, mk [2][per] the Mann-Kendall S and its tie term, sen [per] Sen's slope.  Outputs may be null (not all).
+constexpr int TRD_MAX_PERIODS = 128;
+void trend(hipStream_t s, const double* v, int P, size_t per, int* valid, long long* mk, double* sen);
 // Spectral verification (spectrum.hip) of the N*C fields of y, p (N, H, W, C; p may be null): the unnormalised 2-D DFT of either
 // side in fp64 (kept cells, optional detrending and periodic Hann window), folded over the bins of the HOST map bin [H][W/2 + 1]
 // (values in [-1, B)) into power [N][C][4][B]; valid [N][C] kept cells, mean [N][C][2] the subtracted means.  Outputs are

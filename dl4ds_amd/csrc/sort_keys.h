@@ -92,9 +92,9 @@ __device__ __forceinline__ void group_tree(int t, F combine) {
 
 // bitonic network over ROWS independent rows of P keys (a power of two) at pitch PITCH in LDS, worked by the T threads of the
 // workgroup; with PAYLOAD idx is swapped alongside.  Compare-exchange c works on row c / (P/2); the direction comes from the index
-// within the row.  The caller synchronises before; every stage ends in a barrier.
-template <int P, int ROWS, int PITCH, int T, bool PAYLOAD>
-__device__ __forceinline__ void bitonic_rows(uint32_t* key, uint32_t* idx) {
+// within the row.  The caller synchronises before; every stage ends in a barrier.  K: the key type (uint32_t, or uint64_t in trend.hip).
+template <int P, int ROWS, int PITCH, int T, bool PAYLOAD, typename K = uint32_t>
+__device__ __forceinline__ void bitonic_rows(K* key, uint32_t* idx) {
     constexpr int LOGP = __builtin_ctz(P);
     static_assert((P & (P - 1)) == 0 && P >= 2, "bitonic_rows: P");
     for (int lk = 1; lk <= LOGP; ++lk) {
@@ -103,8 +103,8 @@ __device__ __forceinline__ void bitonic_rows(uint32_t* key, uint32_t* idx) {
                 const int g = c >> (LOGP - 1), q = c & (P / 2 - 1);
                 const int i = ((q >> lj) << (lj + 1)) | (q & ((1 << lj) - 1)), o = i + (1 << lj);
                 const bool up = ((i >> lk) & 1) == 0;
-                uint32_t* row = key + g * PITCH;
-                const uint32_t a = row[i], b = row[o];
+                K* row = key + g * PITCH;
+                const K a = row[i], b = row[o];
                 if ((a > b) == up) {
                     row[i] = b; row[o] = a;
                     if constexpr (PAYLOAD) {

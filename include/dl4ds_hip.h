@@ -391,6 +391,59 @@ int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, c
 int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P,
                           const float* thr_dev, int T, int thr_per_cell, int op, int window, int* valid_dev, int* event_dev,
                           float* ext_dev, double* sum_dev);
+/* Temporal verification along the time axis: the raw sums of the lag-k autocorrelation, the event transition counts and the
+ * histogram of spell lengths per grid cell and period, of one series or of two on common validity.  The reference has no
+ * counterpart; DESIGN.md section 24 carries the same definitions.
+ * y and p are fp32 with shape (N, H, W, C), in time order.  A cell is one (h, w, c), and per = H*W*C.  Cell c of sample n lives at
+ * x[n*per + c].  p_dev may be null.  S = 1 with y alone and S = 2 with both; series 0 is y, series 1 is p.
+ * The P periods are given by period_starts_host exactly as in dl4ds_climate_indices: a HOST array of int64 with P + 1 entries,
+ * strictly increasing, first 0, last N.  Nothing carries across a period boundary.
+ * A sample is VALID in a cell iff it is finite in every series supplied.  This is common validity, as in dl4ds_distribution, so
+ * the two series are compared on the same days.  -0.0 counts as +0.0.
+ * lags_host is a HOST array of 0 <= L <= 4 lags, strictly increasing, each in 1..32.
+ * There are 0 <= T <= 4 thresholds.  thr_dev, thr_per_cell and op mean exactly what they mean in dl4ds_climate_indices: [T] or
+ * [T][per] in a DEVICE array, op 0 is >=, 1 is >, 2 is <, 3 is <=, compared on float32.  Events, non-events, event runs and
+ * non-event runs are defined as there: an invalid sample ends both kinds of run.  spell_bins is B in 1..32.
+ * If thr(t, c) is not finite, every integer output of that (t, c) is -1 in every period.
+ * Per period p and cell c, each output may be null and is then skipped.  All outputs are overwritten.
+ *   valid_dev  int32 [P][per]              the number of valid samples
+ *   moment_dev fp64  [P][S][2][per]        sum x and sum x^2 over the valid samples of the period, each added one term at a time
+ *                                          in ascending sample order, starting from 0.0.  x^2 is formed in fp64 from the fp32
+ *                                          value, which is exact.
+ *   pair_dev   int32 [P][L][per]           the number of pairs (n, n + lag) with both samples inside the period and both valid
+ *   lag_dev    fp64  [P][S][L][3][per]     over exactly those pairs, in ascending n, with a = x_n and b = x_{n+lag}: sum a, sum b,
+ *                                          sum a*b.  The product is formed in fp64 from two fp32 values and is exact, so fused
+ *                                          and unfused evaluation give the same bits.
+ *   trans_dev  int32 [P][S][T][4][per]     over consecutive samples (n, n + 1) both inside the period and both valid: the counts
+ *                                          n00, n01, n10, n11.  The first digit is the state at n, the second at n + 1; 1 means
+ *                                          event.
+ *   spell_dev  int32 [P][S][T][2][B][per]  kind 0 is event runs, kind 1 is non-event runs.  Bin k - 1 holds the number of runs of
+ *                                          length k for k < B; the last bin holds the runs of length >= B.  Every maximal run
+ *                                          counts, including one cut by a period boundary or ended by an invalid sample.
+ * There are no floating-point atomics and no sum whose order can vary.  A repeated call gives the same bits.
+ * Refused (non-zero return, dl4ds_last_error): P < 1; starts that are not strictly increasing from 0 to N; N == 0, per == 0 or
+ * N >= 2^31; L, T or B out of range; a lag out of range or not increasing; an op outside 0..3; a null y_dev or period_starts_host;
+ * lags_host null with L > 0; thr_dev null with T > 0; pair_dev or lag_dev non-null with L == 0; trans_dev or spell_dev non-null
+ * with T == 0; all six outputs null.
+ * A lane owns one cell and walks one period in order, so parallelism is cells x periods.  Algorithmic traffic: 4*S B per element
+ * read once, the outputs written once. */
+int dl4ds_temporal(const float* y_dev, const float* p_dev, size_t N, size_t per, const long long* period_starts_host, int P,
+                   const int* lags_host, int L, const float* thr_dev, int T, int thr_per_cell, int op, int spell_bins,
+                   int* valid_dev, double* moment_dev, int* pair_dev, double* lag_dev, int* trans_dev, int* spell_dev);
+/* Trend per grid cell over the periods: Mann-Kendall and Sen's slope.  The reference has no counterpart; DESIGN.md section 24
+ * carries the same definitions.
+ * v_dev is fp64 [P][per]: one value per period and cell, in period order (annual prcptot, rx1day or a mean from
+ * dl4ds_climate_indices, say).  Time is the period index 0..P-1.  A value is valid iff finite, so gaps keep their true spacing.
+ * Comparisons are made on fp64.  Each output may be null; at least one must be non-null.
+ *   valid_dev int32 [per]     n, the number of valid values
+ *   mk_dev    int64 [2][per]  row 0: S = the sum over i < j, both valid, of sign(v_j - v_i).  row 1: the tie term, the sum over the
+ *                             groups of equal values of g(g - 1)(2g + 5).  Both are exact integers.
+ *   sen_dev   fp64  [per]     with the M = n(n - 1)/2 slopes s = (v_j - v_i) / (double)(j - i) for i < j both valid, sorted
+ *                             ascending: s[(M-1)/2] for odd M and (s[M/2 - 1] + s[M/2]) * 0.5 for even M.  The subtraction, the
+ *                             division and the addition are each rounded on their own; the division is correctly rounded.  A zero
+ *                             is written as +0.0.  NaN when n < 2.
+ * Refused: P < 1 or P > 128; per == 0; a null v_dev; all outputs null. */
+int dl4ds_trend(const double* v_dev, int P, size_t per, int* valid_dev, long long* mk_dev, double* sen_dev);
 /* Spectral verification of a prediction against an observation: binned power and cross spectra per field.  The reference has no
  * such metric; DESIGN.md section 16 carries the same definitions.  y, p are observation and prediction, fp32, shaped (N, H, W, C).
  * Each of the F = N*C planes is one field.  Fields are ordered [n][c].
