@@ -38,6 +38,7 @@ def __getattr__(name):
             'predict': '.inference', 'predict_ensemble': '.inference', 'EnsemblePredictor': '.inference',
             'verify_ensemble': '.inference', 'EnsembleVerifier': '.inference', 'ensemble_scores': '.metrics',
             'exceedance_scores': '.metrics', 'verify_exceedance': '.inference', 'ExceedanceVerifier': '.inference',
+            'multivariate_scores': '.metrics', 'verify_multivariate': '.inference', 'MultivariateVerifier': '.inference',
             'neighbourhood_scores': '.metrics', 'fss': '.metrics',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',

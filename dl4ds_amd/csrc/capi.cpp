@@ -700,6 +700,31 @@ int dl4ds_ensemble_exceedance_walk_limit(size_t K, size_t* samples_out) {
     *samples_out = exc_walk_limit(K);
     API_END
 }
+int dl4ds_ensemble_energy(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                          const float* weight_dev, double* dist_out_dev, long long* nvalid_out_dev) {
+    API_BEGIN
+    ensemble_energy_check(members_dev, K, n, member_stride, obs_dev, B, dist_out_dev, nvalid_out_dev);    // before the workspace is sized
+    const size_t ws = ensemble_energy_workspace_bytes(K, n, B);
+    ensemble_energy(S(), members_dev, K, n, member_stride, obs_dev, B, weight_dev, dist_out_dev, nvalid_out_dev,
+                    ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_ensemble_variogram(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                             const float* weight_dev, size_t planes, size_t H, size_t W, size_t C, int max_lag, int order_code,
+                             long long* npairs_out_dev, double* sums_out_dev) {
+    API_BEGIN
+    ensemble_variogram_check(members_dev, K, n, member_stride, obs_dev, B, planes, H, W, C, max_lag, order_code, npairs_out_dev,
+                             sums_out_dev);
+    const size_t ws = ensemble_variogram_workspace_bytes(B, planes, H, C, max_lag);
+    ensemble_variogram(S(), members_dev, K, n, member_stride, obs_dev, B, weight_dev, planes, H, W, C, max_lag, order_code,
+                       npairs_out_dev, sums_out_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_variogram_lags(int max_lag, int* dydx_out, int* count_out) {
+    API_BEGIN
+    variogram_lags(max_lag, dydx_out, count_out);
+    API_END
+}
 int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
               const int* windows_host, int n_windows, long long* sums_dev, long long* cont_dev, long long* valid_dev) {
     API_BEGIN

@@ -183,6 +183,29 @@ size_t exc_walk_limit(size_t K);
 void ensemble_exceedance(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
                          const float* thr, int T, int thr_per_cell, short* count, long long* sample_out, long long* cell_acc,
                          unsigned long long* table);
+// Multivariate verification of the ensemble members[K][n] against obs[n] (ensemble_multi.hip), 2 <= K <= 128, B whole samples of
+// n / B elements, weight [n / B] or null; an element is valid iff obs and all K members are finite and its weight (if any) is > 0.
+// ensemble_energy: dist_out [B][K (K + 1) / 2] = D_k = sum w (x_k - y)^2 (k < K), then G_kj = sum w (x_k - x_j)^2 row-major over
+// k < j, each term and sum in fp64 from the differences themselves; nvalid_out [B].  ensemble_variogram: a sample is planes x H x W
+// x C; per sample and lag of variogram_lags(max_lag) (ordered (dy, dx) in the upper half-plane, at most 98) npairs_out [B][L] and
+// sums_out [B][L][3] = sum (o - e)^2, sum o, sum e over the valid pairs of one H x W plane, o = |y_i - y_j|^p and e_k in fp32,
+// e = (sum_k e_k in fp64, member order) / K; order_code 0 / 1 / 2: p = 0.5 / 1 / 2.  Outputs are overwritten.  No floating-point
+// atomics; how a sample is split over workgroups depends on (K, sample shape, max_lag) alone: the sums of a sample have the same
+// bits for every B and every position in the call.  The *_check functions throw on a bad request (before a workspace is sized).
+constexpr int ENS_MULTI_MAX_MEMBERS = 128;
+int variogram_lags(int max_lag, int* dydx, int* count);
+void ensemble_energy_check(const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                           const double* dist_out, const long long* nvalid_out);
+size_t ensemble_energy_workspace_bytes(size_t K, size_t n, size_t B);
+void ensemble_energy(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                     const float* weight, double* dist_out, long long* nvalid_out, void* workspace, size_t workspace_bytes);
+void ensemble_variogram_check(const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                              size_t planes, size_t H, size_t W, size_t C, int max_lag, int order_code, const long long* npairs_out,
+                              const double* sums_out);
+size_t ensemble_variogram_workspace_bytes(size_t B, size_t planes, size_t H, size_t C, int max_lag);
+void ensemble_variogram(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B,
+                        const float* weight, size_t planes, size_t H, size_t W, size_t C, int max_lag, int order_code,
+                        long long* npairs_out, double* sums_out, void* workspace, size_t workspace_bytes);
 // Neighbourhood verification (fss.hip) of the N*C fields of y, p (N, H, W, C) at T thresholds and S window sizes (host arrays):
 // sums [N][C][T][S][3] = the exact integer sums D, F, O of the Fractions Skill Score, cont [N][C][T][4] = hits, misses, false
 // alarms, correct negatives over the valid (both finite) cells, valid [N][C] their count.  Outputs are overwritten.  Integer

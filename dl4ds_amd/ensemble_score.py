@@ -258,3 +258,150 @@ class ExceedanceScorer(_Accumulators):
             res['count_field'] = c
             res['probability_field'] = np.where(c >= 0, c.astype(np.float32) / np.float32(self.K), np.float32(np.nan))
         return res
+
+
+# ------------------------------------------------------------------------------------------------ energy and variogram scores
+MULTIVARIATE_MIN_MEMBERS, MULTIVARIATE_MAX_MEMBERS = 2, 128       # caps of dl4ds_ensemble_energy / dl4ds_ensemble_variogram
+MULTIVARIATE_MAX_LAG = 8
+VARIOGRAM_ORDERS = {0.5: 0, 1.0: 1, 2.0: 2}                       # order -> the entry's order code
+
+
+def check_multivariate_args(max_lag, order, lag_weights, fair, weights, sample_shape, n_members=None):
+    """Arguments of the multivariate verification -> (max_lag as int, the entry's order code, weights as a float32 array of
+    ``sample_shape`` or None).  ``max_lag``: an integer in 1 ... 8; ``order``: 0.5, 1 or 2; ``lag_weights``: 'inverse' or
+    'uniform'; ``fair``: a bool; ``weights``: None or finite numbers >= 0 that broadcast to one sample (what
+    ``losses.latitude_weights`` returns does); ``sample_shape``: (H, W, C) or (T, H, W, C), or None: the shape of ``weights`` is
+    not looked at (for a caller that does not know the sample's shape yet); ``n_members``: None or 2 ... 128.  Looks at its
+    arguments only (no library, no device)."""
+    if isinstance(max_lag, (bool, np.bool_)) or not isinstance(max_lag, (int, np.integer)) or not 1 <= max_lag <= MULTIVARIATE_MAX_LAG:
+        raise ValueError(f'`max_lag` must be an integer in 1 ... {MULTIVARIATE_MAX_LAG}, got {max_lag!r}')
+    if isinstance(order, (bool, np.bool_)) or not isinstance(order, (int, float, np.integer, np.floating)) \
+            or float(order) not in VARIOGRAM_ORDERS:
+        raise ValueError(f'`order` must be 0.5, 1 or 2, got {order!r}')
+    if not isinstance(lag_weights, str) or lag_weights not in ('inverse', 'uniform'):
+        raise ValueError(f"`lag_weights` must be 'inverse' or 'uniform', got {lag_weights!r}")
+    if not isinstance(fair, (bool, np.bool_)):
+        raise ValueError(f'`fair` must be True or False, got {fair!r}')
+    if n_members is not None and not MULTIVARIATE_MIN_MEMBERS <= int(n_members) <= MULTIVARIATE_MAX_MEMBERS:
+        raise ValueError(f'the energy and variogram scores take {MULTIVARIATE_MIN_MEMBERS} ... {MULTIVARIATE_MAX_MEMBERS} members, '
+                         f'got {n_members}')
+    if sample_shape is not None:
+        sample_shape = tuple(int(v) for v in sample_shape)
+        if len(sample_shape) not in (3, 4) or min(sample_shape) < 1:
+            raise ValueError(f'one sample must be shaped (H, W, C) or (T, H, W, C), got {sample_shape}')
+    w32 = None
+    if weights is not None:
+        try:
+            w = np.asarray(getattr(weights, 'values', weights))
+            if w.dtype == bool or w.dtype == object or not np.issubdtype(w.dtype, np.number) or np.iscomplexobj(w):
+                raise TypeError
+            w = w.astype(np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f'`weights` must be numbers, got {weights!r}') from None
+        with np.errstate(over='ignore'):
+            w32 = w.astype(np.float32)
+        if not np.isfinite(w32).all() or (w32 < 0).any():
+            raise ValueError('`weights` must be finite (as float32) and >= 0')
+        if sample_shape is not None:
+            try:                                                # (an (H, W) map, as `latitude_weights` makes it, gets the channel axis)
+                w32 = np.ascontiguousarray(np.broadcast_to(w32[..., None] if w32.ndim == 2 else w32, sample_shape))
+            except ValueError:
+                raise ValueError(f'`weights` of shape {w.shape} do not broadcast to one sample {sample_shape}') from None
+    return int(max_lag), VARIOGRAM_ORDERS[float(order)], w32
+
+
+def variogram_lags(max_lag):
+    """The lag list of ``dl4ds_variogram_lags`` (the library's own, so host and device cannot disagree; no device needed) ->
+    int array (L, 2) of (dy, dx)."""
+    lib = _lib.load()
+    out, count = (ctypes.c_int * (2 * 98))(), ctypes.c_int(0)
+    _lib.check(lib.dl4ds_variogram_lags(int(max_lag), out, ctypes.byref(count)))
+    return np.asarray(out[:2 * count.value], np.int64).reshape(count.value, 2)
+
+
+def multivariate_from_sums(dist, nvalid, npairs, sums, K, lags, lag_weights, fair):
+    """The result dict of the multivariate verification from the outputs of ``dl4ds_ensemble_energy`` and
+    ``dl4ds_ensemble_variogram`` (host arithmetic only, no library): ``dist`` (N, K (K + 1) / 2) fp64 (D_k, then G_kj over k < j),
+    ``nvalid`` (N,), ``npairs`` (N, L), ``sums`` (N, L, 3) (sum (o - e)^2, sum o, sum e), ``lags`` (L, 2).  Sums over members,
+    pairs, lags and samples go through ``math.fsum`` (samples in their order); a quotient with a zero denominator is NaN, and a
+    sample without a valid element has the energy score NaN and takes no part in the mean."""
+    import math
+    K = int(K)
+    dist = np.asarray(dist, np.float64)
+    nvalid = np.asarray(nvalid).astype(np.int64)
+    npairs = np.asarray(npairs).astype(np.int64)
+    sums = np.asarray(sums, np.float64)
+    lags = np.asarray(lags).astype(np.int64).reshape(-1, 2)
+    N, L = dist.shape[0], lags.shape[0]
+    if dist.shape != (N, K * (K + 1) // 2) or nvalid.shape != (N,) or npairs.shape != (N, L) or sums.shape != (N, L, 3):
+        raise ValueError(f'expected dist (N, {K * (K + 1) // 2}), nvalid (N,), npairs (N, {L}) and sums (N, {L}, 3), got '
+                         f'{dist.shape}, {nvalid.shape}, {npairs.shape}, {sums.shape}')
+    nan = float('nan')
+    c = 1.0 / (K * (K - 1)) if fair else 1.0 / (K * K)
+    member = np.sqrt(dist[:, :K])
+    pair = np.sqrt(dist[:, K:])
+    es = np.full(N, nan)
+    for i in range(N):
+        if nvalid[i] > 0:
+            es[i] = math.fsum(member[i].tolist()) / K - c * math.fsum(pair[i].tolist())
+    scored = [float(v) for v, m in zip(es, nvalid) if m > 0]
+    lag_distance = np.sqrt((lags.astype(np.float64) ** 2).sum(axis=1))
+    omega = 1.0 / lag_distance if lag_weights == 'inverse' else np.ones(L)
+    om = omega.tolist()
+
+    def weighted(s, n):                                         # sum_l w_l s_l / sum_l w_l n_l
+        den = math.fsum(w * float(v) for w, v in zip(om, n))
+        return math.fsum(w * float(v) for w, v in zip(om, s)) / den if den > 0 else nan
+
+    vs = np.asarray([weighted(sums[i, :, 0], npairs[i]) for i in range(N)], np.float64).reshape(N)
+    tot_n = [int(npairs[:, l].sum()) for l in range(L)]
+    tot = [[math.fsum(sums[:, l, q].tolist()) for q in range(3)] for l in range(L)]
+    per_lag = lambda q: np.asarray([tot[l][q] / tot_n[l] if tot_n[l] else nan for l in range(L)], np.float64).reshape(L)  # noqa: E731
+    return dict(energy_score=math.fsum(scored) / len(scored) if scored else nan, energy_score_per_sample=es,
+                member_distance=member, pair_distance=pair,
+                variogram_score=weighted([t[0] for t in tot], tot_n), variogram_score_per_sample=vs,
+                lags=lags, lag_distance=lag_distance, lag_weight=omega,
+                variogram_obs=per_lag(1), variogram_ens=per_lag(2), variogram_error=per_lag(0),
+                n_pairs=npairs, n_valid_per_sample=nvalid, n_members=K, fair=bool(fair),
+                dist_sums=dist, variogram_sums=sums)
+
+
+class MultivariateScorer(_Accumulators):
+    """The counterpart of ``Scorer`` for the energy and variogram scores (csrc/ensemble_multi.hip): per
+    batch the two entries write the per-sample sums, which come back with the batch; ``result`` derives the scores on the host
+    (``multivariate_from_sums``).  ``max_lag``, ``order_code``, ``w32``: what ``check_multivariate_args`` returned."""
+
+    def __init__(self, n_members, n_samples, sample_shape, max_lag, order, order_code, lag_weights, fair, w32, bmax):
+        npo = int(n_members) * (int(n_members) + 1) // 2
+        super().__init__(n_members, n_samples, sample_shape, False, bmax, (npo,), np.float64)
+        self.max_lag, self.order, self.order_code = int(max_lag), float(order), int(order_code)
+        self.lag_weights, self.fair = lag_weights, bool(fair)
+        self.lags = variogram_lags(self.max_lag)
+        L = self.lags.shape[0]
+        shape = self.sample_shape
+        self.planes = int(np.prod(shape[:-3], dtype=np.int64))
+        self.H, self.W, self.C = shape[-3:]
+        self.dev.update(nvalid=DeviceArray((self.bmax,), np.int64), npairs=DeviceArray((self.bmax, L), np.int64),
+                        vsums=DeviceArray((self.bmax, L, 3), np.float64))
+        if w32 is not None:
+            self.dev['weight'] = DeviceArray.from_numpy(np.ascontiguousarray(w32, np.float32).reshape(self.per))
+        self.nvalid = np.zeros((self.N,), np.int64)
+        self.npairs = np.zeros((self.N, L), np.int64)
+        self.vsums = np.zeros((self.N, L, 3), np.float64)
+
+    def _launch(self, stack_ptr, stride, obs_ptr, first, b):
+        d = self.dev
+        w = d['weight'].ptr if 'weight' in d else None
+        _lib.check(self.lib.dl4ds_ensemble_energy(stack_ptr, self.K, b * self.per, stride, obs_ptr, b, w, d['sample'].ptr,
+                                                  d['nvalid'].ptr))
+        _lib.check(self.lib.dl4ds_ensemble_variogram(stack_ptr, self.K, b * self.per, stride, obs_ptr, b, w, self.planes, self.H,
+                                                     self.W, self.C, self.max_lag, self.order_code, d['npairs'].ptr, d['vsums'].ptr))
+        d['nvalid'].download(self.nvalid[first:first + b])
+        d['npairs'].download(self.npairs[first:first + b])
+        d['vsums'].download(self.vsums[first:first + b])
+
+    def result(self):
+        res = multivariate_from_sums(self.sample_sums, self.nvalid, self.npairs, self.vsums, self.K, self.lags, self.lag_weights,
+                                     self.fair)
+        res['order'] = self.order
+        return res

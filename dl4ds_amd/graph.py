@@ -12,7 +12,8 @@ import numpy as np
 from . import _lib
 from ._chunks import check_batch_size, is_int
 from .device import Buffers, DeviceArray
-from .ensemble_score import ExceedanceScorer, Scorer, check_exceedance_args, check_score_args
+from .ensemble_score import (ExceedanceScorer, MultivariateScorer, Scorer, check_exceedance_args, check_multivariate_args,
+                             check_score_args)
 
 ACT_KINDS = {'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'leaky_relu': 5, 'selu': 6, 'gelu': 7}
 
@@ -871,6 +872,26 @@ class Model:
             thr = check_exceedance_args(thresholds, shape)
             return lambda n, bmax: ExceedanceScorer(n_members, n, shape, thr, return_fields, bmax)
         return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('exceedance', y_true, prepare), 'score_exceedance')
+
+    def score_multivariate(self, inputs, y_true, n_members, batch_size=32, seed=None, max_lag=4, order=0.5, lag_weights='inverse',
+                           fair=False, weights=None):
+        """``predict_ensemble`` plus the verification of the ensemble as a forecast of a FIELD against the observation ``y_true``
+        of shape (N,) + output_shape: the energy score and the variogram score, reduced on the device while each batch's member
+        stack is resident (csrc/ensemble_multi.hip).  Returns ``predict_ensemble``'s dict with one more key,
+        'multivariate': the dict ``metrics.multivariate_scores`` describes.  2 <= ``n_members`` <= 128.  An element is valid iff
+        its observation and all its members are finite (write NaN into ``y_true`` to mask) and its weight is > 0.  ``weights``:
+        finite numbers >= 0 that broadcast to one sample of the output (``losses.latitude_weights``); on another grid than the
+        model was built for that is the output of the re-planned sibling (``resized``).  The sums of a sample do not depend on
+        how the scored samples are grouped (the members do depend on ``batch_size``, as in ``predict_ensemble``)."""
+        n_members, q = check_ensemble_args(n_members, (), seed, batch_size)
+        # (weights are checked against the output's shape in _run_ensemble, once the model is the one planned for the inputs' grid)
+        check_multivariate_args(max_lag, order, lag_weights, fair, weights, None, n_members)
+
+        def prepare(shape):
+            lag, code, w32 = check_multivariate_args(max_lag, order, lag_weights, fair, weights, shape, n_members)
+            return lambda n, bmax: MultivariateScorer(n_members, n, shape, lag, order, code, lag_weights, fair, w32, bmax)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('multivariate', y_true, prepare),
+                                  'score_multivariate')
 
     def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, verify=None, who='predict_ensemble'):
         """The per-batch loop of ``predict_ensemble`` / ``score_ensemble`` / ``score_exceedance``: inputs (and the observation)

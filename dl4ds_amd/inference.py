@@ -3,7 +3,7 @@ import numpy as np
 
 from . import POSTUPSAMPLING_METHODS
 from .dataloader import create_batch_hr_lr
-from .ensemble_score import check_exceedance_args, check_score_args
+from .ensemble_score import check_exceedance_args, check_multivariate_args, check_score_args
 from .graph import check_ensemble_args
 from .metrics import _masked_observation
 
@@ -303,6 +303,36 @@ def verify_exceedance(trainer, array, scale, n_members, thresholds, y_true=None,
     return _saved_and_returned(res, 'exceedance', inputs, save_path, save_fname, return_lr)
 
 
+def verify_multivariate(trainer, array, scale, n_members, y_true=None, seed=None, max_lag=4, order=0.5, lag_weights='inverse',
+                        fair=False, weights=None, mask=None, array_in_hr=True, static_vars=None, predictors=None, time_window=None,
+                        time_metadata=None, interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
+                        save_fname='y_hat_multivariate.npz', return_lr=False, device='GPU'):
+    """``predict_ensemble`` plus the verification of the ensemble as a forecast of a FIELD: the energy score and the variogram
+    score, reduced on the device while the member stack is resident (``Model.score_multivariate``, csrc/ensemble_multi.hip):
+    returns ``predict_ensemble``'s dict of statistics with one more key, 'multivariate'; see ``metrics.multivariate_scores`` for
+    every key and for ``max_lag``, ``order``, ``lag_weights``, ``fair`` and ``weights`` (``losses.latitude_weights`` fits).
+
+    ``y_true``, ``mask``: as in ``verify_ensemble`` (the observation in physical units; None means the HR ``array`` itself, allowed
+    only with ``array_in_hr=True`` and without a ``scaler``).  ``scaler``: the observation goes through ``scaler.transform`` and
+    THE SCORES ARE TAKEN IN THE MODEL'S UNITS, where the members live: a distance between fields has no per-cell slope that would
+    carry it back.  NaN in ``y_true`` stays NaN through the transform.  ``save_path``: one ``np.savez`` of the statistics and the
+    scores (flattened with a ``multivariate_`` prefix).
+
+    Out of scope: recurrent models.  ``time_window is not None`` raises ValueError, because how the scores of overlapping windows
+    flatten to spatial samples is not defined yet."""
+    y_true = _check_verify_args(array, scale, n_members, y_true, (), seed, False, array_in_hr, time_window, batch_size, scaler,
+                                who='verify_multivariate', model_method='Model.score_multivariate')
+    check_multivariate_args(max_lag, order, lag_weights, fair, weights, None, n_members)
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    obs = _model_unit_observation(y_true, scaler, mask)
+    res = model.score_multivariate(inputs, obs, n_members, batch_size=batch_size, seed=seed, max_lag=max_lag, order=order,
+                                   lag_weights=lag_weights, fair=fair, weights=weights)
+    scores = res.pop('multivariate')
+    _finish_ensemble(res, scaler, time_window)
+    res['multivariate'] = scores
+    return _saved_and_returned(res, 'multivariate', inputs, save_path, save_fname, return_lr)
+
+
 class Predictor:
     """inference.py:12-106."""
 
@@ -379,3 +409,21 @@ class ExceedanceVerifier:
 
     def run(self):
         return verify_exceedance(**self.kw)
+
+
+class MultivariateVerifier:
+    """``EnsembleVerifier`` for the energy and variogram scores: same constructor-then-``.run()`` shape, runs
+    ``verify_multivariate``."""
+
+    def __init__(self, trainer, array, scale, n_members, y_true=None, seed=None, max_lag=4, order=0.5, lag_weights='inverse',
+                 fair=False, weights=None, mask=None, array_in_hr=False, static_vars=None, predictors=None, time_window=None,
+                 time_metadata=None, interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
+                 save_fname='y_hat_multivariate.npz', return_lr=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, n_members=n_members, y_true=y_true, seed=seed, max_lag=max_lag,
+                       order=order, lag_weights=lag_weights, fair=fair, weights=weights, mask=mask, array_in_hr=array_in_hr,
+                       static_vars=static_vars, predictors=predictors, time_window=time_window, time_metadata=time_metadata,
+                       interpolation=interpolation, batch_size=batch_size, scaler=scaler, save_path=save_path,
+                       save_fname=save_fname, return_lr=return_lr, device=device)
+
+    def run(self):
+        return verify_multivariate(**self.kw)

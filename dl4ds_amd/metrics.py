@@ -16,7 +16,8 @@ from . import _exact, _lib
 from ._chunks import check_batch_size, host_ensemble, paired_chunks
 from .device import DeviceArray
 from .dataloader import checkarray_ndim
-from .ensemble_score import ExceedanceScorer, Scorer, check_exceedance_args, check_score_args
+from .ensemble_score import (ExceedanceScorer, MultivariateScorer, Scorer, check_exceedance_args, check_multivariate_args,
+                             check_score_args)
 from .graph import check_ensemble_args
 
 
@@ -273,6 +274,36 @@ def exceedance_scores(y_true, members, thresholds, mask=None, batch_size=None, r
     thr = check_exceedance_args(thresholds, sample_shape)
     return host_ensemble(_masked_observation(y_true, mask), members, batch_size=batch_size,
                          make_scorer=lambda bmax: ExceedanceScorer(K, N, sample_shape, thr, return_fields, bmax))
+
+
+def multivariate_scores(y_true, members, max_lag=4, order=0.5, lag_weights='inverse', fair=False, weights=None, mask=None,
+                        batch_size=None):
+    """Verification of an ensemble the caller already has on the host as a forecast of a FIELD: the energy score (Gneiting et al.
+    2008, the multivariate CRPS) and the variogram score (Scheuerer & Hamill 2015, which sees the dependence between cells that
+    the per-cell scores of ``ensemble_scores`` cannot).  ``members`` shaped (K,) + y_true.shape, 2 <= K <= 128, against the
+    observation ``y_true`` shaped (N, H, W, C) or (N, T, H, W, C); uploaded in chunks of ``batch_size`` samples and reduced on the
+    device by the entries ``Model.score_multivariate`` uses (csrc/ensemble_multi.hip).  An element is valid
+    iff its observation and all its members are finite, ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it and its
+    weight is > 0.  ``weights``: finite numbers >= 0 that broadcast to one sample (``losses.latitude_weights``); they weight the
+    squared differences of the energy score and only decide validity for the variogram score.  ``fair``: the pair term of the
+    energy score over K (K - 1) instead of K^2.  ``max_lag`` (1 ... 8): pairs of cells of one H x W plane up to that distance;
+    ``order``: 0.5, 1 or 2; ``lag_weights``: 'inverse' (1 / distance) or 'uniform'.  Returns a dict (N samples, L lags):
+
+    * ``energy_score`` (mean over the samples with a valid element), ``energy_score_per_sample`` (N,), ``member_distance`` (N, K)
+      = sqrt(D_k), ``pair_distance`` (N, K (K - 1) / 2) = sqrt(G_kj) over k < j;
+    * ``variogram_score``, ``variogram_score_per_sample`` (N,): sum_l w_l sum (o - e)^2 / sum_l w_l n_pairs; ``lags`` (L, 2) as
+      (dy, dx), ``lag_distance``, ``lag_weight`` (L,); ``variogram_obs``, ``variogram_ens``, ``variogram_error`` (L,): the mean
+      of o, e and (o - e)^2 over all valid pairs of the lag; ``n_pairs`` (N, L);
+    * ``n_valid_per_sample`` (N,), ``n_members``, ``order``, ``fair``, and the raw float64 sums ``dist_sums`` (N, K (K + 1) / 2)
+      and ``variogram_sums`` (N, L, 3).
+
+    The per-sample sums have the same bits for every ``batch_size``."""
+    members, K, _, y_true = _host_ensemble_args(y_true, members, (), None, batch_size)
+    N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
+    lag, code, w32 = check_multivariate_args(max_lag, order, lag_weights, fair, weights, sample_shape, K)
+    return host_ensemble(_masked_observation(y_true, mask), members, batch_size=batch_size,
+                         make_scorer=lambda bmax: MultivariateScorer(K, N, sample_shape, lag, order, code, lag_weights, fair, w32,
+                                                                     bmax))
 
 
 FSS_DEFAULT_WINDOWS = (1, 3, 5, 9, 17, 33, 65)

@@ -282,6 +282,40 @@ int dl4ds_ensemble_exceedance(const float* members_dev, size_t K, size_t n, size
                               const float* thr_dev, int T, int thr_per_cell, short* count_dev, long long* sample_out_dev,
                               long long* cell_acc_dev, unsigned long long* table_dev);
 int dl4ds_ensemble_exceedance_walk_limit(size_t K, size_t* samples_out);
+/* Multivariate verification of an MC-dropout ensemble against an observation: the energy score (Gneiting et al. 2008) and the
+ * variogram score (Scheuerer & Hamill 2015), the scores that see the members' SPATIAL structure (every score above looks at one
+ * cell at a time).  The reference has neither; the definitions are DESIGN.md section 25.  members_dev, n, member_stride, obs_dev
+ * and B as for dl4ds_ensemble_score: K rows of n fp32 values (row k at members_dev + k * member_stride), here 2 <= K <= 128, the
+ * observation obs_dev [n], the n elements being B whole samples of P = n / B elements.  weight_dev (or null) [P]: a weight >= 0
+ * per cell of one sample.  An element is VALID iff its observation and all K members are finite (no NaN, no infinity) and, with
+ * weights, its cell weight is > 0: NaN in obs_dev is the masking mechanism.
+ * dl4ds_ensemble_energy, per sample b, over its valid elements i, w_i = 1 without weights:
+ *   D_k  = sum_i w_i (x_ki - y_i)^2,  k = 0 .. K - 1          G_kj = sum_i w_i (x_ki - x_kj)^2,  k < j
+ *   dist_out_dev [B][K (K + 1) / 2] fp64: the K values D_k, then G_kj row-major over k < j;  nvalid_out_dev [B] int64
+ *   (the host takes ES = (1/K) sum_k sqrt(D_k) - c sum_{k<j} sqrt(G_kj), c = 1 / K^2 or, fair, 1 / (K (K - 1)))
+ *   Every term is computed and accumulated in fp64: (double)x - (double)y, squared, times (double)w.  The pair terms come from
+ *   the differences themselves, never from a Gram matrix S_kk + S_jj - 2 S_kj, which cancels where members are close: every sum is
+ *   a sum of non-negative terms.  One read of the stack; K (K + 1) / 2 fp64 multiply-adds per element against 4 (K + 1) bytes.
+ * dl4ds_ensemble_variogram: a sample is planes x H x W x C (C innermost; planes: the product of its leading dimensions), a FIELD
+ * one H x W plane of it (fixed leading index and channel).  The lags are the offsets (dy, dx) with 0 < dy^2 + dx^2 <= max_lag^2
+ * and dy > 0 or (dy == 0 and dx > 0), ordered by (dy, dx) ascending: L <= 98 for 1 <= max_lag <= 8; dl4ds_variogram_lags writes
+ * them as L (dy, dx) pairs into the HOST array dydx_out (or null) and L into count_out (or null).  A pair (i, i + lag) is valid
+ * iff both elements are valid and lie in the same field.  Per valid pair, order p = 0.5 / 1 / 2 for order_code 0 / 1 / 2:
+ *   o = |y_i - y_j|^p, e_k = |x_ki - x_kj|^p: difference and power are float32 IEEE operations (sqrtf, fabsf, one multiply)
+ *   e = (sum_k (double)e_k) / K, summed in fp64 in member order k = 0, 1, ...
+ *   npairs_out_dev [B][L] int64;  sums_out_dev [B][L][3] fp64: sum (o - e)^2, sum o, sum e over the valid pairs
+ *   Weights only decide validity here (weight 0 excludes the element).
+ * All outputs are overwritten.  No floating-point atomics: a repeated call gives the same bits.  How a sample's elements are split
+ * over workgroups depends on (K, sample shape, max_lag) alone, and the partial sums are added in a fixed order: the sums of a
+ * sample have the same bits for every B and for every position of the sample inside a call.
+ * Refused (non-zero return, dl4ds_last_error): K or max_lag out of range, an unknown order code, n % B != 0, planes * H * W * C !=
+ * n / B, member_stride < n, a null member stack, observation or output. */
+int dl4ds_ensemble_energy(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                          const float* weight_dev, double* dist_out_dev, long long* nvalid_out_dev);
+int dl4ds_ensemble_variogram(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B,
+                             const float* weight_dev, size_t planes, size_t H, size_t W, size_t C, int max_lag, int order_code,
+                             long long* npairs_out_dev, double* sums_out_dev);
+int dl4ds_variogram_lags(int max_lag, int* dydx_out, int* count_out);
 /* Neighbourhood (scale- and threshold-dependent) verification of a prediction against an observation: the Fractions Skill Score
  * of Roberts & Lean (2008) and the 2 x 2 contingency table.  The reference has no such metric; the definitions are DESIGN.md
  * section 14.  y_dev / p_dev: observation and prediction, (N, H, W, C) fp32; each of the N*C planes is one field.
