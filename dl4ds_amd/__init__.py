@@ -48,6 +48,10 @@ def __getattr__(name):
             'percentile_threshold': '.indices', 'index_scores': '.indices', 'check_index_args': '.indices',
             'temporal_statistics': '.temporal', 'temporal_scores': '.temporal', 'temporal_from_sums': '.temporal',
             'mann_kendall': '.temporal', 'trend_scores': '.temporal', 'check_temporal_args': '.temporal',
+            'l_moments': '.extremes', 'block_maxima': '.extremes', 'peaks_over_threshold': '.extremes',
+            'lmoments_from_pwm': '.extremes', 'gev_from_lmoments': '.extremes', 'gumbel_from_lmoments': '.extremes',
+            'gpd_from_lmoments': '.extremes', 'return_levels': '.extremes', 'fit_gev': '.extremes', 'fit_gumbel': '.extremes',
+            'fit_gpd': '.extremes', 'extreme_scores': '.extremes', 'check_extreme_args': '.extremes',
             'net_postupsampling': '.models', 'net_pin': '.models', 'unet_pin': '.models',
             'recnet_postupsampling': '.models', 'recnet_pin': '.models', 'residual_discriminator': '.models',
             'DataGenerator': '.dataloader', 'create_batch_hr_lr': '.dataloader', 'create_pair_hr_lr': '.dataloader',

@@ -766,6 +766,20 @@ int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long l
                     sum_dev, scratch(ws), ws);
     API_END
 }
+int dl4ds_lmoments(const float* x_dev, size_t N, size_t per, size_t stride, int sign, int* valid_dev, double* pwm_dev) {
+    API_BEGIN
+    const size_t ws = lmoments_workspace_bytes(N, per, stride, sign);                // (refuses a bad request)
+    lmoments(S(), x_dev, N, per, stride, sign, valid_dev, pwm_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_pot_peaks(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P, const float* thr_dev,
+                    int thr_per_cell, int sign, int run, int K, int* count_dev, float* peak_dev, int* pos_dev) {
+    API_BEGIN
+    const size_t ws = pot_peaks_workspace_bytes(N, per, period_starts_host, P, sign, run, K);              // (refuses a bad request)
+    pot_peaks(S(), x_dev, N, per, period_starts_host, P, thr_dev, thr_per_cell, sign, run, K, count_dev, peak_dev, pos_dev,
+              scratch(ws), ws);
+    API_END
+}
 int dl4ds_temporal(const float* y_dev, const float* p_dev, size_t N, size_t per, const long long* period_starts_host, int P,
                    const int* lags_host, int L, const float* thr_dev, int T, int thr_per_cell, int op, int spell_bins,
                    int* valid_dev, double* moment_dev, int* pair_dev, double* lag_dev, int* trans_dev, int* spell_dev) {

@@ -245,6 +245,20 @@ size_t climate_indices_workspace_bytes(size_t N, size_t per, const long long* pe
 void climate_indices(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
                      int T, int thr_per_cell, int op, int window, int* valid, int* event, float* ext, double* sum, void* workspace,
                      size_t workspace_bytes);
+// Extreme-value verification (extremes.hip).  lmoments: per cell c < per Hosking's unbiased probability-weighted
+// moments b_0..b_3 of the finite values among sign * x[n*stride + c], n < N (stride >= per), summed in rank order in fp64 into
+// pwm [4][per] (NaN where n <= r), their number into valid [per]; either may be null.  pot_peaks: the declustered peaks of x (N
+// samples of per cells) over the threshold thr ([1] or, thr_per_cell, [per]; DEVICE) within the P periods of the HOST array
+// period_starts [P + 1]: count [per] the clusters, peak / pos [K][per] the first K peaks and their sample indices in order of
+// occurrence, NaN / -1 beyond the count (either may be null; K == 0 only counts).  Both *_workspace_bytes throw on a request
+// the entry refuses, before anything is sized; pot_peaks' workspace takes the period starts and it synchronises the stream once.
+constexpr int POT_MAX_RUN = 32;
+size_t lmoments_workspace_bytes(size_t N, size_t per, size_t stride, int sign);
+void lmoments(hipStream_t s, const float* x, size_t N, size_t per, size_t stride, int sign, int* valid, double* pwm, void* workspace,
+              size_t workspace_bytes);
+size_t pot_peaks_workspace_bytes(size_t N, size_t per, const long long* period_starts, int P, int sign, int run, int K);
+void pot_peaks(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
+               int thr_per_cell, int sign, int run, int K, int* count, float* peak, int* pos, void* workspace, size_t workspace_bytes);
 // Temporal verification (temporal.hip) of y and, when p is not null, of p on common validity (N samples of per
 // cells, S = 1 or 2 series) over the P periods of the HOST array period_starts [P + 1], at the L <= 4 lags of the HOST array lags
 // (strictly increasing, 1..32) and at T <= 4 thresholds (thr [T] or, thr_per_cell, [T][per]; DEVICE) under one comparison op:

@@ -425,6 +425,40 @@ int dl4ds_qmap_apply(const float* x_dev, float* out_dev, size_t B, size_t per, c
 int dl4ds_climate_indices(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P,
                           const float* thr_dev, int T, int thr_per_cell, int op, int window, int* valid_dev, int* event_dev,
                           float* ext_dev, double* sum_dev);
+/* Extreme-value verification: sorted probability-weighted moments per cell and declustered peaks over a threshold, the device
+ * side of L-moment fits (GEV, Gumbel, GPD) and N-year return levels.  The reference has no counterpart; DESIGN.md section 26
+ * carries the same definitions.
+ * dl4ds_lmoments.  Sample n of cell c lives at x_dev[n*stride + c] with stride >= per, so row 0 of dl4ds_climate_indices' ext_dev
+ *   (stride 2*per) and the peaks of dl4ds_pot_peaks are read in place.  sign is +1 or -1 and the sample is sign * x, so -1 serves
+ *   the lower tail and minima.  The valid samples of a cell are the finite ones (NaN is the masking mechanism); -0.0 counts as
+ *   +0.0.  Let n be their number and x_0 <= ... <= x_{n-1} their values in ascending order, widened exactly to fp64.  For r = 0..3:
+ *     S_r = the sum of w_r(j) * x_j over j = r..n-1, in ascending j, starting from its first term
+ *     w_0 = 1,  w_r(j) = w_{r-1}(j) * ((double)(j-r+1) / (double)(n-r))
+ *   Every division is correctly rounded.  Every multiplication and addition is rounded on its own (no fused multiply-add).
+ *     pwm_dev fp64 [4][per]   pwm_dev[r*per + c] = S_r / (double)n, NaN when n <= r: Hosking's unbiased b_0..b_3
+ *     valid_dev int32 [per]   n
+ *   Either output may be null, not both.  With ties the order of equal values does not matter.  Segments of up to 512 samples are
+ *   sorted in LDS, longer ones by the key-only radix sort of dl4ds_distribution in a workspace of at most 128 MiB per chunk of
+ *   cells; the lane that owns a cell then adds its values in rank order, so both engines give the same bits.  No atomics.
+ *   Refused (non-zero return, dl4ds_last_error): N == 0, per == 0, N >= 2^31, stride < per, sign not +-1, a null x_dev, both
+ *   outputs null.
+ * dl4ds_pot_peaks.  x, per, period_starts_host and P as in dl4ds_climate_indices (stride per; validity and -0.0 as there).  One
+ *   threshold in the DEVICE array thr_dev: thr_per_cell == 0 means [1], otherwise [per].  sign is +1 or -1, run is in 1..32.
+ *   With v = sign*x and u = sign*thr(c), compared on fp32, a valid sample is an EXCEEDANCE iff v > u.  A cluster opens at an
+ *   exceedance.  It closes after `run` consecutive valid non-exceedances, at an invalid sample, at a period boundary and at the end
+ *   of the series; run = 1 makes every maximal run of exceedances a cluster.  The peak of a cluster is its largest v, written as x
+ *   (not v) with a zero as +0.0, and its position is the sample index of the first occurrence of that value in the cluster.
+ *     count_dev int32 [per]     the number of clusters of the cell, also beyond K; -1 where the threshold is not finite
+ *     peak_dev  fp32  [K][per]  the peaks in order of occurrence, row k < min(count, K); NaN in the rows from count on (so
+ *                               dl4ds_lmoments reads the buffer as it is); all K rows NaN where the threshold is not finite
+ *     pos_dev   int32 [K][per]  their sample indices; -1 where peak_dev holds NaN
+ *   peak_dev and pos_dev may be null.  K == 0 only counts.  All outputs are overwritten.
+ *   Refused: what dl4ds_climate_indices refuses of N, per, P and the starts; a null x_dev, thr_dev, period_starts_host or
+ *   count_dev; sign not +-1; run outside 1..32; K < 0; K > 0 with peak_dev and pos_dev both null.
+ *   A lane owns one cell and walks the series in order.  Algorithmic traffic: 4 B per element read once. */
+int dl4ds_lmoments(const float* x_dev, size_t N, size_t per, size_t stride, int sign, int* valid_dev, double* pwm_dev);
+int dl4ds_pot_peaks(const float* x_dev, size_t N, size_t per, const long long* period_starts_host, int P, const float* thr_dev,
+                    int thr_per_cell, int sign, int run, int K, int* count_dev, float* peak_dev, int* pos_dev);
 /* Temporal verification along the time axis: the raw sums of the lag-k autocorrelation, the event transition counts and the
  * histogram of spell lengths per grid cell and period, of one series or of two on common validity.  The reference has no
  * counterpart; DESIGN.md section 24 carries the same definitions.
