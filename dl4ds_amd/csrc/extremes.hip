@@ -8,13 +8,10 @@
 //   S_r = sum_{j = r}^{n-1} w_r(j) * x_j in ascending j from its first term,   w_0 = 1,  w_r(j) = w_{r-1}(j) * ((j-r+1) / (n-r))
 // every quotient correctly rounded, every product and sum rounded on its own (no fused multiply-add), and
 //   pwm[r*per + c] = S_r / n  (NaN when n <= r),   valid[c] = n:
-// Hosking's unbiased b_0..b_3.  Equal values have equal bits, so the order inside a tie does not matter.  A third key-only client
-// of sort_keys.h, next to distribution.hip and qmap.hip, with qmap.hip's two engines:
-//  * N <= SORT_STRIDED_MAX: a workgroup loads G consecutive cells row by row into LDS rows of pitch P + 1, the bitonic network
-//    sorts the G rows, then the lane that owns a cell walks its row in rank order (bank (g*(P+1) + j) % 32: conflict-free).
-//  * longer: the 64 x 64 transposing gather writes the keys contiguous per cell into the workspace, the key-only radix sort sorts
-//    them, and a wave walks 64 cells: tiles of 64 cells x 64 ranks come through LDS (read with lanes along the ranks, walked with
-//    lanes along the cells).  Cells go through in chunks sized by the workspace budget.
+// Hosking's unbiased b_0..b_3.  Equal values have equal bits, so the order inside a tie does not matter.  The cells' ascending keys
+// come from the per-cell engine of cell_sort.h (sign < 0: the keys of -x).  N <= SORT_STRIDED_MAX: the lane that owns a cell walks
+// its LDS row in rank order.  Longer: a wave walks 64 cells of the chunk: tiles of 64 cells x 64 ranks come through LDS (read with
+// lanes along the ranks, walked with lanes along the cells).
 // Both walks are the same function on the same sequence of values: the same bits.  No atomics.
 //
 // pot_peaks.  x as in climate_indices (stride per), periods from period_starts, one threshold [1] or [per].  v = sign*x and
@@ -27,23 +24,16 @@
 #include "common.h"
 #include "ops.h"
 #include "prof.h"
-#include "sort_keys.h"
-#include <algorithm>
+#include "cell_sort.h"
+#include "periods.h"
 
 // every product and sum of the S_r walk is rounded on its own
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int LM_TR = 64;                              // gather and walk kernels: 64 cells x 64 samples per transposed tile
-constexpr int LM_THREADS = 512;                        // LDS engine: threads per workgroup
 constexpr int POT_CELLS = 64;                          // pot_peaks: cells (threads) per workgroup, one wave
 constexpr int POT_DEPTH = 16;                          // pot_peaks: samples a lane has in flight
-
-__device__ __forceinline__ uint32_t lm_key(float v, bool neg) {
-    v = neg ? -v : v;
-    return finite_bits(v) ? rank_key(v) : SORT_INVALID;
-}
 
 // the four running sums of one cell; add() takes the values in rank order j = 0, 1, ..., n-1
 struct PwmWalk {
@@ -74,28 +64,18 @@ struct PwmWalk {
     }
 };
 
-template <int P>
-constexpr int lm_group() { return 2 * (4096 / P > 16 ? 4096 / P : 16); }
-template <int P>
-constexpr size_t lm_lds_bytes() { return (size_t)lm_group<P>() * (P + 1) * 4; }
-
 // strided LDS engine: G cells of N <= P samples per workgroup
 template <int P>
-__global__ void __launch_bounds__(LM_THREADS) lmom_lds_kernel(const float* __restrict__ x, size_t N, size_t per, size_t stride, int neg,
-                                                             int* __restrict__ valid, double* __restrict__ pwm) {
-    constexpr int T = LM_THREADS, G = lm_group<P>(), PITCH = P + 1;
-    static_assert(G <= T, "lmom_lds_kernel: one lane per cell");
+__global__ void __launch_bounds__(CELL_THREADS) lmom_lds_kernel(const float* __restrict__ x, size_t N, size_t per, size_t stride, int neg,
+                                                               int* __restrict__ valid, double* __restrict__ pwm) {
+    constexpr int G = cell_group<P>(), PITCH = P + 1;
+    static_assert(G <= CELL_THREADS, "lmom_lds_kernel: one lane per cell");
     extern __shared__ __attribute__((aligned(16))) unsigned char lmom_lds[];
     uint32_t* key = reinterpret_cast<uint32_t*>(lmom_lds);                // [G][PITCH]
     const int t = threadIdx.x;
     const size_t c0 = (size_t)blockIdx.x * G;
     const int cells = (int)(per - c0 < (size_t)G ? per - c0 : (size_t)G);
-    for (int i = t; i < G * P; i += T) {                                  // sample k of the G cells: adjacent lanes, adjacent floats
-        const int k = i / G, g = i % G;
-        key[g * PITCH + k] = ((size_t)k < N && g < cells) ? lm_key(x[(size_t)k * stride + c0 + g], neg) : SORT_INVALID;
-    }
-    __syncthreads();
-    bitonic_rows<P, G, PITCH, T, false>(key, nullptr);
+    sorted_cell_rows<P>(x, N, stride, neg, c0, cells, key);
     if (t >= cells) return;
     const uint32_t* row = key + t * PITCH;
     const uint32_t n = bound<true>(row, (uint32_t)P, SORT_INVALID);
@@ -104,68 +84,28 @@ __global__ void __launch_bounds__(LM_THREADS) lmom_lds_kernel(const float* __res
     acc.store(n, c0 + t, per, valid, pwm);
 }
 
-// global engine, step 1: the keys of a chunk of `ncell` cells (the first at x), contiguous per cell, as qmap.hip's gather: a tile
-// of 64 cells x 64 samples is read with lanes along the cells and written with lanes along the samples.
-// blockIdx.x = cell block * etiles + sample block
-__global__ void __launch_bounds__(SORT_THREADS) lmom_gather_kernel(const float* __restrict__ x, size_t ncell, size_t N, size_t stride,
-                                                                 int neg, unsigned etiles, uint32_t* __restrict__ k) {
-    __shared__ uint32_t tk[LM_TR][LM_TR + 1];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const size_t c0 = (size_t)(blockIdx.x / etiles) * LM_TR, p0 = (size_t)(blockIdx.x % etiles) * LM_TR;
-    for (int e = ty; e < LM_TR; e += SORT_WAVES) {
-        const size_t cell = c0 + tx, pos = p0 + e;
-        tk[e][tx] = (cell < ncell && pos < N) ? lm_key(x[pos * stride + cell], neg) : SORT_INVALID;
-    }
-    __syncthreads();
-    for (int g = ty; g < LM_TR; g += SORT_WAVES) {
-        const size_t cell = c0 + g, pos = p0 + tx;
-        if (cell < ncell && pos < N) k[cell * N + pos] = tk[tx][g];
-    }
-}
-
 // global engine, step 3: one wave per 64 cells of the chunk, from their sorted keys
-__global__ void __launch_bounds__(LM_TR) lmom_walk_kernel(const uint32_t* __restrict__ k, size_t ncell, size_t N, size_t per,
+__global__ void __launch_bounds__(CELL_TR) lmom_walk_kernel(const uint32_t* __restrict__ k, size_t ncell, size_t N, size_t per,
                                                          size_t cell0, int* __restrict__ valid, double* __restrict__ pwm) {
-    __shared__ uint32_t tk[LM_TR][LM_TR + 1];
+    __shared__ uint32_t tk[CELL_TR][CELL_TR + 1];
     const int lane = threadIdx.x;
-    const size_t c0 = (size_t)blockIdx.x * LM_TR;
-    const int cells = (int)(ncell - c0 < (size_t)LM_TR ? ncell - c0 : (size_t)LM_TR);
+    const size_t c0 = (size_t)blockIdx.x * CELL_TR;
+    const int cells = (int)(ncell - c0 < (size_t)CELL_TR ? ncell - c0 : (size_t)CELL_TR);
     const bool live = lane < cells;
     const uint32_t n = live ? bound<true>(k + (c0 + lane) * N, (uint32_t)N, SORT_INVALID) : 0u;
     uint32_t nmax = n;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) nmax = max(nmax, (uint32_t)__shfl_xor((int)nmax, o, 64));
     PwmWalk acc;
-    for (uint32_t p0 = 0; p0 < nmax; p0 += LM_TR) {                       // (uniform)
+    for (uint32_t p0 = 0; p0 < nmax; p0 += CELL_TR) {                       // (uniform)
         __syncthreads();
         const size_t pos = (size_t)p0 + lane;
         for (int g = 0; g < cells; ++g) tk[g][lane] = pos < N ? k[(c0 + g) * N + pos] : SORT_INVALID;
         __syncthreads();
         if (live)
-            for (int e = 0; e < LM_TR && p0 + e < n; ++e) acc.add(p0 + e, n, (double)key_value(tk[lane][e]));
+            for (int e = 0; e < CELL_TR && p0 + e < n; ++e) acc.add(p0 + e, n, (double)key_value(tk[lane][e]));
     }
     if (live) acc.store(n, cell0 + c0 + lane, per, valid, pwm);
-}
-
-// workspace of `segs` cells: their keys, the sort's second buffer, the digit counts per tile
-struct Workspace {
-    uint32_t *k, *tmp, *hist;
-    Workspace(Carver& w, size_t segs, size_t ntiles, size_t L)
-        : k(w.take<uint32_t>(segs * L)), tmp(w.take<uint32_t>(segs * L)), hist(w.take<uint32_t>(segs * ntiles * SORT_RADIX)) {}
-};
-
-template <int P>
-void launch_lmom_lds(hipStream_t s, const float* x, size_t N, size_t per, size_t stride, int neg, int* valid, double* pwm) {
-    auto kern = lmom_lds_kernel<P>;
-    static bool once = false;
-    if (!once) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)lm_lds_bytes<P>()));
-        once = true;
-    }
-    DL4DS_LAUNCH(kern, dim3((unsigned)cdivz(per, lm_group<P>())), dim3(LM_THREADS), lm_lds_bytes<P>(), s, x, N, per, stride, neg, valid,
-                 pwm);
-    HIP_CHECK(hipGetLastError());
 }
 
 // ------------------------------------------------------------------------------------------------------------------ pot_peaks
@@ -180,15 +120,13 @@ struct PotArgs {
     int* pos;
 };
 
-__device__ __forceinline__ bool pot_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }       // false for NaN
-
 __global__ void __launch_bounds__(POT_CELLS) pot_peaks_kernel(const PotArgs a) {
     const size_t per = a.per, c = (size_t)blockIdx.x * POT_CELLS + threadIdx.x;
     const bool live = c < per;
     const size_t cc = live ? c : per - 1;                                 // an idle lane walks the last cell and stores nothing
     const bool neg = a.neg != 0;
     const float t0 = a.thr_per_cell ? a.thr[cc] : a.thr[0];
-    const bool thr_ok = pot_finite(t0);
+    const bool thr_ok = finite_f32(t0);
     const float u = neg ? -t0 : t0;
     const int K = a.K, run = a.run;
     const float nan32 = __builtin_nanf("");
@@ -226,7 +164,7 @@ __global__ void __launch_bounds__(POT_CELLS) pot_peaks_kernel(const PotArgs a) {
                 close();
                 nb = (size_t)a.starts[++p + 1];                           // n < N = starts[P]: p + 1 <= P
             }
-            const bool ok = pot_finite(blk[k]);
+            const bool ok = finite_f32(blk[k]);
             const float x = blk[k] == 0.f ? 0.f : blk[k];                 // -0.0 counts as +0.0
             const float v = neg ? -x : x;
             if (!ok) {
@@ -257,8 +195,7 @@ size_t lmoments_workspace_bytes(size_t N, size_t per, size_t stride, int sign) {
     DL4DS_REQUIRE(per < (size_t(1) << 36), "lmoments: too many cells");
     DL4DS_REQUIRE(stride >= per, "lmoments: the stride between samples must be at least the number of cells");
     DL4DS_REQUIRE(sign == 1 || sign == -1, "lmoments: sign must be +1 or -1");
-    if (N <= (size_t)SORT_STRIDED_MAX) return 0;
-    return plan_chunks<Workspace>(per, N).bytes();
+    return cell_sort_workspace_bytes(N, per);
 }
 
 void lmoments(hipStream_t s, const float* x, size_t N, size_t per, size_t stride, int sign, int* valid, double* pwm, void* workspace,
@@ -266,30 +203,14 @@ void lmoments(hipStream_t s, const float* x, size_t N, size_t per, size_t stride
     const size_t need = lmoments_workspace_bytes(N, per, stride, sign);   // (refuses a bad request)
     DL4DS_REQUIRE(x, "lmoments: null array");
     DL4DS_REQUIRE(valid || pwm, "lmoments: both outputs are null");
-    const bool lds = N <= (size_t)SORT_STRIDED_MAX;
+    if (need) DL4DS_REQUIRE(workspace && workspace_bytes >= need, "lmoments workspace too small");
     const int neg = sign < 0;
-    ProfScope ps(s, lds ? "lmoments_strided" : "lmoments_global", 0.0, 4.0 * (double)N * (double)per);
-    if (lds) {
-        if (N <= 64) return launch_lmom_lds<64>(s, x, N, per, stride, neg, valid, pwm);
-        if (N <= 128) return launch_lmom_lds<128>(s, x, N, per, stride, neg, valid, pwm);
-        if (N <= 256) return launch_lmom_lds<256>(s, x, N, per, stride, neg, valid, pwm);
-        return launch_lmom_lds<SORT_STRIDED_MAX>(s, x, N, per, stride, neg, valid, pwm);
-    }
-    DL4DS_REQUIRE(workspace && workspace_bytes >= need, "lmoments workspace too small");
-    const Chunk c = plan_chunks<Workspace>(per, N);
-    Carver carver{static_cast<char*>(workspace)};
-    const Workspace w(carver, c.segs, c.ntiles, N);
-    const unsigned nt = (unsigned)c.ntiles, etiles = (unsigned)cdivz(N, LM_TR);
-    for (size_t c0 = 0; c0 < per; c0 += c.segs) {
-        const size_t nc = std::min(c.segs, per - c0);
-        const size_t cblocks = cdivz(nc, LM_TR);
-        DL4DS_REQUIRE(cblocks * etiles < (size_t(1) << 31), "lmoments: too many tiles for one launch");
-        DL4DS_LAUNCH(lmom_gather_kernel, dim3((unsigned)(cblocks * etiles)), dim3(SORT_THREADS), 0, s, x + c0, nc, N, stride, neg, etiles,
-                     w.k);
-        segmented_sort<false>(s, KeyBuffer{w.k}, w.k, nullptr, w.tmp, nullptr, nc, N, nt, w.hist);
-        DL4DS_LAUNCH(lmom_walk_kernel, dim3((unsigned)cblocks), dim3(LM_TR), 0, s, (const uint32_t*)w.k, nc, N, per, c0, valid, pwm);
-    }
-    HIP_CHECK(hipGetLastError());
+    cell_sort(
+        s, "lmoments", x, N, per, stride, neg, workspace,
+        [&](auto P) { launch_cell_lds<P(), lmom_lds_kernel<P()>>(s, per, x, N, per, stride, neg, valid, pwm); },
+        [&](const uint32_t* keys, size_t nc, size_t c0) {
+            DL4DS_LAUNCH(lmom_walk_kernel, dim3((unsigned)cdivz(nc, CELL_TR)), dim3(CELL_TR), 0, s, keys, nc, N, per, c0, valid, pwm);
+        });
 }
 
 size_t pot_peaks_workspace_bytes(size_t N, size_t per, const long long* period_starts, int P, int sign, int run, int K) {
@@ -299,13 +220,9 @@ size_t pot_peaks_workspace_bytes(size_t N, size_t per, const long long* period_s
     DL4DS_REQUIRE(sign == 1 || sign == -1, "pot_peaks: sign must be +1 or -1");
     DL4DS_REQUIRE(run >= 1 && run <= POT_MAX_RUN, "pot_peaks: 1 <= run <= 32");
     DL4DS_REQUIRE(K >= 0, "pot_peaks: K must not be negative");
-    DL4DS_REQUIRE(period_starts, "pot_peaks: null period starts");
-    DL4DS_REQUIRE((size_t)P <= N && period_starts[0] == 0 && period_starts[P] == (long long)N,
-                  "pot_peaks: period starts must be strictly increasing from 0 to N");
-    for (int p = 0; p < P; ++p)
-        DL4DS_REQUIRE(period_starts[p + 1] > period_starts[p], "pot_peaks: period starts must be strictly increasing from 0 to N");
+    check_period_starts("pot_peaks", period_starts, P, N);
     DL4DS_REQUIRE(cdivz(per, POT_CELLS) < (size_t(1) << 31), "pot_peaks: too many cells for one launch");
-    return ((size_t)P + 1) * sizeof(long long);
+    return period_starts_bytes(P);
 }
 
 void pot_peaks(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
@@ -315,9 +232,7 @@ void pot_peaks(hipStream_t s, const float* x, size_t N, size_t per, const long l
     DL4DS_REQUIRE(count, "pot_peaks: null count output");
     DL4DS_REQUIRE(K == 0 || peak || pos, "pot_peaks: K > 0 with both the peak and the position output null");
     DL4DS_REQUIRE(workspace && workspace_bytes >= need, "pot_peaks workspace too small");
-    long long* starts = static_cast<long long*>(workspace);
-    HIP_CHECK(hipMemcpyAsync(starts, period_starts, need, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));                                   // the caller's array may go away after the call
+    const long long* starts = upload_period_starts(s, period_starts, P, workspace);
     const PotArgs a{x, N, per, starts, thr, thr_per_cell, sign < 0, run, K, count, peak, pos};
     ProfScope ps(s, "pot_peaks", 0.0, 4.0 * (double)N * (double)per + (double)per * (4.0 + (peak ? 4.0 * K : 0.0) + (pos ? 4.0 * K : 0.0)));
     DL4DS_LAUNCH(pot_peaks_kernel, dim3((unsigned)cdivz(per, POT_CELLS)), dim3(POT_CELLS), 0, s, a);

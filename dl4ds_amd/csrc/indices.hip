@@ -32,6 +32,7 @@
 // order of the fp64 sums: parallelism is cells x periods.
 #include "common.h"
 #include "ops.h"
+#include "periods.h"
 #include "prof.h"
 #include <vector>
 
@@ -53,8 +54,6 @@ struct IdxArgs {
     double* sum;
 };
 
-__device__ __forceinline__ bool idx_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }       // false for NaN
-
 // GLOBAL_WINDOW: the window's values are read again from global memory (L2) instead of the LDS ring
 template <int T, bool GLOBAL_WINDOW>
 __global__ void __launch_bounds__(IDX_CELLS) climate_indices_kernel(const IdxArgs a) {
@@ -66,7 +65,7 @@ __global__ void __launch_bounds__(IDX_CELLS) climate_indices_kernel(const IdxArg
     const size_t cc = live ? c : per - 1;                                 // an idle lane walks the last cell and stores nothing
     const size_t s0 = (size_t)a.starts[p], s1 = (size_t)a.starts[p + 1];
     const int len = (int)(s1 - s0), w = a.window;
-    const bool neg = a.op >= 2, strict = a.op == 1 || a.op == 2;          // x < t is -x > -t, x <= t is -x >= -t (exact)
+    const auto [neg, strict] = decode_op(a.op);
 
     float thr[T];
     bool thr_ok[T];
@@ -75,7 +74,7 @@ __global__ void __launch_bounds__(IDX_CELLS) climate_indices_kernel(const IdxArg
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const float v = a.thr_per_cell ? a.thr[(size_t)t * per + cc] : a.thr[t];
-        thr_ok[t] = idx_finite(v);
+        thr_ok[t] = finite_f32(v);
         thr[t] = neg ? -v : v;
         n_event[t] = run_e[t] = run_n[t] = long_e[t] = long_n[t] = n_runs[t] = 0;
         first[t] = last[t] = -1;
@@ -97,7 +96,7 @@ __global__ void __launch_bounds__(IDX_CELLS) climate_indices_kernel(const IdxArg
         for (int u = 0; u < IDX_DEPTH; ++u) {
             const int i = i0 + u;
             if (i >= len) break;                                          // (uniform)
-            const bool ok = idx_finite(blk[u]);
+            const bool ok = finite_f32(blk[u]);
             const float v = blk[u] == 0.f ? 0.f : blk[u];                 // -0.0 counts as +0.0
             if (!GLOBAL_WINDOW) ring[(i & (IDX_RING - 1)) * IDX_CELLS + tid] = v;
             const double d = (double)v;
@@ -179,13 +178,9 @@ size_t climate_indices_workspace_bytes(size_t N, size_t per, const long long* pe
     DL4DS_REQUIRE(T >= 1 && T <= IDX_MAX_THRESHOLDS, "climate_indices: 1 <= T <= 4 thresholds");
     DL4DS_REQUIRE(window >= 1 && window <= IDX_RING, "climate_indices: 1 <= window <= 32");
     DL4DS_REQUIRE(op >= 0 && op <= 3, "climate_indices: op must be 0 (>=), 1 (>), 2 (<) or 3 (<=)");
-    DL4DS_REQUIRE(period_starts, "climate_indices: null period starts");
-    DL4DS_REQUIRE((size_t)P <= N && period_starts[0] == 0 && period_starts[P] == (long long)N,
-                  "climate_indices: period starts must be strictly increasing from 0 to N");
-    for (int p = 0; p < P; ++p)
-        DL4DS_REQUIRE(period_starts[p + 1] > period_starts[p], "climate_indices: period starts must be strictly increasing from 0 to N");
+    check_period_starts("climate_indices", period_starts, P, N);
     DL4DS_REQUIRE(cdivz(per, IDX_CELLS) * (size_t)P < (size_t(1) << 31), "climate_indices: too many cells x periods for one launch");
-    return ((size_t)P + 1) * sizeof(long long);
+    return period_starts_bytes(P);
 }
 
 void climate_indices(hipStream_t s, const float* x, size_t N, size_t per, const long long* period_starts, int P, const float* thr,
@@ -195,9 +190,7 @@ void climate_indices(hipStream_t s, const float* x, size_t N, size_t per, const 
     DL4DS_REQUIRE(x && thr, "climate_indices: null array or thresholds");
     DL4DS_REQUIRE(valid || event || ext || sum, "climate_indices: all four outputs are null");
     DL4DS_REQUIRE(workspace && workspace_bytes >= need, "climate_indices workspace too small");
-    long long* starts = static_cast<long long*>(workspace);
-    HIP_CHECK(hipMemcpyAsync(starts, period_starts, need, hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));                                   // the caller's array may go away after the call
+    const long long* starts = upload_period_starts(s, period_starts, P, workspace);
     const IdxArgs a{x, per, starts, (unsigned)P, thr, thr_per_cell, op, window, valid, event, ext, sum};
     const unsigned blocks = (unsigned)(cdivz(per, IDX_CELLS) * (size_t)P);
     const double cells = (double)per * P;

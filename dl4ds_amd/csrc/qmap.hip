@@ -6,14 +6,9 @@
 // +0.0); with x_0 <= ... <= x_{n-1} the ascending valid values and q_i the Q probabilities (fp64, strictly increasing, in [0, 1]):
 //   h = q_i*(n-1), j = floor(h), g = h - j, val = x_j + (x_{min(j+1, n-1)} - x_j) * g      in fp64, not contracted (numpy 'linear')
 // rounded once to fp32 into table[i*per + c] ([Q][per]: neighbouring lanes of the map read neighbouring addresses); n = 0 gives NaN
-// in all Q entries; valid[c] = n.  It runs on the engines of sort_keys.h, as distribution.hip does for seg_stride == 1: an invalid
-// element gets the key SORT_INVALID, which sorts last, and n is its lower bound in the sorted keys.
-//  * N <= SORT_STRIDED_MAX: a workgroup loads G consecutive cells row by row (adjacent lanes, adjacent cells) into LDS rows of
-//    pitch P + 1 and sorts the G rows with the bitonic network; G is twice distribution.hip's, whose network sorts two sides.
-//  * longer: a 64 x 64 transposing gather writes the keys contiguous per cell into the workspace, the key-only radix sort sorts
-//    them; cells go through in chunks sized by the workspace budget.
-// Then 64 (or G) cells' Q values are written by threads that run along the cells.  No floating-point atomics, no sum whose order
-// could vary: a repeated call gives the same bits.
+// in all Q entries; valid[c] = n.  The cells' ascending keys come from the per-cell engine of cell_sort.h (stride per, no
+// negation); 64 (or G) cells' Q values are then written by threads that run along the cells.  No floating-point atomics, no sum
+// whose order could vary: a repeated call gives the same bits.
 //
 // Map (qmap_apply), m the model's historical table, o the observed one, f the table of the period being corrected (QDM only); the
 // search table s is m for EQM and f for QDM.  Every operation is on fp32 and rounded on its own (no fused multiply-add, division
@@ -35,7 +30,7 @@
 #include "common.h"
 #include "ops.h"
 #include "prof.h"
-#include "sort_keys.h"
+#include "cell_sort.h"
 #include <algorithm>
 #include <cmath>
 
@@ -45,7 +40,6 @@
 namespace {
 
 constexpr int QM_MAX_Q = 256;                          // (the C header states it)
-constexpr int QM_TR = 64;                              // gather and table kernels: 64 cells x 64 samples per transposed tile
 constexpr int QM_CELLS = 64;                           // map: cells per workgroup, one per lane
 constexpr int QM_THREADS = 256;                        // map: 4 waves, each on its own samples
 constexpr int QM_WAVES = QM_THREADS / 64;
@@ -71,88 +65,38 @@ __device__ __forceinline__ void write_tables(const QuantParams& prm, Row row, co
     }
 }
 
-__device__ __forceinline__ uint32_t table_key(float v) { return finite_bits(v) ? rank_key(v) : SORT_INVALID; }
-
-template <int P>
-constexpr int tab_group() { return 2 * (4096 / P > 16 ? 4096 / P : 16); }
-template <int P>
-constexpr size_t tab_lds_bytes() { return (size_t)tab_group<P>() * (P + 1) * 4; }
-
 // strided LDS engine: G cells of N <= P samples per workgroup
 template <int P>
-__global__ void __launch_bounds__(512) qtab_lds_kernel(const float* __restrict__ x, size_t N, size_t per, const QuantParams prm,
-                                                      float* __restrict__ table, long long* __restrict__ valid) {
-    constexpr int T = 512, G = tab_group<P>(), PITCH = P + 1;
+__global__ void __launch_bounds__(CELL_THREADS) qtab_lds_kernel(const float* __restrict__ x, size_t N, size_t per, const QuantParams prm,
+                                                               float* __restrict__ table, long long* __restrict__ valid) {
+    constexpr int T = CELL_THREADS, G = cell_group<P>(), PITCH = P + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char qtab_lds[];
     uint32_t* key = reinterpret_cast<uint32_t*>(qtab_lds);                // [G][PITCH]
     __shared__ uint32_t nn[G];
     const int t = threadIdx.x;
     const size_t c0 = (size_t)blockIdx.x * G;
     const int cells = (int)(per - c0 < (size_t)G ? per - c0 : (size_t)G);
-    for (int i = t; i < G * P; i += T) {                                  // sample k of the G cells: adjacent lanes, adjacent floats
-        const int k = i / G, g = i % G;
-        key[g * PITCH + k] = ((size_t)k < N && g < cells) ? table_key(x[(size_t)k * per + c0 + g]) : SORT_INVALID;
-    }
-    __syncthreads();
-    bitonic_rows<P, G, PITCH, T, false>(key, nullptr);
+    sorted_cell_rows<P>(x, N, per, false, c0, cells, key);
     if (t < G) nn[t] = bound<true>(key + t * PITCH, (uint32_t)P, SORT_INVALID);
     __syncthreads();
     if (valid && t < cells) valid[c0 + t] = (long long)nn[t];
     write_tables(prm, [&](int g) { return (const uint32_t*)(key + g * PITCH); }, nn, cells, c0, per, t, T, table);
 }
 
-// global engine, step 1: the keys of a chunk of `ncell` cells (the first at x), contiguous per cell: a tile of 64 cells x 64
-// samples is read with lanes along the cells and written with lanes along the samples.  blockIdx.x = cell block * etiles + sample block
-__global__ void __launch_bounds__(SORT_THREADS) qtab_gather_kernel(const float* __restrict__ x, size_t ncell, size_t N, size_t per,
-                                                                 unsigned etiles, uint32_t* __restrict__ k) {
-    __shared__ uint32_t tk[QM_TR][QM_TR + 1];
-    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-    const size_t c0 = (size_t)(blockIdx.x / etiles) * QM_TR, p0 = (size_t)(blockIdx.x % etiles) * QM_TR;
-    for (int e = ty; e < QM_TR; e += SORT_WAVES) {
-        const size_t cell = c0 + tx, pos = p0 + e;
-        tk[e][tx] = (cell < ncell && pos < N) ? table_key(x[pos * per + cell]) : SORT_INVALID;
-    }
-    __syncthreads();
-    for (int g = ty; g < QM_TR; g += SORT_WAVES) {
-        const size_t cell = c0 + g, pos = p0 + tx;
-        if (cell < ncell && pos < N) k[cell * N + pos] = tk[tx][g];
-    }
-}
-
 // global engine, step 3: 64 cells of the chunk per workgroup, from their sorted keys
 __global__ void __launch_bounds__(SORT_THREADS) qtab_finish_kernel(const uint32_t* __restrict__ k, size_t ncell, size_t N, size_t per,
                                                                  size_t cell0, const QuantParams prm, float* __restrict__ table,
                                                                  long long* __restrict__ valid) {
-    __shared__ uint32_t nn[QM_TR];
+    __shared__ uint32_t nn[CELL_TR];
     const int t = threadIdx.x;
-    const size_t c0 = (size_t)blockIdx.x * QM_TR;
-    const int cells = (int)(ncell - c0 < (size_t)QM_TR ? ncell - c0 : (size_t)QM_TR);
+    const size_t c0 = (size_t)blockIdx.x * CELL_TR;
+    const int cells = (int)(ncell - c0 < (size_t)CELL_TR ? ncell - c0 : (size_t)CELL_TR);
     if (t < cells) {
         nn[t] = bound<true>(k + (c0 + t) * N, (uint32_t)N, SORT_INVALID);
         if (valid) valid[cell0 + c0 + t] = (long long)nn[t];
     }
     __syncthreads();
     write_tables(prm, [&](int g) { return k + (c0 + g) * N; }, nn, cells, cell0 + c0, per, t, SORT_THREADS, table);
-}
-
-// workspace of `segs` cells: their keys, the sort's second buffer, the digit counts per tile
-struct Workspace {
-    uint32_t *k, *tmp, *hist;
-    Workspace(Carver& w, size_t segs, size_t ntiles, size_t L)
-        : k(w.take<uint32_t>(segs * L)), tmp(w.take<uint32_t>(segs * L)), hist(w.take<uint32_t>(segs * ntiles * SORT_RADIX)) {}
-};
-
-template <int P>
-void launch_tab_lds(hipStream_t s, const float* x, size_t N, size_t per, const QuantParams& prm, float* table, long long* valid) {
-    auto kern = qtab_lds_kernel<P>;
-    static bool once = false;
-    if (!once) {
-        HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)tab_lds_bytes<P>()));
-        once = true;
-    }
-    DL4DS_LAUNCH(kern, dim3((unsigned)cdivz(per, tab_group<P>())), dim3(512), tab_lds_bytes<P>(), s, x, N, per, prm, table, valid);
-    HIP_CHECK(hipGetLastError());
 }
 
 // --------------------------------------------------------------------------------------------------------------------- the map
@@ -301,8 +245,7 @@ size_t quantile_table_workspace_bytes(size_t N, size_t per) {
     DL4DS_REQUIRE(N > 0 && per > 0, "quantile_table: empty array");
     DL4DS_REQUIRE(N < (size_t(1) << 31), "quantile_table: 2^31 or more samples are not supported");
     DL4DS_REQUIRE(per < (size_t(1) << 36), "quantile_table: too many cells");
-    if (N <= (size_t)SORT_STRIDED_MAX) return 0;
-    return plan_chunks<Workspace>(per, N).bytes();
+    return cell_sort_workspace_bytes(N, per);
 }
 
 void quantile_table(hipStream_t s, const float* x, size_t N, size_t per, const double* q, int Q, float* table, long long* valid,
@@ -310,29 +253,14 @@ void quantile_table(hipStream_t s, const float* x, size_t N, size_t per, const d
     const QuantParams prm = checked_probabilities(q, Q);
     const size_t need = quantile_table_workspace_bytes(N, per);           // (refuses an empty or oversized array)
     DL4DS_REQUIRE(x && table, "quantile_table: null array or table");
-    const bool lds = N <= (size_t)SORT_STRIDED_MAX;
-    ProfScope ps(s, lds ? "quantile_table_strided" : "quantile_table_global", 0.0, 4.0 * (double)N * (double)per);
-    if (lds) {
-        if (N <= 64) return launch_tab_lds<64>(s, x, N, per, prm, table, valid);
-        if (N <= 128) return launch_tab_lds<128>(s, x, N, per, prm, table, valid);
-        if (N <= 256) return launch_tab_lds<256>(s, x, N, per, prm, table, valid);
-        return launch_tab_lds<SORT_STRIDED_MAX>(s, x, N, per, prm, table, valid);
-    }
-    DL4DS_REQUIRE(workspace_bytes >= need, "quantile_table workspace too small");
-    const Chunk c = plan_chunks<Workspace>(per, N);
-    Carver carver{static_cast<char*>(workspace)};
-    const Workspace w(carver, c.segs, c.ntiles, N);
-    const unsigned nt = (unsigned)c.ntiles, etiles = (unsigned)cdivz(N, QM_TR);
-    for (size_t c0 = 0; c0 < per; c0 += c.segs) {
-        const size_t nc = std::min(c.segs, per - c0);
-        const size_t cblocks = cdivz(nc, QM_TR);
-        DL4DS_REQUIRE(cblocks * etiles < (size_t(1) << 31), "quantile_table: too many tiles for one launch");
-        DL4DS_LAUNCH(qtab_gather_kernel, dim3((unsigned)(cblocks * etiles)), dim3(SORT_THREADS), 0, s, x + c0, nc, N, per, etiles, w.k);
-        segmented_sort<false>(s, KeyBuffer{w.k}, w.k, nullptr, w.tmp, nullptr, nc, N, nt, w.hist);
-        DL4DS_LAUNCH(qtab_finish_kernel, dim3((unsigned)cblocks), dim3(SORT_THREADS), 0, s, (const uint32_t*)w.k, nc, N, per, c0, prm,
-                     table, valid);
-    }
-    HIP_CHECK(hipGetLastError());
+    if (need) DL4DS_REQUIRE(workspace_bytes >= need, "quantile_table workspace too small");
+    cell_sort(
+        s, "quantile_table", x, N, per, per, 0, workspace,
+        [&](auto P) { launch_cell_lds<P(), qtab_lds_kernel<P()>>(s, per, x, N, per, prm, table, valid); },
+        [&](const uint32_t* keys, size_t nc, size_t c0) {
+            DL4DS_LAUNCH(qtab_finish_kernel, dim3((unsigned)cdivz(nc, CELL_TR)), dim3(SORT_THREADS), 0, s, keys, nc, N, per, c0, prm, table,
+                         valid);
+        });
 }
 
 void qmap_apply(hipStream_t s, const float* x, float* out, size_t B, size_t per, const float* model_tab, const float* obs_tab,

@@ -38,6 +38,7 @@
 // order of the fp64 sums: parallelism is cells x periods.
 #include "common.h"
 #include "ops.h"
+#include "periods.h"
 #include "prof.h"
 
 namespace {
@@ -61,8 +62,6 @@ struct TmpArgs {
     int* spell;
 };
 
-__device__ __forceinline__ bool tmp_finite(float v) { return __builtin_fabsf(v) < __builtin_inff(); }       // false for NaN
-
 template <int S, int T, int L>
 __global__ void __launch_bounds__(TMP_CELLS) temporal_kernel(const TmpArgs a) {
     constexpr int T1 = T ? T : 1, L1 = L ? L : 1;
@@ -74,7 +73,7 @@ __global__ void __launch_bounds__(TMP_CELLS) temporal_kernel(const TmpArgs a) {
     const size_t cc = live ? c : per - 1;                                 // an idle lane walks the last cell and stores nothing
     const size_t s0 = (size_t)a.starts[p], s1 = (size_t)a.starts[p + 1];
     const int len = (int)(s1 - s0), B = a.bins;
-    const bool neg = a.op >= 2, strict = a.op == 1 || a.op == 2;          // x < t is -x > -t, x <= t is -x >= -t (exact)
+    const auto [neg, strict] = decode_op(a.op);
 
     int lags[L1];
 #pragma unroll
@@ -84,7 +83,7 @@ __global__ void __launch_bounds__(TMP_CELLS) temporal_kernel(const TmpArgs a) {
 #pragma unroll
     for (int t = 0; t < T; ++t) {
         const float v = a.thr_per_cell ? a.thr[(size_t)t * per + cc] : a.thr[t];
-        thr_ok[t] = tmp_finite(v);
+        thr_ok[t] = finite_f32(v);
         thr[t] = neg ? -v : v;
     }
     int n_valid = 0, n_pair[L1];
@@ -142,7 +141,7 @@ __global__ void __launch_bounds__(TMP_CELLS) temporal_kernel(const TmpArgs a) {
             float v[S];
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                ok = ok && tmp_finite(blk[s][u]);
+                ok = ok && finite_f32(blk[s][u]);
                 v[s] = blk[s][u] == 0.f ? 0.f : blk[s][u];                // -0.0 counts as +0.0
             }
             n_valid += ok ? 1 : 0;
@@ -272,7 +271,7 @@ void tmp_launch_s(hipStream_t s, const TmpArgs& a, unsigned blocks, int T, int L
     }
 }
 
-size_t tmp_lags_offset(int P) { return (((size_t)P + 1) * sizeof(long long) + 15) & ~size_t(15); }
+size_t tmp_lags_offset(int P) { return (period_starts_bytes(P) + 15) & ~size_t(15); }
 
 }  // namespace
 
@@ -285,15 +284,12 @@ size_t temporal_workspace_bytes(size_t N, size_t per, const long long* period_st
     DL4DS_REQUIRE(T >= 0 && T <= TMP_MAX_THRESHOLDS, "temporal: 0 <= T <= 4 thresholds");
     DL4DS_REQUIRE(spell_bins >= 1 && spell_bins <= TMP_MAX_BINS, "temporal: 1 <= spell_bins <= 32");
     DL4DS_REQUIRE(op >= 0 && op <= 3, "temporal: op must be 0 (>=), 1 (>), 2 (<) or 3 (<=)");
-    DL4DS_REQUIRE(period_starts, "temporal: null period starts");
+    DL4DS_REQUIRE(period_starts, "temporal: null period starts");       // (before the lags, as it has always been)
     DL4DS_REQUIRE(L == 0 || lags, "temporal: null lags");
     for (int l = 0; l < L; ++l)
         DL4DS_REQUIRE(lags[l] >= 1 && lags[l] <= TMP_RING && (l == 0 || lags[l] > lags[l - 1]),
                       "temporal: lags must be strictly increasing, each in 1..32");
-    DL4DS_REQUIRE((size_t)P <= N && period_starts[0] == 0 && period_starts[P] == (long long)N,
-                  "temporal: period starts must be strictly increasing from 0 to N");
-    for (int p = 0; p < P; ++p)
-        DL4DS_REQUIRE(period_starts[p + 1] > period_starts[p], "temporal: period starts must be strictly increasing from 0 to N");
+    check_period_starts("temporal", period_starts, P, N);
     DL4DS_REQUIRE(cdivz(per, TMP_CELLS) * (size_t)P < (size_t(1) << 31), "temporal: too many cells x periods for one launch");
     return tmp_lags_offset(P) + TMP_MAX_LAGS * sizeof(int);
 }
@@ -308,13 +304,11 @@ void temporal(hipStream_t s, const float* y, const float* p, size_t N, size_t pe
     DL4DS_REQUIRE(T > 0 || (!trans && !spell), "temporal: transition and spell outputs need at least one threshold");
     DL4DS_REQUIRE(valid || moment || pair || lag || trans || spell, "temporal: all six outputs are null");
     DL4DS_REQUIRE(workspace && workspace_bytes >= need, "temporal workspace too small");
-    long long* starts = static_cast<long long*>(workspace);
     int* dlags = reinterpret_cast<int*>(static_cast<char*>(workspace) + tmp_lags_offset(P));
     int hl[TMP_MAX_LAGS] = {1, 1, 1, 1};
     for (int l = 0; l < L; ++l) hl[l] = lags[l];
-    HIP_CHECK(hipMemcpyAsync(starts, period_starts, ((size_t)P + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(dlags, hl, sizeof(hl), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamSynchronize(s));                                   // the caller's arrays (and hl) may go away after the call
+    const long long* starts = upload_period_starts(s, period_starts, P, workspace);      // (waits for the lags too: hl may go away)
     const int S = p ? 2 : 1;
     const TmpArgs a{{y, p}, per, starts, dlags, (unsigned)P, thr, thr_per_cell, op, spell_bins, valid, moment, pair, lag, trans, spell};
     const unsigned blocks = (unsigned)(cdivz(per, TMP_CELLS) * (size_t)P);

@@ -13,8 +13,8 @@ import math
 
 import numpy as np
 
-from ._chunks import check_batch_size, is_int, paired_chunks
-from .indices import _as_4d, _is_device, check_index_args, climate_indices
+from ._chunks import as_4d as _as_4d, cell_bands, check_4d_shape, check_batch_size, is_int, masked as _masked, numeric_array
+from .indices import check_index_args, climate_indices
 
 __all__ = ['l_moments', 'block_maxima', 'peaks_over_threshold', 'lmoments_from_pwm', 'gev_from_lmoments', 'gumbel_from_lmoments',
            'gpd_from_lmoments', 'return_levels', 'fit_gev', 'fit_gumbel', 'fit_gpd', 'extreme_scores', 'check_extreme_args',
@@ -31,9 +31,7 @@ _gamma = np.vectorize(math.gamma, otypes=[np.float64])
 def check_extreme_args(shape, tail='upper', run=1, return_periods=(5, 10, 20, 50), method='gev', threshold=None, batch_size=None):
     """Validation from the arguments alone (no library call).  ``shape``: the array's (N, H, W, C).
     -> (sign +1 / -1, threshold float32 (1,) or (H, W, C) or None, return periods float64 (R,))."""
-    shape = tuple(int(v) for v in shape)
-    if len(shape) != 4 or min(shape) < 1:
-        raise ValueError(f'expected a non-empty (N, H, W, C) array, got shape {shape}')
+    shape = check_4d_shape(shape)
     if tail not in EXTREME_TAILS:
         raise ValueError(f'`tail` must be one of {EXTREME_TAILS}, got {tail!r}')
     if not is_int(run) or not 1 <= run <= EXTREME_MAX_RUN:
@@ -51,9 +49,7 @@ def check_extreme_args(shape, tail='upper', run=1, return_periods=(5, 10, 20, 50
         raise ValueError("method='pot' needs a `threshold`")
     thr = None
     if threshold is not None:
-        thr = np.asarray(getattr(threshold, 'values', threshold))
-        if thr.dtype == object or not (np.issubdtype(thr.dtype, np.floating) or np.issubdtype(thr.dtype, np.integer)):
-            raise ValueError('`threshold` must be a number or a field of numbers')
+        thr = numeric_array(threshold, '`threshold` must be a number or a field of numbers')
         if thr.ndim == 4 and thr.shape[0] == 1:                                          # what percentile_threshold returns
             thr = thr[0]
         if thr.ndim == 2 and shape[3] == 1:
@@ -66,15 +62,6 @@ def check_extreme_args(shape, tail='upper', run=1, return_periods=(5, 10, 20, 50
     return (1 if tail == 'upper' else -1), thr, periods
 
 
-def _masked(x, mask):
-    if mask is None:
-        return x
-    if _is_device(x):
-        raise ValueError('`mask` needs a host array: mark the excluded cells of a DeviceArray with NaN')
-    from .metrics import _masked_observation
-    return _masked_observation(x, mask)
-
-
 # ------------------------------------------------------------------------------------------------------------ device-backed
 def l_moments(x, tail='upper', mask=None, batch_size=None):
     """Sample L-moments per grid cell over the samples of ``x`` (N, H, W, C), from the sorted probability-weighted moments of
@@ -84,7 +71,6 @@ def l_moments(x, tail='upper', mask=None, batch_size=None):
     -> dict of ``n_valid`` int32 (H, W, C); ``pwm`` float64 (4, H, W, C) (b_r is NaN where n_valid <= r); ``l1``, ``l2``, ``t3``,
     ``t4`` float64 (H, W, C) as `lmoments_from_pwm` gives them."""
     from . import _lib
-    from .device import Buffers
     x, shape = _as_4d(x)
     sign, _, _ = check_extreme_args(shape, tail, batch_size=batch_size)
     x = _masked(x, mask)
@@ -92,27 +78,8 @@ def l_moments(x, tail='upper', mask=None, batch_size=None):
     N, H, W, C = shape
     per = H * W * C
     valid, pwm = np.empty((per,), np.int32), np.empty((4, per), np.float64)
-    if _is_device(x):
-        with Buffers() as buf:
-            dv, dp = buf.alloc(valid.shape, np.int32), buf.alloc(pwm.shape, np.float64)
-            _lib.check(lib.dl4ds_lmoments(x.ptr, N, per, per, sign, dv.ptr, dp.ptr))
-            dv.download(valid)
-            dp.download(pwm)
-    else:
-        row = W * C
-        done = [0]                                                      # chunks run in ascending order
-
-        def call(b, dx, _):
-            cells, c0 = b * row, done[0] * row
-            with Buffers() as buf:
-                dv, dp = buf.alloc((cells,), np.int32), buf.alloc((4, cells), np.float64)
-                _lib.check(lib.dl4ds_lmoments(dx, N, cells, cells, sign, dv.ptr, dp.ptr))
-                part = np.empty((4, cells), np.float64)
-                dp.download(part)
-                pwm[:, c0:c0 + cells] = part
-                dv.download(valid[c0:c0 + cells])
-            done[0] += b
-        paired_chunks(x, None, (), call, batch_size, axis=1)
+    cell_bands(x, None, shape, (valid, pwm),
+               lambda band: _lib.check(lib.dl4ds_lmoments(band.x, N, band.cells, band.cells, sign, *band.outs)), batch_size)
     out = {'n_valid': valid.reshape(H, W, C), 'pwm': pwm.reshape(4, H, W, C)}
     out.update(lmoments_from_pwm(out['pwm']))
     return out
@@ -140,7 +107,6 @@ def peaks_over_threshold(x, threshold, run=1, tail='upper', periods=None, period
     -> dict of ``n_peaks`` int32 (H, W, C) (-1 without a threshold); ``peaks`` float32 (K, H, W, C) in order of occurrence, NaN
     beyond a cell's count; ``positions`` int32 (K, H, W, C), their sample indices, -1 beyond the count; ``period_starts``."""
     from . import _lib
-    from .device import Buffers
     x, shape = _as_4d(x)
     sign, thr, _ = check_extreme_args(shape, tail, run, method='pot', threshold=threshold, batch_size=batch_size)
     starts, _, _ = check_index_args(shape, periods, (0.0,), '>=', 1, batch_size, period_starts)
@@ -148,39 +114,25 @@ def peaks_over_threshold(x, threshold, run=1, tail='upper', periods=None, period
     lib = _lib.lib()
     N, H, W, C = shape
     per, P, cell = H * W * C, len(starts) - 1, thr.ndim == 3
-    thr = thr.reshape(-1)
     count = np.empty((per,), np.int32)
     parts = []                                                          # (first cell, peaks (k, cells), positions (k, cells))
 
-    def band(dx, cells, c0, buf):
-        dthr, dc = buf.alloc((cells if cell else 1,)), buf.alloc((cells,), np.int32)
-        dthr.upload(np.ascontiguousarray(thr[c0:c0 + cells] if cell else thr))
-        args = (dx, N, cells, starts.ctypes.data, P, dthr.ptr, int(cell), sign, int(run))
+    def call(band):
+        cells, c0 = band.cells, band.c0
+        dc = band.buf.alloc((cells,), np.int32)
+        args = (band.x, N, cells, starts.ctypes.data, P, band.fields[0], int(cell), sign, int(run))
         _lib.check(lib.dl4ds_pot_peaks(*args, 0, dc.ptr, None, None))
-        n = np.empty((cells,), np.int32)
+        n = count[c0:c0 + cells]
         dc.download(n)
-        count[c0:c0 + cells] = n
         k = max(int(n.max()), 0)
         pk, ps = np.empty((k, cells), np.float32), np.empty((k, cells), np.int32)
         if k:
-            dpk, dps = buf.alloc(pk.shape), buf.alloc(ps.shape, np.int32)
+            dpk, dps = band.buf.alloc(pk.shape), band.buf.alloc(ps.shape, np.int32)
             _lib.check(lib.dl4ds_pot_peaks(*args, k, dc.ptr, dpk.ptr, dps.ptr))
             dpk.download(pk)
             dps.download(ps)
         parts.append((c0, pk, ps))
-
-    if _is_device(x):
-        with Buffers() as buf:
-            band(x.ptr, per, 0, buf)
-    else:
-        row = W * C
-        done = [0]
-
-        def call(b, dx, _):
-            with Buffers() as buf:
-                band(dx, b * row, done[0] * row, buf)
-            done[0] += b
-        paired_chunks(x, None, (), call, batch_size, axis=1)
+    cell_bands(x, None, shape, (), call, batch_size, fields=(thr,))
     K = max(pk.shape[0] for _, pk, _ in parts)
     peaks, pos = np.full((K, per), np.nan, np.float32), np.full((K, per), -1, np.int32)
     for c0, pk, ps in parts:

@@ -9,7 +9,7 @@ definitions are those of ``dl4ds_climate_indices`` in include/dl4ds_hip.h.  nump
 """
 import numpy as np
 
-from ._chunks import check_batch_size, is_int, paired_chunks, upload_batch
+from ._chunks import as_4d as _as_4d, cell_bands, check_4d_shape, check_batch_size, is_device as _is_device, is_int, masked, numeric_array
 
 __all__ = ['climate_indices', 'precipitation_indices', 'temperature_indices', 'percentile_threshold', 'index_scores',
            'check_index_args', 'period_starts_from_labels', 'INDEX_OPS', 'INDEX_MAX_THRESHOLDS', 'INDEX_MAX_WINDOW']
@@ -34,9 +34,7 @@ def period_starts_from_labels(labels):
 def check_index_args(shape, periods=None, thresholds=(1.0,), op='>=', window=5, batch_size=None, period_starts=None):
     """Validation of `climate_indices` from the arguments alone (no library call).  ``shape``: the array's (N, H, W, C).
     -> (period starts int64 (P + 1,), thresholds float32 (T,) or (T, H, W, C), the number of ``op``)."""
-    shape = tuple(int(v) for v in shape)
-    if len(shape) != 4 or min(shape) < 1:
-        raise ValueError(f'expected a non-empty (N, H, W, C) array, got shape {shape}')
+    shape = check_4d_shape(shape)
     N = shape[0]
     if N >= INDEX_LENGTH_BOUND:
         raise ValueError(f'the array has {N} samples: the number must stay below 2^31')
@@ -60,9 +58,7 @@ def check_index_args(shape, periods=None, thresholds=(1.0,), op='>=', window=5, 
             raise ValueError(f'`periods` has {starts[-1]} labels for {N} samples')
     else:
         starts = np.array([0, N], np.int64)
-    thr = np.asarray(getattr(thresholds, 'values', thresholds))
-    if thr.dtype == object or not (np.issubdtype(thr.dtype, np.floating) or np.issubdtype(thr.dtype, np.integer)):
-        raise ValueError('`thresholds` must be numbers')
+    thr = numeric_array(thresholds, '`thresholds` must be numbers')
     if thr.ndim == 0:
         thr = thr.reshape(1)
     if thr.ndim == 3 and shape[3] == 1:
@@ -72,23 +68,6 @@ def check_index_args(shape, periods=None, thresholds=(1.0,), op='>=', window=5, 
     if not 1 <= thr.shape[0] <= INDEX_MAX_THRESHOLDS:
         raise ValueError(f'between 1 and {INDEX_MAX_THRESHOLDS} thresholds are supported, got {thr.shape[0]}')
     return np.ascontiguousarray(starts), np.ascontiguousarray(thr, np.float32), INDEX_OPS.index(op)
-
-
-def _is_device(a):
-    from .device import DeviceArray
-    return isinstance(a, DeviceArray)
-
-
-def _as_4d(a, name='x'):
-    """-> (the array, its shape as (N, H, W, C)): an ndarray of any dtype (3-D input gets a channel axis) or a float32 DeviceArray,
-    which is left as it is (a 3-D one is read as (N, H, W, 1))."""
-    if _is_device(a):
-        if a.dtype != np.float32:
-            raise TypeError(f'`{name}`: a DeviceArray must hold float32, got {a.dtype}')
-        return a, tuple(a.shape) + ((1,) if len(a.shape) == 3 else ())
-    from .dataloader import checkarray_ndim
-    a = checkarray_ndim(np.asarray(getattr(a, 'values', a)), 4, -1)
-    return a, a.shape
 
 
 def _named(valid, event, ext, sums, starts, grid):
@@ -122,52 +101,19 @@ def climate_indices(x, periods=None, thresholds=(1.0,), op='>=', window=5, mask=
     largest sum of ``window`` consecutive valid samples; NaN without one) float64; ``event_sum`` float64 (P, T, H, W, C);
     ``period_starts`` int64 (P + 1,)."""
     from . import _lib
-    from .device import Buffers
     x, shape = _as_4d(x)
     starts, thr, opn = check_index_args(shape, periods, thresholds, op, window, batch_size, period_starts)
-    if mask is not None:
-        if _is_device(x):
-            raise ValueError('`mask` needs a host array: mark the excluded cells of a DeviceArray with NaN')
-        from .metrics import _masked_observation
-        x = _masked_observation(x, mask)
+    x = masked(x, mask)
     lib = _lib.lib()
     N, H, W, C = shape
     per, P, T, cell = H * W * C, len(starts) - 1, thr.shape[0], thr.ndim == 4
     valid, event = np.empty((P, per), np.int32), np.empty((P, T, 6, per), np.int32)
     ext, sums = np.empty((P, 2, per), np.float32), np.empty((P, 2 + T, per), np.float64)
-    hosts = (valid, event, ext, sums)
 
-    def run(dx, cells, dthr, devs):
-        _lib.check(lib.dl4ds_climate_indices(dx, N, cells, starts.ctypes.data, P, dthr, T, int(cell), opn, int(window),
-                                             *(d.ptr for d in devs)))
-    with Buffers() as buf:
-        if _is_device(x):
-            devs = [buf.alloc(h.shape, h.dtype) for h in hosts]
-            dthr = buf.alloc(thr.shape)
-            dthr.upload(thr)
-            run(x.ptr, per, dthr.ptr, devs)
-            for h, d in zip(hosts, devs):
-                d.download(h)
-        else:
-            row = W * C                                                 # cells per unit of axis 1
-            bmax = upload_batch(batch_size, N * row, H)
-            devs = [buf.alloc(h.shape[:-1] + (bmax * row,), h.dtype) for h in hosts]
-            dthr = buf.alloc((T, bmax * row) if cell else (T,))
-            if not cell:
-                dthr.upload(thr)
-            done = [0]                                                  # chunks run in ascending order
-
-            def call(b, dx, _):
-                cells, c0 = b * row, done[0] * row
-                if cell:
-                    dthr.upload(np.ascontiguousarray(thr[:, done[0]:done[0] + b]).reshape(T, cells))
-                run(dx, cells, dthr.ptr, devs)
-                for h, d in zip(hosts, devs):                           # [...][cells of the band] -> its columns of [...][per]
-                    part = np.empty(h.shape[:-1] + (cells,), h.dtype)
-                    d.download(part)
-                    h[..., c0:c0 + cells] = part
-                done[0] += b
-            paired_chunks(x, None, (), call, batch_size, axis=1)
+    def call(band):
+        _lib.check(lib.dl4ds_climate_indices(band.x, N, band.cells, starts.ctypes.data, P, band.fields[0], T, int(cell), opn,
+                                             int(window), *band.outs))
+    cell_bands(x, None, shape, (valid, event, ext, sums), call, batch_size, fields=(thr,))
     return _named(valid, event, ext, sums, starts, (H, W, C))
 
 

@@ -10,7 +10,7 @@ one streaming pass.  Empirical quantile mapping (``method='eqm'``) and its trend
 """
 import numpy as np
 
-from ._chunks import check_batch_size, paired_chunks, upload_batch
+from ._chunks import as_4d as _as_4d, cell_bands, check_4d_shape, check_batch_size, is_device as _is_device, masked, paired_chunks
 from .preprocessing import NotFittedError
 
 __all__ = ['QuantileMapper', 'quantile_map', 'check_qmap_args', 'QMAP_MIN_QUANTILES', 'QMAP_MAX_QUANTILES']
@@ -24,9 +24,7 @@ COUNT_NAMES = ('n_nonfinite', 'n_unfitted', 'n_below', 'n_above')
 def _check_shape(name, shape):
     if shape is None:
         return None
-    shape = tuple(int(v) for v in shape)
-    if len(shape) != 4 or min(shape) < 1:
-        raise ValueError(f'expected a non-empty (N, H, W, C) array for `{name}`, got shape {shape}')
+    shape = check_4d_shape(shape, name)
     if shape[0] >= QMAP_LENGTH_BOUND:
         raise ValueError(f'`{name}` has {shape[0]} samples: the number must stay below 2^31')
     return shape
@@ -70,51 +68,16 @@ def check_qmap_args(n_quantiles=101, quantiles=None, method='eqm', kind='+', bat
     return np.ascontiguousarray(q)
 
 
-def _is_device(a):
-    from .device import DeviceArray
-    return isinstance(a, DeviceArray)
-
-
-def _as_4d(a, name):
-    """-> (the array, its shape as (N, H, W, C)): an ndarray of any dtype (3-D input gets a channel axis) or a float32 DeviceArray,
-    which is left as it is (a 3-D one is read as (N, H, W, 1))."""
-    if _is_device(a):
-        if a.dtype != np.float32:
-            raise TypeError(f'`{name}`: a DeviceArray must hold float32, got {a.dtype}')
-        return a, tuple(a.shape) + ((1,) if len(a.shape) == 3 else ())
-    from .dataloader import checkarray_ndim
-    a = checkarray_ndim(np.asarray(getattr(a, 'values', a)), 4, -1)
-    return a, a.shape
-
-
 def _device_table(x, shape, q, batch_size=None):
     """(table float32 (Q, H, W, C), valid int64 (H, W, C)) of the array ``x`` of ``shape`` (N, H, W, C): a DeviceArray in one call,
     a host array in bands of grid rows."""
     from . import _lib
-    from .device import Buffers
     lib = _lib.lib()
     N, H, W, C = shape
     Q = len(q)
     table, valid = np.empty((Q, H * W * C), np.float32), np.empty((H * W * C,), np.int64)
-    with Buffers() as buf:
-        if _is_device(x):
-            dt, dv = buf.alloc(table.shape), buf.alloc(valid.shape, np.int64)
-            _lib.check(lib.dl4ds_quantile_table(x.ptr, N, H * W * C, q.ctypes.data, Q, dt.ptr, dv.ptr))
-            dt.download(table)
-            dv.download(valid)
-        else:
-            row = W * C                                                 # cells per unit of axis 1
-            bmax = upload_batch(batch_size, N * row, H)
-            dt = buf.alloc((Q * bmax * row,))
-            done = [0]                                                  # chunks run in ascending order
-
-            def call(b, dx, _, dvalid):
-                _lib.check(lib.dl4ds_quantile_table(dx, N, b * row, q.ctypes.data, Q, dt.ptr, dvalid))
-                part = np.empty((Q, b * row), np.float32)               # [Q][cells of the band] -> its columns of [Q][per]
-                dt.download(part)
-                table[:, done[0]:done[0] + b * row] = part
-                done[0] += b * row
-            paired_chunks(x, None, (valid,), call, batch_size, axis=1)
+    cell_bands(x, None, shape, (table, valid),
+               lambda band: _lib.check(lib.dl4ds_quantile_table(band.x, N, band.cells, q.ctypes.data, Q, *band.outs)), batch_size)
     return table.reshape(Q, H, W, C), valid.reshape(H, W, C)
 
 
@@ -162,13 +125,9 @@ class QuantileMapper:
         return self
 
     def fit(self, obs, model, mask=None):
-        from .metrics import _masked_observation
         (obs, obs_shape), (model, model_shape) = _as_4d(obs, 'obs'), _as_4d(model, 'model')
         q = self._check(obs_shape=obs_shape, model_shape=model_shape)
-        if mask is not None:
-            if _is_device(obs):
-                raise ValueError('`mask` needs a host observation: mark the excluded cells of a DeviceArray with NaN')
-            obs = _masked_observation(obs, mask)                        # (a copy; without a mask the bands are cut from the caller's array)
+        obs = masked(obs, mask, 'observation')                          # (a copy; without a mask the bands are cut from the caller's array)
         self.obs_quantiles_, self.n_obs_ = _device_table(obs, obs_shape, q, self.batch_size)
         self.model_quantiles_, self.n_model_ = _device_table(model, model_shape, q, self.batch_size)
         self.quantiles_ = q

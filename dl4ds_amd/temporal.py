@@ -13,8 +13,8 @@ import math
 
 import numpy as np
 
-from ._chunks import check_batch_size, is_int, paired_chunks, upload_batch
-from .indices import _as_4d, _is_device, check_index_args
+from ._chunks import as_4d as _as_4d, cell_bands, check_batch_size, is_device as _is_device, is_int, masked
+from .indices import check_index_args
 
 __all__ = ['temporal_statistics', 'temporal_scores', 'temporal_from_sums', 'mann_kendall', 'trend_scores', 'check_temporal_args',
            'TEMPORAL_MAX_LAGS', 'TEMPORAL_MAX_LAG', 'TEMPORAL_MAX_THRESHOLDS', 'TEMPORAL_MAX_BINS', 'TREND_MAX_PERIODS']
@@ -105,48 +105,16 @@ def _named(flat, s, starts, grid):
 def _device_temporal(y, p, shape, starts, lags, thr, opn, bins, batch_size):
     """One `dl4ds_temporal` call per band of grid rows (or one on DeviceArrays) -> the six flat host outputs [P][...][per]"""
     from . import _lib
-    from .device import Buffers
     lib = _lib.lib()
     N, H, W, C = shape
     per, P, S, L, T, cell = H * W * C, len(starts) - 1, 1 if p is None else 2, len(lags), thr.shape[0], thr.ndim == 4
     hosts = (np.empty((P, per), np.int32), np.empty((P, S, 2, per), np.float64), np.empty((P, L, per), np.int32),
              np.empty((P, S, L, 3, per), np.float64), np.empty((P, S, T, 4, per), np.int32), np.empty((P, S, T, 2, bins, per), np.int32))
 
-    def run(dy, dp, cells, dthr, devs):
-        _lib.check(lib.dl4ds_temporal(dy, dp, N, cells, starts.ctypes.data, P, lags.ctypes.data if L else None, L, dthr, T,
-                                      int(cell), opn, int(bins), *(d.ptr if d is not None else None for d in devs)))
-
-    def fetch(devs, cells, c0):
-        for h, d in zip(hosts, devs):                                   # [...][cells of the band] -> its columns of [...][per]
-            if d is not None:
-                part = np.empty(h.shape[:-1] + (cells,), h.dtype)
-                d.download(part)
-                h[..., c0:c0 + cells] = part
-    with Buffers() as buf:
-        if _is_device(y):
-            devs = [buf.alloc(h.shape, h.dtype) if h.size else None for h in hosts]
-            dthr = buf.alloc(thr.shape) if T else None
-            if T:
-                dthr.upload(thr)
-            run(y.ptr, p.ptr if p is not None else None, per, dthr.ptr if T else None, devs)
-            fetch(devs, per, 0)
-        else:
-            row = W * C                                                 # cells per unit of axis 1
-            bmax = upload_batch(batch_size, N * row, H)
-            devs = [buf.alloc(h.shape[:-1] + (bmax * row,), h.dtype) if h.size else None for h in hosts]
-            dthr = buf.alloc((T, bmax * row) if cell else (T,)) if T else None
-            if T and not cell:
-                dthr.upload(thr)
-            done = [0]                                                  # chunks run in ascending order
-
-            def call(b, dy, dp):
-                cells = b * row
-                if cell:
-                    dthr.upload(np.ascontiguousarray(thr[:, done[0]:done[0] + b]).reshape(T, cells))
-                run(dy, dp, cells, dthr.ptr if T else None, devs)
-                fetch(devs, cells, done[0] * row)
-                done[0] += b
-            paired_chunks(y, p, (), call, batch_size, axis=1)
+    def call(band):
+        _lib.check(lib.dl4ds_temporal(band.x, band.pred, N, band.cells, starts.ctypes.data, P, lags.ctypes.data if L else None, L,
+                                      band.fields[0], T, int(cell), opn, int(bins), *band.outs))
+    cell_bands(y, p, shape, [h if h.size else None for h in hosts], call, batch_size, fields=(thr,))
     return hosts
 
 
@@ -158,12 +126,7 @@ def _series(x, p, periods, lags, thresholds, op, spell_bins, mask, batch_size, p
         if pshape != shape or _is_device(p) != _is_device(x):
             raise ValueError(f'expected two arrays of one shape and kind, got {shape} and {pshape}')
     starts, lags, thr, opn = check_temporal_args(shape, periods, lags, thresholds, op, spell_bins, batch_size, period_starts)
-    if mask is not None:
-        if _is_device(x):
-            raise ValueError('`mask` needs a host array: mark the excluded cells of a DeviceArray with NaN')
-        from .metrics import _masked_observation
-        x = _masked_observation(x, mask)
-    return _device_temporal(x, p, shape, starts, lags, thr, opn, spell_bins, batch_size), starts, tuple(shape[1:])
+    return _device_temporal(masked(x, mask), p, shape, starts, lags, thr, opn, spell_bins, batch_size), starts, tuple(shape[1:])
 
 
 def temporal_statistics(x, periods=None, lags=(1,), thresholds=(), op='>=', spell_bins=16, mask=None, batch_size=None,
@@ -201,8 +164,7 @@ def _trend_values(values, mask=None):
     if _is_device(values):
         if values.dtype != np.float64:
             raise TypeError(f'`values`: a DeviceArray must hold float64, got {values.dtype}')
-        if mask is not None:
-            raise ValueError('`mask` needs a host array: mark the excluded cells of a DeviceArray with NaN')
+        masked(values, mask)                                                             # (refuses a mask)
         shape = tuple(values.shape) + ((1,) if len(values.shape) == 3 else ())
     else:
         values = np.array(getattr(values, 'values', values), np.float64)                 # (a copy: the mask is written into it)
@@ -242,30 +204,14 @@ def mann_kendall(values, mask=None, batch_size=None):
     (two-sided) float64 as in `mann_kendall_from_counts`; ``sen_slope`` float64, the median of the pairwise slopes per period step
     (NaN with fewer than two values).  Host arrays go up in bands of ``batch_size`` grid rows; the result does not depend on it."""
     from . import _lib
-    from .device import Buffers
     check_batch_size(batch_size)
-    values, (P, H, W, C) = _trend_values(values, mask)
+    values, shape = _trend_values(values, mask)
     lib = _lib.lib()
-    per, row = H * W * C, W * C
+    P, H, W, C = shape
+    per = H * W * C
     n, mk, sen = np.empty(per, np.int32), np.empty((2, per), np.int64), np.empty(per, np.float64)
-    with Buffers() as buf:
-        if _is_device(values):
-            dn, dmk, dsen = buf.alloc(n.shape, n.dtype), buf.alloc(mk.shape, mk.dtype), buf.alloc(sen.shape, sen.dtype)
-            _lib.check(lib.dl4ds_trend(values.ptr, P, per, dn.ptr, dmk.ptr, dsen.ptr))
-            dn.download(n), dmk.download(mk), dsen.download(sen)
-        else:
-            bmax = upload_batch(batch_size, 2 * P * row, H)                              # (fp64: two floats per value)
-            dv = buf.alloc((P, bmax * row), np.float64)
-            dn, dmk, dsen = buf.alloc((bmax * row,), np.int32), buf.alloc((2, bmax * row), np.int64), buf.alloc((bmax * row,), np.float64)
-            for i in range(0, H, bmax):
-                b = min(bmax, H - i)
-                cells, c0 = b * row, i * row
-                dv.upload(np.ascontiguousarray(values[:, i:i + b]).reshape(P, cells))
-                _lib.check(lib.dl4ds_trend(dv.ptr, P, cells, dn.ptr, dmk.ptr, dsen.ptr))
-                part = np.empty((2, cells), np.int64)
-                dmk.download(part)
-                mk[:, c0:c0 + cells] = part
-                dn.download(n[c0:c0 + cells]), dsen.download(sen[c0:c0 + cells])
+    cell_bands(values, None, shape, (n, mk, sen), lambda band: _lib.check(lib.dl4ds_trend(band.x, P, band.cells, *band.outs)),
+               batch_size, dtype=np.float64)
     grid = (H, W, C)
     return mann_kendall_from_counts(n.reshape(grid), mk[0].reshape(grid), mk[1].reshape(grid), sen.reshape(grid))
 

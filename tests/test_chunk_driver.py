@@ -1,4 +1,4 @@
-"""The host side the verification scores share, without a device: the buffer scope of dl4ds_amd/device.py, the chunk driver of
+"""The host side the verification scores share, without a device: the buffer scope of dl4ds_amd/device.py, the chunk driver and the band driver of
 dl4ds_amd/_chunks.py and the exact ratios of dl4ds_amd/_exact.py.  A stub stands in for the library: device memory is host memory."""
 import ctypes
 import gc
@@ -158,6 +158,127 @@ def test_chunk_driver_covers_every_unit_once_in_order(stub):
     empty, full = np.empty((3, 2, 0), np.float64), np.empty((3,), np.int64)
     paired_chunks(y, y, (empty, full), lambda b, *ptrs: None, batch_size=2)
     assert [n for _, _, n in stub.d2h] == [16, 8]
+
+
+# ---------------------------------------------------------------------------------------------------------- the band driver
+GRID = (4, 5, 3, 2)                                    # N, H, W, C: bands of 2 grid rows leave a ragged last band of one
+
+
+def _bands(batch_size):
+    """[(cells, c0)] that `cell_bands` must hand out on GRID"""
+    _, H, W, C = GRID
+    b = min(batch_size or H, H)
+    return [(min(b, H - i) * W * C, i * W * C) for i in range(0, H, b)]
+
+
+def _fill(ptr, shape, dtype, c0):
+    """writes cell index + 1000 * leading index into the device buffer [...][cells] at ``ptr``"""
+    cells = shape[-1]
+    lead = np.arange(int(np.prod(shape[:-1], dtype=np.int64))).reshape(shape[:-1] + (1,))
+    want = np.ascontiguousarray((c0 + np.arange(cells)) + 1000 * lead, dtype)
+    ctypes.memmove(ptr, want.ctypes.data, want.nbytes)
+
+
+def _expected(shape, dtype):
+    per = shape[-1]
+    lead = np.arange(int(np.prod(shape[:-1], dtype=np.int64))).reshape(shape[:-1] + (1,))
+    return (np.arange(per) + 1000 * lead).astype(dtype)
+
+
+@pytest.mark.parametrize('batch_size', [2, 5, None])
+def test_cell_bands_cover_every_cell_once_and_place_the_outputs(stub, batch_size):
+    from dl4ds_amd._chunks import cell_bands
+    N, H, W, C = GRID
+    per = H * W * C
+    rng = np.random.default_rng(5)
+    x = rng.integers(-300, 300, GRID).astype(np.int16)                     # goes up as its float32 conversion
+    pred = rng.standard_normal(GRID)
+    field = rng.standard_normal((3,) + GRID[1:]).astype(np.float32)        # per cell: cut per band
+    flat = np.arange(3, dtype=np.float32)                                  # (T,): uploaded once
+    empty = np.zeros((0,), np.float32)
+    outs = [np.full((per,), -1, np.int32), None, np.full((2, per), -1, np.int64), np.full((3, 2, per), np.nan, np.float64)]
+    seen = []
+
+    def call(band):
+        seen.append((band.cells, band.c0))
+        rows = slice(band.c0 // (W * C), (band.c0 + band.cells) // (W * C))
+        assert ctypes.string_at(band.x, N * band.cells * 4) == np.ascontiguousarray(x[:, rows], np.float32).tobytes()
+        assert ctypes.string_at(band.pred, N * band.cells * 4) == np.ascontiguousarray(pred[:, rows], np.float32).tobytes()
+        assert ctypes.string_at(band.fields[0], 3 * band.cells * 4) == np.ascontiguousarray(field[:, rows]).tobytes(), 'cell order'
+        assert ctypes.string_at(band.fields[1], 12) == flat.tobytes() and band.fields[2] is None
+        assert band.outs[1] is None
+        for h, ptr in zip(outs, band.outs):
+            if h is not None:
+                _fill(ptr, h.shape[:-1] + (band.cells,), h.dtype, band.c0)
+    cell_bands(x, pred, GRID, outs, call, batch_size, fields=(field, flat, empty))
+    want = _bands(batch_size)
+    assert seen == want and (batch_size != 2 or want == [(12, 0), (12, 12), (6, 24)]), 'ascending, every cell once'
+    for h in (outs[0], outs[2], outs[3]):
+        np.testing.assert_array_equal(h, _expected(h.shape, h.dtype))
+    # two inputs, three outputs, two fields: allocated once at the widest band, every one freed exactly once
+    assert stub.n_malloc == 7 and sorted(stub.frees.values()) == [1] * 7 and not stub.live
+    flat_uploads = [sent for _, _, sent in stub.h2d if sent == flat.tobytes()]
+    assert len(flat_uploads) == 1 and len(stub.h2d) == 3 * len(want) + 1
+    assert sum(n for _, _, n in stub.d2h) == sum(h.nbytes for h in outs if h is not None), 'every output column comes back once'
+
+
+def test_cell_bands_upload_dtype(stub):
+    from dl4ds_amd._chunks import cell_bands
+    x = np.random.default_rng(6).standard_normal(GRID)                     # float64 stays float64 when asked for
+    n = np.empty((GRID[1] * GRID[2] * GRID[3],), np.int32)
+    cell_bands(x, None, GRID, (n,), lambda band: _fill(band.outs[0], (band.cells,), np.int32, band.c0), 2, dtype=np.float64)
+    assert [sent for _, _, sent in stub.h2d] == [np.ascontiguousarray(x[:, i:i + 2]).tobytes() for i in (0, 2, 4)]
+    np.testing.assert_array_equal(n, np.arange(n.size))
+    del stub.h2d[:]
+    ints = np.arange(np.prod(GRID), dtype=np.int16).reshape(GRID)
+    cell_bands(ints, None, GRID, (n,), lambda band: None, 5)
+    assert [sent for _, _, sent in stub.h2d] == [ints.astype(np.float32).tobytes()]
+
+
+def test_cell_bands_free_every_buffer_also_when_the_call_raises(stub):
+    from dl4ds_amd._chunks import cell_bands
+
+    class Boom(Exception):
+        pass
+    x = np.zeros(GRID, np.float32)
+    out = np.empty((2, GRID[1] * GRID[2] * GRID[3]), np.float64)
+    extra = []
+
+    def call(band):
+        extra.append(band.buf.alloc((3, band.cells)).ptr)                  # a second phase allocates from the band's scope
+        assert extra[-1] in stub.live
+        if len(extra) > 1:
+            assert extra[0] not in stub.live or extra[0] == extra[-1], 'the first band\'s buffer went with its band'
+        if len(extra) == 2:
+            raise Boom
+    with pytest.raises(Boom):
+        cell_bands(x, None, GRID, (out,), call, 2)
+    assert stub.n_malloc == 4 and sum(stub.frees.values()) == 4 and not stub.live
+    stub.frees.clear()
+    del extra[:]
+    before = stub.n_malloc
+    cell_bands(x, None, GRID, (out,), lambda band: extra.append(band.buf.alloc((band.cells,)).ptr), 2)
+    assert stub.n_malloc - before == 2 + 3 and sum(stub.frees.values()) == 5 and not stub.live
+
+
+def test_cell_bands_device_array_in_one_call(stub):
+    from dl4ds_amd._chunks import cell_bands
+    from dl4ds_amd.device import DeviceArray
+    per = GRID[1] * GRID[2] * GRID[3]
+    x = DeviceArray(GRID)
+    field = np.arange(2 * per, dtype=np.float32).reshape((2,) + GRID[1:])
+    out = np.empty((2, per), np.int64)
+    seen = []
+
+    def call(band):
+        seen.append((band.cells, band.c0, band.x))
+        assert ctypes.string_at(band.fields[0], field.nbytes) == field.tobytes()
+        _fill(band.outs[0], (2, band.cells), np.int64, band.c0)
+    cell_bands(x, None, GRID, (out,), call, 2, fields=(field,))
+    assert seen == [(per, 0, x.ptr)] and len(stub.h2d) == 1, 'one call over all cells; nothing of the input is uploaded'
+    np.testing.assert_array_equal(out, _expected(out.shape, np.int64))
+    assert x.ptr in stub.live and len(stub.live) == 1, 'the caller\'s array is not the driver\'s to free'
+    x.free()
 
 
 def test_exact_ratios_against_fractions():

@@ -111,6 +111,33 @@ def test_lmoments_engines_agree_at_the_seam():
     assert_all(device_lmoments(x, cases.LDS_MAX, 65), want)
 
 
+def test_lmoments_and_quantile_table_read_the_same_sorted_rows():
+    """dl4ds_lmoments and dl4ds_quantile_table are the two clients of one per-cell engine (csrc/cell_sort.h): on one array with
+    NaN, +-inf and +-0.0 sprinkled in, each side of every step of the row-length ladder and of the LDS / radix seam, with one cell,
+    a ragged 64-cell tile and a ragged last group, every cell has the same valid count from both, the table at q = (0, 1) is its
+    smallest and largest valid value (tests/qmap_ref.py) and pwm[0] is tests/extremes_ref.py's, bit for bit; sign -1 against -x"""
+    from tests import qmap_ref
+    from tests.test_gpu_qmap import device_table
+    rng = np.random.default_rng(26)
+    full = (4.0 * rng.standard_normal((513, 257))).astype(np.float32)
+    for value, share in ((np.nan, 0.05), (np.inf, 0.02), (-np.inf, 0.02), (0.0, 0.03), (-0.0, 0.03)):
+        full[rng.random(full.shape) < share] = value
+    full[:, 0] = np.nan                                                  # a cell without a valid sample
+    q = np.array([0.0, 1.0])
+    for n, group in ((1, 128), (64, 128), (65, 64), (512, 32), (513, 64)):               # G of the row length; the gather's tile
+        for cells in (1, 65, 2 * group + 1):
+            x = np.ascontiguousarray(full[:n, :cells])
+            for sign in (1, -1):
+                valid, pwm = device_lmoments(x, n, cells, None, sign)
+                signed = x if sign > 0 else -x
+                table, valid_q = device_table(signed, q)
+                np.testing.assert_array_equal(valid_q, valid.astype(np.int64), err_msg=str((n, cells, sign)))
+                want_table, want_n = qmap_ref.quantile_table(signed, q)
+                np.testing.assert_array_equal(valid_q, want_n)
+                assert_bits(table, want_table, ('table', n, cells, sign))
+                assert_bits(pwm[0], ref.pwm(x, sign)[1][0], ('pwm[0]', n, cells, sign))
+
+
 # -------------------------------------------------------------------------------------------------------------- dl4ds_pot_peaks
 def device_pot(x, st, thr, sign=1, run=1, K=0, want=(True, True), then_lmoments=False):
     """dl4ds_pot_peaks on the (N, cells) host array -> (count, peak, pos), None where the pointer was null; with then_lmoments the
