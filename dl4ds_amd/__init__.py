@@ -40,6 +40,8 @@ def __getattr__(name):
             'exceedance_scores': '.metrics', 'verify_exceedance': '.inference', 'ExceedanceVerifier': '.inference',
             'multivariate_scores': '.metrics', 'verify_multivariate': '.inference', 'MultivariateVerifier': '.inference',
             'neighbourhood_scores': '.metrics', 'fss': '.metrics',
+            'neighbourhood_ensemble_scores': '.metrics', 'verify_neighbourhood': '.inference',
+            'NeighbourhoodVerifier': '.inference',
             'sal_from_objects': '.objects', 'check_object_args': '.objects',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',

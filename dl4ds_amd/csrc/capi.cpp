@@ -734,6 +734,17 @@ int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C
         ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_ensemble_fss(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B, int H,
+                       int W, int C, const float* thresholds_host, int T, const int* windows_host, int n_windows, long long* sums_dev,
+                       long long* cont_dev, long long* valid_dev) {
+    API_BEGIN
+    ensemble_fss_check_args(members_dev, K, n, member_stride, obs_dev, B, H, W, C, thresholds_host, T, windows_host, n_windows, sums_dev,
+                            cont_dev, valid_dev);                                    // before the workspace is sized
+    const size_t ws = ensemble_fss_workspace_bytes(K, B, H, W, C, T);
+    ensemble_fss(S(), members_dev, K, n, member_stride, obs_dev, B, H, W, C, thresholds_host, T, windows_host, n_windows, sums_dev, cont_dev,
+                 valid_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
 int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, size_t L, size_t seg_stride, size_t elem_stride,
                        const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
                        long long* ks_dev, long long* hist_dev, long long* valid_dev) {

@@ -214,6 +214,19 @@ size_t fss_workspace_bytes(int N, int H, int W, int C, int T);
 void fss_check_args(int N, int H, int W, int C, const float* thresholds, int T, const int* windows, int S);
 void fss(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T,
          const int* windows, int S, long long* sums, long long* cont, long long* valid, void* workspace, size_t workspace_bytes);
+// Neighbourhood verification of the ensemble members[K][n] against obs[n] (ensemble_fss.hip): the n elements are B samples of
+// (H, W, C), each of the B*C planes a field; per valid cell (obs and all members finite) and threshold o = [obs >= t], c = #{k :
+// x_k >= t}; co, cf their sums over fss.hip's window.  sums [B][C][T][S][5] = D = sum (cf - K co)^2, F = sum cf^2, O = sum co^2
+// over all cells, Fv = sum cf^2 over the valid centre cells, X = sum cf over the centre cells with o = 1; cont [B][C][T][2] = sum o,
+// sum c; valid [B][C].  Thresholds and windows are host arrays.  Outputs are overwritten.  Integer arithmetic only.
+// ensemble_fss_check_args throws on a bad or overflowing request (before the workspace is sized).
+size_t ensemble_fss_workspace_bytes(size_t K, size_t B, int H, int W, int C, int T);
+void ensemble_fss_check_args(const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B, int H,
+                             int W, int C, const float* thresholds, int T, const int* windows, int S, const long long* sums,
+                             const long long* cont, const long long* valid);
+void ensemble_fss(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B, int H,
+                  int W, int C, const float* thresholds, int T, const int* windows, int S, long long* sums, long long* cont,
+                  long long* valid, void* workspace, size_t workspace_bytes);
 // Distribution verification (distribution.hip) of S pairs of length-L segments, element k of segment s at [s*seg_stride +
 // k*elem_stride]: per segment quant [S][2][Q] (numpy 'linear' quantiles of the valid values of y, p), w1 [S] (1-Wasserstein), ks [S]
 // (n times the two-sample KS statistic), hist [S][2][E-1] (np.histogram over the E edges; may be null when E == 0), valid [S] (n).

@@ -260,6 +260,126 @@ class ExceedanceScorer(_Accumulators):
         return res
 
 
+# ------------------------------------------------------------------------------------------------ neighbourhood probabilities
+NEIGHBOURHOOD_MAX_MEMBERS = 256                    # caps of dl4ds_ensemble_fss
+NEIGHBOURHOOD_MAX_THRESHOLDS = 16
+NEIGHBOURHOOD_DEFAULT_WINDOWS = (1, 3, 5, 9, 17, 33, 65)       # metrics.FSS_DEFAULT_WINDOWS
+NEIGHBOURHOOD_SUM_BOUND = 1 << 62                  # H*W*(K*m)^2 must stay below it: the 64-bit sums of dl4ds_ensemble_fss are exact
+
+
+def largest_neighbourhood_window(n_members, h, w):
+    """The largest window size n whose sums stay exact: H*W*(K*m)^2 < 2^62 with m = min(n, H)*min(n, W); None when every window
+    is legal (the whole field is).  Window 1 always is: H*W < 2^31 and K <= 256."""
+    K, h, w = int(n_members), int(h), int(w)
+    legal = lambda n: h * w * (K * min(n, h) * min(n, w)) ** 2 < NEIGHBOURHOOD_SUM_BOUND           # noqa: E731
+    if legal(max(h, w)):
+        return None
+    lo, hi = 1, max(h, w)                                       # legal(lo), not legal(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if legal(mid) else (lo, mid)
+    return lo
+
+
+def check_neighbourhood_ensemble_args(sample_shape, n_members, thresholds, windows):
+    """Validation of the neighbourhood verification of an ensemble (no library call) -> (thresholds as float32 (T,), windows as
+    int32 (S,)): ``metrics.check_neighbourhood_args`` (finite, strictly increasing thresholds; positive, strictly increasing
+    integer windows; H*W < 2^31) plus what the ensemble adds: 1 ... 256 members, at most 16 thresholds, a sample shaped (H, W, C)
+    and the overflow rule with the members in it, H*W*(K*m)^2 < 2^62 for m = min(n, H)*min(n, W).  ``sample_shape=None``: the
+    shape is not looked at (for a caller that does not know it yet)."""
+    from .metrics import check_neighbourhood_args
+    K = int(n_members)
+    if not 1 <= K <= NEIGHBOURHOOD_MAX_MEMBERS:
+        raise ValueError(f'`n_members` must be in [1, {NEIGHBOURHOOD_MAX_MEMBERS}], got {n_members}')
+    if sample_shape is None:
+        shape = (1, 1, 1)
+    else:
+        shape = tuple(int(v) for v in sample_shape)
+        if len(shape) != 3 or min(shape) < 1:
+            raise ValueError(f'one sample must be shaped (H, W, C), got {shape}')
+    h, w, _ = shape
+    if sample_shape is not None and h * w < 1 << 31:
+        top = largest_neighbourhood_window(K, h, w)
+        for n in np.atleast_1d(np.asarray(windows)).ravel().tolist() if top is not None else ():
+            if isinstance(n, int) and not isinstance(n, bool) and n > top:
+                m = min(n, h) * min(n, w)
+                raise ValueError(f'window {n} on a {h} x {w} field with {K} members: H*W*(K*m)^2 = {h * w * (K * m) ** 2} with '
+                                 f'm = min(n, H)*min(n, W) = {m} must stay below 2^62 for the exact 64-bit sums; the largest '
+                                 f'legal window for K = {K}, H = {h}, W = {w} is {top}')
+    thr, win = check_neighbourhood_args((1,) + shape, thresholds, windows)
+    if len(thr) > NEIGHBOURHOOD_MAX_THRESHOLDS:
+        raise ValueError(f'at most {NEIGHBOURHOOD_MAX_THRESHOLDS} thresholds per call, got {len(thr)}')
+    return thr, win
+
+
+def neighbourhood_from_sums(sums, cont, nvalid, n_members, thresholds, windows):
+    """The result dict of the neighbourhood verification of an ensemble from the integer outputs of ``dl4ds_ensemble_fss`` (host
+    arithmetic only, no library): ``sums`` (N, C, T, S, 5) = D, F, O, Fv, X, ``cont`` (N, C, T, 2) = E, Cs, ``nvalid`` (N, C).
+    Every score is a quotient of Python integers rounded to fp64 once (``pfss`` is 1 minus such a quotient), NaN on a zero
+    denominator; n^4 of a large window and sums pooled beyond int64 are harmless."""
+    K = int(n_members)
+    sums, cont, nvalid = np.asarray(sums).astype(np.int64), np.asarray(cont).astype(np.int64), np.asarray(nvalid).astype(np.int64)
+    win = np.asarray(windows).astype(np.int64).reshape(-1)
+    N, C = nvalid.shape
+    T, S = cont.shape[2], len(win)
+    if sums.shape != (N, C, T, S, 5) or cont.shape != (N, C, T, 2):
+        raise ValueError(f'expected sums (N, C, T, {S}, 5), cont (N, C, T, 2) and nvalid (N, C), got {sums.shape}, {cont.shape}, '
+                         f'{nvalid.shape}')
+    so = sums.astype(object)
+    D, F, O, Fv, X = (so[..., q] for q in range(5))
+    E, Cs, nv = cont[..., 0].astype(object), cont[..., 1].astype(object), nvalid.astype(object)
+    n2 = np.asarray([int(n) ** 2 for n in win], object)        # the REQUESTED n, also where the kernel clamps the window
+    kn = K * K * n2 * n2                                        # K^2 n^4, (S,)
+    num = Fv - 2 * K * n2 * X + kn * E[..., None]               # K^2 n^4 n_valid times the neighbourhood Brier score
+    den = np.broadcast_to(kn * nv[..., None, None], num.shape)
+    pool = lambda a: np.sum(a, axis=(0, 1))                     # noqa: E731  (Python integers: cannot overflow)
+    pE, pCs, pn = pool(E), pool(Cs), int(pool(nv))
+    res = dict(sums=sums, events=cont[..., 0].copy(), member_events=cont[..., 1].copy(), n_valid=nvalid, n_members=K,
+               thresholds=np.asarray(thresholds, np.float32), windows=win)
+    res['pfss'] = 1.0 - ratio_exact(D, F + K * K * O)
+    res['pfss_pooled'] = 1.0 - ratio_exact(pool(D), pool(F + K * K * O))
+    res['nbs'] = ratio_exact(num, den)
+    pnum, pden = pool(num), pool(den)
+    res['nbs_pooled'] = ratio_exact(pnum, pden)
+    unc = kn * (pE * (pn - pE))[:, None]                        # K^2 n^4 n_valid^2 f_o (1 - f_o)
+    res['nbss_pooled'] = ratio_exact(unc - pnum * pn, unc)
+    base = ratio_exact(pE, np.full(pE.shape, pn, object))
+    res.update(base_rate=base, forecast_rate=ratio_exact(pCs, np.full(pCs.shape, K * pn, object)), fss_random=base.copy(),
+               fss_useful=0.5 + base / 2.0)
+    with np.errstate(invalid='ignore'):
+        reach = res['pfss_pooled'] >= res['fss_useful'][:, None]          # NaN compares false
+    res['useful_window'] = np.where(reach.any(1), win[np.argmax(reach, 1)], -1).astype(np.int64)
+    return res
+
+
+class NeighbourhoodScorer(_Accumulators):
+    """The counterpart of ``Scorer`` for neighbourhood probabilities (csrc/ensemble_fss.hip): per batch
+    the entry writes the per-field integer sums, which come back with the batch; ``result`` derives the scores on the host
+    (``neighbourhood_from_sums``).  ``thr32``, ``win32``: what ``check_neighbourhood_ensemble_args`` returned.  There are no
+    per-element fields to return."""
+
+    def __init__(self, n_members, n_samples, sample_shape, thr32, win32, bmax):
+        self.thr = np.ascontiguousarray(thr32, np.float32)
+        self.win = np.ascontiguousarray(win32, np.int32)
+        self.T, self.S = len(self.thr), len(self.win)
+        self.H, self.W, self.C = (int(v) for v in sample_shape)
+        super().__init__(n_members, n_samples, sample_shape, False, bmax, (self.C, self.T, self.S, 5), np.int64)
+        self.dev.update(cont=DeviceArray((self.bmax, self.C, self.T, 2), np.int64), valid=DeviceArray((self.bmax, self.C), np.int64))
+        self.cont = np.zeros((self.N, self.C, self.T, 2), np.int64)
+        self.valid = np.zeros((self.N, self.C), np.int64)
+
+    def _launch(self, stack_ptr, stride, obs_ptr, first, b):
+        d = self.dev
+        _lib.check(self.lib.dl4ds_ensemble_fss(stack_ptr, self.K, b * self.per, stride, obs_ptr, b, self.H, self.W, self.C,
+                                               self.thr.ctypes.data, self.T, self.win.ctypes.data, self.S, d['sample'].ptr,
+                                               d['cont'].ptr, d['valid'].ptr))
+        d['cont'].download(self.cont[first:first + b])
+        d['valid'].download(self.valid[first:first + b])
+
+    def result(self):
+        return neighbourhood_from_sums(self.sample_sums, self.cont, self.valid, self.K, self.thr, self.win)
+
+
 # ------------------------------------------------------------------------------------------------ energy and variogram scores
 MULTIVARIATE_MIN_MEMBERS, MULTIVARIATE_MAX_MEMBERS = 2, 128       # caps of dl4ds_ensemble_energy / dl4ds_ensemble_variogram
 MULTIVARIATE_MAX_LAG = 8

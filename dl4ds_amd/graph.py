@@ -12,8 +12,8 @@ import numpy as np
 from . import _lib
 from ._chunks import check_batch_size, is_int
 from .device import Buffers, DeviceArray
-from .ensemble_score import (ExceedanceScorer, MultivariateScorer, Scorer, check_exceedance_args, check_multivariate_args,
-                             check_score_args)
+from .ensemble_score import (NEIGHBOURHOOD_DEFAULT_WINDOWS, ExceedanceScorer, MultivariateScorer, NeighbourhoodScorer, Scorer,
+                             check_exceedance_args, check_multivariate_args, check_neighbourhood_ensemble_args, check_score_args)
 
 ACT_KINDS = {'relu': 1, 'sigmoid': 2, 'tanh': 3, 'elu': 4, 'leaky_relu': 5, 'selu': 6, 'gelu': 7}
 
@@ -892,6 +892,27 @@ class Model:
             return lambda n, bmax: MultivariateScorer(n_members, n, shape, lag, order, code, lag_weights, fair, w32, bmax)
         return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('multivariate', y_true, prepare),
                                   'score_multivariate')
+
+    def score_neighbourhood(self, inputs, y_true, n_members, thresholds, windows=NEIGHBOURHOOD_DEFAULT_WINDOWS, batch_size=32,
+                            seed=None):
+        """``predict_ensemble`` plus the neighbourhood verification of the ensemble as a probability forecast of the events
+        ``value >= threshold`` against the observation ``y_true`` of shape (N,) + output_shape, reduced on the device while each
+        batch's member stack is resident (csrc/ensemble_fss.hip).  Returns ``predict_ensemble``'s dict with
+        one more key, 'neighbourhood': the dict ``metrics.neighbourhood_ensemble_scores`` describes (the Fractions Skill Score of
+        the neighbourhood ensemble probability and the neighbourhood Brier score per threshold and window size, all from exact
+        integer sums).  ``thresholds``: up to 16 finite, strictly increasing numbers in the units of the model's output;
+        ``windows``: strictly increasing sizes >= 1.  A cell is valid iff its observation and all its members are finite: write
+        NaN into ``y_true`` to mask.  The output must be shaped (H, W, C): a recurrent model's is refused.  The sums do not depend
+        on how the scored samples are grouped (the members do depend on ``batch_size``, as in ``predict_ensemble``)."""
+        n_members, q = check_ensemble_args(n_members, (), seed, batch_size)
+        # (the sample's shape and the overflow rule are checked in _run_ensemble, once the model is the one planned for the grid)
+        check_neighbourhood_ensemble_args(None, n_members, thresholds, windows)
+
+        def prepare(shape):
+            thr, win = check_neighbourhood_ensemble_args(shape, n_members, thresholds, windows)
+            return lambda n, bmax: NeighbourhoodScorer(n_members, n, shape, thr, win, bmax)
+        return self._run_ensemble(inputs, n_members, q, batch_size, seed, False, ('neighbourhood', y_true, prepare),
+                                  'score_neighbourhood')
 
     def _run_ensemble(self, inputs, n_members, q, batch_size, seed, return_members, verify=None, who='predict_ensemble'):
         """The per-batch loop of ``predict_ensemble`` / ``score_ensemble`` / ``score_exceedance``: inputs (and the observation)

@@ -3,7 +3,8 @@ import numpy as np
 
 from . import POSTUPSAMPLING_METHODS
 from .dataloader import create_batch_hr_lr
-from .ensemble_score import check_exceedance_args, check_multivariate_args, check_score_args
+from .ensemble_score import (NEIGHBOURHOOD_DEFAULT_WINDOWS, check_exceedance_args, check_multivariate_args,
+                             check_neighbourhood_ensemble_args, check_score_args)
 from .graph import check_ensemble_args
 from .metrics import _masked_observation
 
@@ -242,7 +243,7 @@ def verify_ensemble(trainer, array, scale, n_members, y_true=None, quantiles=(),
     return _saved_and_returned(res, 'scores', inputs, save_path, save_fname, return_lr)
 
 
-def _model_unit_thresholds(thresholds, scaler, sample_shape):
+def _model_unit_thresholds(thresholds, scaler, sample_shape, who='verify_exceedance'):
     """Physical ``thresholds`` (checked by ``check_exceedance_args``; (T,) values or (T,) + sample_shape fields) -> (float32 threshold fields (T,) + sample_shape in the
     model's units, number of cells excluded): every threshold goes through ``scaler.transform`` as a field, evaluated on two
     samples of which the first is kept (the scalers drop size-1 axes); cells whose ``scaler_slope`` is not finite and positive
@@ -255,7 +256,7 @@ def _model_unit_thresholds(thresholds, scaler, sample_shape):
             both = np.broadcast_to(np.asarray(t, np.float64), (2,) + sample_shape).copy()
             fields.append(np.asarray(scaler.transform(both), np.float32)[0].reshape(sample_shape))
     except IndexError:
-        raise ValueError('verify_exceedance: `scaler` has no per-cell transform for one sample (a scaler fitted on data with NaNs '
+        raise ValueError(f'{who}: `scaler` has no per-cell transform for one sample (a scaler fitted on data with NaNs '
                          'carries a mask of the full array\'s shape); that is not supported') from None
     thr = np.stack(fields)
     with np.errstate(invalid='ignore'):
@@ -331,6 +332,46 @@ def verify_multivariate(trainer, array, scale, n_members, y_true=None, seed=None
     _finish_ensemble(res, scaler, time_window)
     res['multivariate'] = scores
     return _saved_and_returned(res, 'multivariate', inputs, save_path, save_fname, return_lr)
+
+
+def verify_neighbourhood(trainer, array, scale, n_members, thresholds, windows=NEIGHBOURHOOD_DEFAULT_WINDOWS, y_true=None, seed=None,
+                         mask=None, array_in_hr=True, static_vars=None, predictors=None, time_window=None, time_metadata=None,
+                         interpolation='inter_area', batch_size=64, scaler=None, save_path=None,
+                         save_fname='y_hat_neighbourhood.npz', return_lr=False, device='GPU'):
+    """``predict_ensemble`` plus the NEIGHBOURHOOD verification of the ensemble as a probability forecast of the events ``value >=
+    threshold``, reduced on the device while the member stack is resident (``Model.score_neighbourhood``, csrc/ensemble_fss.hip):
+    returns ``predict_ensemble``'s dict of statistics with one more key, 'neighbourhood' -- the Fractions Skill Score of the
+    neighbourhood ensemble probability and the neighbourhood Brier score per threshold and window size; see
+    ``metrics.neighbourhood_ensemble_scores`` for every key.  All of them come from exact integer sums.
+
+    ``thresholds``: up to 16 strictly increasing numbers in PHYSICAL units; ``windows``: strictly increasing sizes >= 1.
+    ``y_true``, ``mask``: as in ``verify_ensemble`` (the observation in physical units; None means the HR ``array`` itself, allowed
+    only with ``array_in_hr=True`` and without a ``scaler``).  ``scaler``: the observation and the thresholds go through
+    ``scaler.transform``: EVENTS ARE DECIDED IN THE MODEL'S UNITS, where the members live.  The entry takes one value per threshold,
+    so the transform must map a threshold to the same value in every cell (a scaler fitted over all axes does) and keep the
+    thresholds increasing; anything else raises ValueError.  NaN in ``y_true`` stays NaN through the transform.  ``save_path``: one
+    ``np.savez`` of the statistics and the scores (flattened with a ``neighbourhood_`` prefix).
+
+    Out of scope: recurrent models.  ``time_window is not None`` raises ValueError, because how the scores of overlapping windows
+    flatten to spatial samples is not defined yet."""
+    y_true = _check_verify_args(array, scale, n_members, y_true, (), seed, False, array_in_hr, time_window, batch_size, scaler,
+                                who='verify_neighbourhood', model_method='Model.score_neighbourhood')
+    thr, win = check_neighbourhood_ensemble_args(y_true.shape[1:], n_members, thresholds, windows)
+    model, inputs = _prepare_inputs(trainer, array, scale, array_in_hr, static_vars, predictors, time_window, interpolation)
+    obs = _model_unit_observation(y_true, scaler, mask)
+    if scaler is not None:
+        physical = np.atleast_1d(np.asarray(getattr(thresholds, 'values', thresholds), np.float64))
+        fields, _ = _model_unit_thresholds(physical, scaler, y_true.shape[1:], who='verify_neighbourhood')
+        flat = fields.reshape(len(physical), -1)
+        if not (flat == flat[:, :1]).all():                    # (a NaN, the mark of an unusable cell, fails it too)
+            raise ValueError('verify_neighbourhood: `scaler` maps a threshold to different values in different cells; the '
+                             'neighbourhood verification takes one value per threshold (score in the model\'s units instead)')
+        thr = flat[:, 0]
+    res = model.score_neighbourhood(inputs, obs, n_members, thr, win.tolist(), batch_size=batch_size, seed=seed)
+    scores = res.pop('neighbourhood')
+    _finish_ensemble(res, scaler, time_window)
+    res['neighbourhood'] = scores
+    return _saved_and_returned(res, 'neighbourhood', inputs, save_path, save_fname, return_lr)
 
 
 class Predictor:
@@ -409,6 +450,22 @@ class ExceedanceVerifier:
 
     def run(self):
         return verify_exceedance(**self.kw)
+
+
+class NeighbourhoodVerifier:
+    """``EnsembleVerifier`` for neighbourhood probabilities: same constructor-then-``.run()`` shape, runs ``verify_neighbourhood``."""
+
+    def __init__(self, trainer, array, scale, n_members, thresholds, windows=NEIGHBOURHOOD_DEFAULT_WINDOWS, y_true=None, seed=None,
+                 mask=None, array_in_hr=False, static_vars=None, predictors=None, time_window=None, time_metadata=None,
+                 interpolation='inter_area', batch_size=64, scaler=None, save_path=None, save_fname='y_hat_neighbourhood.npz',
+                 return_lr=False, device='GPU'):
+        self.kw = dict(trainer=trainer, array=array, scale=scale, n_members=n_members, thresholds=thresholds, windows=windows,
+                       y_true=y_true, seed=seed, mask=mask, array_in_hr=array_in_hr, static_vars=static_vars, predictors=predictors,
+                       time_window=time_window, time_metadata=time_metadata, interpolation=interpolation, batch_size=batch_size,
+                       scaler=scaler, save_path=save_path, save_fname=save_fname, return_lr=return_lr, device=device)
+
+    def run(self):
+        return verify_neighbourhood(**self.kw)
 
 
 class MultivariateVerifier:

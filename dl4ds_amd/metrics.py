@@ -16,8 +16,8 @@ from . import _exact, _lib
 from ._chunks import check_batch_size, host_ensemble, paired_chunks
 from .device import DeviceArray
 from .dataloader import checkarray_ndim
-from .ensemble_score import (ExceedanceScorer, MultivariateScorer, Scorer, check_exceedance_args, check_multivariate_args,
-                             check_score_args)
+from .ensemble_score import (ExceedanceScorer, MultivariateScorer, NeighbourhoodScorer, Scorer, check_exceedance_args,
+                             check_multivariate_args, check_neighbourhood_ensemble_args, check_score_args)
 from .graph import check_ensemble_args
 
 
@@ -407,6 +407,39 @@ def scores_from_counts(sums, cont, nvalid, thresholds, windows):
         reach = res['fss_pooled'] >= res['fss_useful'][:, None]       # NaN compares false
     res['useful_window'] = np.where(reach.any(1), res['windows'][np.argmax(reach, 1)], -1).astype(np.int64)
     return res
+
+
+def neighbourhood_ensemble_scores(y_true, members, thresholds, windows=FSS_DEFAULT_WINDOWS, mask=None, batch_size=None):
+    """Scale- and threshold-dependent verification of an ensemble the caller already has on the host as a PROBABILITY forecast:
+    ``members`` shaped (K,) + y_true.shape against the observation ``y_true`` (N, H, W, C), uploaded in chunks of ``batch_size``
+    samples (default: chunks of at most 256 MiB of members) and reduced on the device by the entry ``Model.score_neighbourhood``
+    uses (csrc/ensemble_fss.hip).  Every one of the N*C planes is one field.  ``thresholds``: up to 16
+    finite, strictly increasing numbers (cast to float32); ``windows``: strictly increasing sizes >= 1.  A cell is valid iff its
+    observation and all K members are finite and ``mask`` (2-D or with a channel axis, 0 = excluded) keeps it.  On a valid cell
+    o = [y >= t] and c = #{k : x_k >= t}; co, cf are their sums over the window of `neighbourhood_scores`.  The neighbourhood
+    ensemble probability (Schwartz et al. 2010) is cf / (K n^2): a sharp member that is displaced by less than the window still
+    counts, which the per-cell scores of `exceedance_scores` punish twice.  The device returns exact int64 sums, so the result
+    equals an integer reference and does not depend on ``batch_size``.  Returns a dict:
+
+    * ``sums`` (N, C, T, S, 5) int64: D = sum (cf - K co)^2, F = sum cf^2, O = sum co^2 over all cells, Fv = sum cf^2 over the
+      valid cells, X = sum cf over the cells with o = 1; ``events`` = sum o and ``member_events`` = sum c (N, C, T), ``n_valid``
+      (N, C), all int64;
+    * ``pfss`` (N, C, T, S) = 1 - D / (F + K^2 O): the FSS of the neighbourhood ensemble probability against the observed
+      fraction co / n^2; ``pfss_pooled`` (T, S) = 1 - sum D / sum (F + K^2 O) over the fields;
+    * ``nbs`` (N, C, T, S) and ``nbs_pooled`` (T, S): the neighbourhood Brier score, the mean over the valid cells of
+      (cf / (K n^2) - o)^2 with the requested n (at n = 1 the Brier score of `exceedance_scores`); ``nbss_pooled`` (T, S) =
+      1 - nbs / (f_o (1 - f_o));
+    * ``base_rate`` = ``fss_random`` (T,): the pooled observed frequency f_o, ``forecast_rate`` (T,) = sum c / (K n_valid),
+      ``fss_useful`` = 0.5 + base_rate / 2 and ``useful_window`` (T,): the smallest requested window whose pooled pFSS reaches
+      it, or -1;
+    * ``thresholds`` (float32), ``windows`` and ``n_members`` as used.  Every ratio is NaN on a zero denominator."""
+    members, K, _, y_true = _host_ensemble_args(y_true, members, (), None, batch_size)
+    if y_true.ndim != 4 or min(y_true.shape) < 1:
+        raise ValueError(f'expected a non-empty (N, H, W, C) observation, got shape {y_true.shape}')
+    N, sample_shape = y_true.shape[0], tuple(y_true.shape[1:])
+    thr, win = check_neighbourhood_ensemble_args(sample_shape, K, thresholds, windows)
+    return host_ensemble(_masked_observation(y_true, mask), members, batch_size=batch_size,
+                         make_scorer=lambda bmax: NeighbourhoodScorer(K, N, sample_shape, thr, win, bmax))
 
 
 def fss(y, y_hat, thresholds, windows=FSS_DEFAULT_WINDOWS, scaler=None, mask=None, batch_size=None):

@@ -332,6 +332,34 @@ int dl4ds_variogram_lags(int max_lag, int* dydx_out, int* count_out);
  * 4 T per cell written once, 16 T per cell and window read, mostly from cache. */
 int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
               const int* windows_host, int S, long long* sums_dev, long long* cont_dev, long long* valid_dev);
+/* Neighbourhood verification of an MC-dropout ensemble as a PROBABILITY forecast: the Fractions Skill Score of the neighbourhood
+ * ensemble probability (Schwartz et al. 2010) and the neighbourhood Brier score, for the sharp, slightly displaced members that
+ * every per-cell score punishes twice.  The reference has no such metric; the definitions are DESIGN.md section 28.
+ * members_dev, K, n, member_stride and obs_dev as for dl4ds_ensemble_exceedance: K rows of n fp32 values (row k at members_dev +
+ * k * member_stride, 1 <= K <= 256) and the observation obs_dev [n].  The n elements are B whole samples of shape (H, W, C); each
+ * of the B*C planes is one field.  thresholds_host [T] (1 <= T <= 16, finite) and windows_host [S] (S >= 1, each >= 1): HOST
+ * arrays, as for dl4ds_fss.  A cell is VALID iff its observation and all K members are finite: NaN in obs_dev is the masking
+ * mechanism.  Per valid cell and threshold t, every comparison on float32 (-0.0 >= 0.0 holds):
+ *   o = [obs >= t],  c = #{k : x_k >= t} in 0 ... K;  an invalid cell has o = c = 0.
+ * The window of size n at cell (i, j) is dl4ds_fss's: rows [i - n/2, i - n/2 + n), columns likewise, clipped to the field (even n
+ * included, windows larger than the field are legal).  co = sum of o, cf = sum of c over the window; with m = min(n, H) * min(n, W),
+ * co <= m and cf <= K m.  All outputs are overwritten:
+ *   sums_dev  [B][C][T][S][5]  D = sum (cf - K co)^2, F = sum cf^2, O = sum co^2 over all H*W cells; Fv = sum cf^2 over the valid
+ *                              centre cells; X = sum cf over the valid centre cells with o = 1
+ *   cont_dev  [B][C][T][2]     E = sum o, Cs = sum c
+ *   valid_dev [B][C]           number of valid cells
+ * On the host: pFSS = 1 - D / (F + K^2 O), the FSS of the probability cf / (K n^2) against the observed fraction co / n^2; the
+ * neighbourhood Brier score of that probability against the point observation is (Fv - 2 K n^2 X + K^2 n^4 E) / (K^2 n^4 n_valid)
+ * with the REQUESTED n.  With n = 1 it is dl4ds_ensemble_exceedance's Brier score; with K = 1, D, F and O are dl4ds_fss's.
+ * Integer arithmetic only (64-bit sums, integer atomics): the result equals an integer reference, a repeated call gives the same
+ * bits, and nothing depends on B or on how the samples are grouped into calls.  More than 8 thresholds mean a second pass over
+ * the stack.  Refused (non-zero return, dl4ds_last_error): K or T out of range, S < 1, n != B*H*W*C, member_stride < n, a null
+ * pointer, a threshold that is not finite, a window < 1, H*W >= 2^31, or a window with H*W*(K m)^2 >= 2^62.
+ * Algorithmic traffic: (K + 1) * 4 B per cell read once per group of 8 thresholds, then 2-byte row prefixes (4-byte when
+ * K*W > 65535): 4 T per cell written once, 20 T per cell and window read, mostly from cache. */
+int dl4ds_ensemble_fss(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B, int H,
+                       int W, int C, const float* thresholds_host, int T, const int* windows_host, int S, long long* sums_dev,
+                       long long* cont_dev, long long* valid_dev);
 /* Distribution verification of a prediction against an observation: per segment the sample quantiles of either side, the
  * 1-Wasserstein distance, the two-sample Kolmogorov-Smirnov statistic, a histogram of either side and the valid count.  The
  * reference has no such metric; the definitions are DESIGN.md section 15.  Element k of segment s of either array lives at
