@@ -50,12 +50,6 @@ struct ExcArgs {
 
 __device__ __forceinline__ bool exc_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // false for NaN
 
-__device__ __forceinline__ unsigned long long exc_wave_sum(unsigned long long x) {          // lane 0 holds the sum
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-    return x;
-}
-
 template <int VEC>
 __device__ __forceinline__ void exc_load(const float* p, float (&v)[VEC]) {
     if constexpr (VEC == 4) {
@@ -177,7 +171,7 @@ __global__ void __launch_bounds__(EXC_THREADS) ensemble_exceedance_kernel(ExcArg
                 }
                 if (a.count && act) exc_store<VEC>(a.count + (size_t)t * n + e0, res);
                 if (a.sample_out) {
-                    pk = exc_wave_sum(pk);
+                    pk = wave_sum_u64(pk);
                     if ((threadIdx.x & 63) == 0 && pk) {
                         atomicAdd(&slots[slot + t * 4 + 0], (unsigned)(pk >> 52));
                         atomicAdd(&slots[slot + t * 4 + 1], (unsigned)(pk >> 42) & 0x3ffu);

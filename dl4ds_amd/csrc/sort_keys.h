@@ -52,8 +52,6 @@ __device__ __forceinline__ float key_value(uint32_t k) {
     return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
 }
 
-__device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // first position in sorted k[0, n) whose key is >= x (LB) or > x (!LB)
 template <bool LB, typename P>
 __device__ __forceinline__ uint32_t bound(P k, uint32_t n, uint32_t x) {

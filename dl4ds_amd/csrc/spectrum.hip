@@ -38,8 +38,6 @@ struct SpShape { int H, W, C, Wh; };
 // samples [n0, n0 + ns) x channels [c0, c0 + nc): whole samples (nc == C), or some channels of one sample when a sample is over budget
 struct SpChunk { size_t n0; int ns, c0, nc; };
 
-__device__ __forceinline__ bool sp_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // ------------------------------------------------------------------------------------------------------------------ (a) prepare
 __global__ void __launch_bounds__(SP_THREADS) spec_prepare_kernel(const float* __restrict__ y, const float* __restrict__ p, const SpShape sh,
                                                                  int detrend, long long* __restrict__ valid, double* __restrict__ mean) {
@@ -52,7 +50,7 @@ __global__ void __launch_bounds__(SP_THREADS) spec_prepare_kernel(const float* _
     unsigned k = 0;
     for (size_t i = t; i < cells; i += SP_THREADS) {
         const float yv = y[base + i * sh.C], pv = p ? p[base + i * sh.C] : 0.f;
-        if (sp_finite(yv) && sp_finite(pv)) { a += (double)yv; b += (double)pv; ++k; }
+        if (finite_bits(yv) && finite_bits(pv)) { a += (double)yv; b += (double)pv; ++k; }
     }
     sy[t] = a; sp[t] = b; cnt[t] = k;
     group_tree<SP_THREADS>(t, [&](int i, int j) { sy[i] += sy[j]; sp[i] += sp[j]; cnt[i] += cnt[j]; });
@@ -102,7 +100,7 @@ __global__ void __launch_bounds__(SP_THREADS) spec_rows_kernel(const float* __re
                 const int yy = (int)(q % H);
                 const size_t o = ((n * H + yy) * W + j) * C + c;
                 const float a = y[o], b = p ? p[o] : 0.f;
-                if (sp_finite(a) && sp_finite(b))
+                if (finite_bits(a) && finite_bits(b))
                     v = ((double)(side ? b : a) - mean[(n * C + c) * 2 + side]) * (wy[yy] * wx[j]);
             }
             As[jj][r - r0] = v;

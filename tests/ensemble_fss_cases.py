@@ -7,15 +7,10 @@ of fss_cases plus per-member noise, rounded to 0.1 so that ties with the thresho
 threshold indices whose pFSS is NaN by construction (no event on either side: F + K^2 O = 0)."""
 import numpy as np
 
-from tests.fss_cases import NEAR, normal_pair, precip_pair
-
-# constants of csrc/ensemble_fss.hip the shapes below are built around
-SEGMENT = 64                  # cells a wave scans at a time
-COLUMNS = 256                 # EFSS_THREADS: columns per workgroup of the window kernel
-PREFIX_ROWS = 32              # EFSS_PREFIX_ROWS: rows per workgroup of the prefix kernel
-THRESHOLD_GROUP = 8           # EFSS_TG: thresholds per pass over the stack
-WS_BUDGET = 128 << 20         # EFSS_WS_BUDGET: workspace of one chunk of fields
-NARROW_MAX = 65535            # largest K * W with 16-bit prefixes; largest K * m squared in 32 bits
+# the constants of csrc/neighbourhood.h the shapes below are built around: one set for both entries.  Here NARROW_MAX is the
+# largest K * W with 16-bit prefixes and the largest K * m squared in 32 bits, THRESHOLD_GROUP the thresholds per pass over the stack
+from tests.fss_cases import (COLUMNS, NARROW_MAX, NEAR, PREFIX_ROWS, SEGMENT, THRESHOLD_GROUP, WS_BUDGET,  # noqa: F401
+                             normal_pair, precip_pair)
 
 
 def ensemble(rng, p, K, noise=0.4):

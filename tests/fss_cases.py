@@ -5,12 +5,12 @@ Every case is ``dict(y, p, thresholds, windows, mask, nan_thresholds)``: ``nan_t
 is NaN by construction (no event on either side: F + O = 0); everywhere else the FSS is finite."""
 import numpy as np
 
-# constants of csrc/fss.hip the shapes below are built around
+# constants of csrc/neighbourhood.h (shared by fss.hip and ensemble_fss.hip) the shapes below are built around
 SEGMENT = 64                  # cells a wave scans at a time (one __ballot)
-COLUMNS = 256                 # FSS_THREADS: columns per workgroup of the window kernel
-PREFIX_ROWS = 32              # FSS_PREFIX_ROWS: rows per workgroup of the prefix kernel
-THRESHOLD_GROUP = 8           # FSS_TG: thresholds handled per pass over the data
-WS_BUDGET = 128 << 20         # FSS_WS_BUDGET: workspace of one chunk of fields
+COLUMNS = 256                 # NB_THREADS: columns per workgroup of the window kernel
+PREFIX_ROWS = 32              # NB_PREFIX_ROWS: rows per workgroup of the prefix kernel
+THRESHOLD_GROUP = 8           # NB_TG: thresholds handled per pass over the data
+WS_BUDGET = 128 << 20         # NB_WS_BUDGET: workspace of one chunk of fields
 NARROW_MAX = 65535            # largest window count squared in 32 bits; also the widest row with 16-bit prefixes
 
 
