@@ -27,13 +27,6 @@ namespace {
 constexpr int SQNORM_THREADS = 256;
 constexpr int SQNORM_BLOCK_CAP = 1024;
 
-// sum over the 64 lanes of a wave in a fixed tree order; every lane ends with the same value only in lane 0
-__device__ inline double wave_sum_f64(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
-    return x;
-}
-
 __global__ void __launch_bounds__(SQNORM_THREADS) sqnorm_partials_kernel(const float* __restrict__ g, size_t n,
                                                                          double* __restrict__ partials, const unsigned* err) {
     if (err && __builtin_nontemporal_load(err) != 0u) return;
@@ -51,7 +44,7 @@ __global__ void __launch_bounds__(SQNORM_THREADS) sqnorm_partials_kernel(const f
         const double x = g[e];
         acc += x * x;
     }
-    acc = wave_sum_f64(acc);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -97,7 +90,7 @@ __global__ void __launch_bounds__(256) adam_ext_kernel(float* __restrict__ w, co
         if (threadIdx.x < 64) {
             double s = 0.0;
             for (int k = threadIdx.x; k < a.n_partials; k += 64) s += partials[k];
-            s = wave_sum_f64(s);
+            s = wave_sum(s);
             if (threadIdx.x == 0) s_norm = (float)((double)a.gs * sqrt(s));
         }
         __syncthreads();

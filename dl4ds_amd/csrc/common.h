@@ -203,6 +203,11 @@ __device__ __forceinline__ float wave_sum(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     return v;
 }
+__device__ __forceinline__ double wave_sum(double v) {          // a fixed tree: the same bits every call; lane 0 holds the sum
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;
+}
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {      // lane 0 holds the sum
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);

@@ -27,8 +27,7 @@ namespace {
 struct EnsOut { float *mean, *std, *mn, *mx, *quant; };
 
 // ------------------------------------------------------------------------------------------------ K <= 64: registers
-// n % VEC == 0, member_stride % VEC == 0 and every pointer aligned to VEC floats (else the host takes the VEC = 1 instance).
-// FULL: K == KP (the powers of two): no padding and no predication at all.
+// (KP, VEC, FULL) and what the host guarantees for VEC > 1: ens_launch.
 template <int KP, int VEC, bool FULL>
 __global__ void __launch_bounds__(ENS_THREADS) ensemble_reduce_reg(const float* __restrict__ members, int K, size_t n, size_t stride,
                                                                    EnsQ q, int nq, EnsOut out) {
@@ -59,13 +58,7 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_reduce_reg(const float* 
         const double mean = s / (double)K;
         double m2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            float x = v[k][c];
-            asm("" : "+v"(x));                    // converted again, not kept: 2 K fp64 registers would halve the occupancy
-            const double d = (double)x - mean;
-            const double m1 = m2 + d * d;
-            m2 = (FULL || k < K) ? m1 : m2;
-        }
+        for (int k = 0; k < KP; ++k) m2 = ens_m2_add(m2, v[k][c], mean, FULL || k < K);
         isnan_[c] = bad;
         r_mean[c] = bad ? ens_nan() : (float)mean;
         r_std[c] = bad ? ens_nan() : (float)sqrt(m2 / (double)K);
@@ -115,11 +108,7 @@ __global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_reduce_staged(con
     }
     for (int k = K; k < KP; ++k) s[k * ENS_STAGED_THREADS] = __builtin_inff();
     const double mean = sum / (double)K;
-    double m2 = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double d = (double)s[k * ENS_STAGED_THREADS] - mean;
-        m2 += d * d;
-    }
+    const double m2 = ens_m2_column(s, K, mean);
     if (out.mean) out.mean[e] = bad ? ens_nan() : (float)mean;
     if (out.std) out.std[e] = bad ? ens_nan() : (float)sqrt(m2 / (double)K);
     if (out.mn) out.mn[e] = bad ? ens_nan() : mn;
@@ -130,29 +119,6 @@ __global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_reduce_staged(con
         const float a = s[q.lo[j] * ENS_STAGED_THREADS], b = s[q.hi[j] * ENS_STAGED_THREADS];
         out.quant[(size_t)j * n + e] = bad ? ens_nan() : (float)ens_lerp(a, b, q.t[j]);
     }
-}
-
-template <int KP, int VEC>
-void launch_reg_v(hipStream_t s, const float* members, int K, size_t n, size_t stride, const EnsQ& q, int nq, const EnsOut& out) {
-    if constexpr (VEC > 1) {
-        // vector loads / stores need whole, aligned groups in every row; otherwise one element per lane (still coalesced)
-        auto aligned = [](const void* p) { return ((uintptr_t)p % (sizeof(float) * VEC)) == 0; };
-        if (n % VEC || stride % VEC || !aligned(members) || !aligned(out.mean) || !aligned(out.std) || !aligned(out.mn) ||
-            !aligned(out.mx) || !aligned(out.quant))
-            return launch_reg_v<KP, 1>(s, members, K, n, stride, q, nq, out);
-    }
-    const size_t blocks = cdivz(n, (size_t)ENS_THREADS * VEC);
-    DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_reduce: too many elements for one launch");
-    if (K == KP)
-        DL4DS_LAUNCH((ensemble_reduce_reg<KP, VEC, true>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, q,
-                     nq, out);
-    else
-        DL4DS_LAUNCH((ensemble_reduce_reg<KP, VEC, false>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, q,
-                     nq, out);
-}
-template <int KP, int VEC>
-void launch_reg(hipStream_t s, const float* members, int K, size_t n, size_t stride, const EnsQ& q, int nq, const EnsOut& out) {
-    launch_reg_v<KP, VEC>(s, members, K, n, stride, q, nq, out);
 }
 
 }  // namespace
@@ -170,19 +136,15 @@ void ensemble_reduce(hipStream_t s, const float* members, size_t K, size_t n, si
     const EnsOut out{mean, std_, mn, mx, quant};
     const int k = (int)K;
     ProfScope ps(s, "ensemble_reduce", (double)n * (4.0 * K), (double)n * 4.0 * (double)(K + 4 + nq));
-    if (k <= 2) launch_reg<2, 4>(s, members, k, n, member_stride, q, nq, out);
-    else if (k <= 4) launch_reg<4, 4>(s, members, k, n, member_stride, q, nq, out);
-    else if (k <= 8) launch_reg<8, 4>(s, members, k, n, member_stride, q, nq, out);
-    else if (k <= 16) launch_reg<16, 4>(s, members, k, n, member_stride, q, nq, out);
-    else if (k <= 32) launch_reg<32, 2>(s, members, k, n, member_stride, q, nq, out);
-    else if (k <= 64) launch_reg<64, 1>(s, members, k, n, member_stride, q, nq, out);
-    else {
-        const int kp = k <= 128 ? 128 : 256;
-        const size_t blocks = cdivz(n, ENS_STAGED_THREADS);
-        DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_reduce: too many elements for one launch");
-        const size_t lds = (size_t)kp * ENS_STAGED_THREADS * sizeof(float);        // 32 KB / 64 KB
-        DL4DS_LAUNCH(ensemble_reduce_staged, dim3((unsigned)blocks), dim3(ENS_STAGED_THREADS), lds, s, members, k, kp, n,
-                     member_stride, q, nq, out);
-    }
+    ens_launch(
+        "ensemble_reduce", k, n, member_stride, {members, mean, std_, mn, mx, quant},
+        [&](auto KP, auto VEC, auto FULL, dim3 grid) {
+            DL4DS_LAUNCH((ensemble_reduce_reg<decltype(KP)::value, decltype(VEC)::value, decltype(FULL)::value>), grid,
+                         dim3(ENS_THREADS), 0, s, members, k, n, member_stride, q, nq, out);
+        },
+        [&](int kp, dim3 grid, size_t lds) {
+            DL4DS_LAUNCH(ensemble_reduce_staged, grid, dim3(ENS_STAGED_THREADS), lds, s, members, k, kp, n,
+                         member_stride, q, nq, out);
+        });
     HIP_CHECK(hipGetLastError());
 }

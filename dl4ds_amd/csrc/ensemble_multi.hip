@@ -26,8 +26,6 @@
 
 namespace {
 
-__device__ __forceinline__ bool em_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // false for NaN
-
 // ------------------------------------------------------------------------------------------------------------------ energy
 constexpr int EM_THREADS = 256;
 constexpr int EM_RED_BYTES = EM_THREADS * 16 * 8;          // the slice reduction: 16 fp64 per lane
@@ -144,7 +142,7 @@ __global__ void __launch_bounds__(EM_THREADS) ensemble_energy_kernel(EnergyArgs 
             const size_t ge = e0 + e;
             float v = 0.f;
             if (ge < e_end) v = k < K ? mem[(size_t)k * a.stride + ge] : obs[ge];
-            if (!em_finite(v)) {
+            if (!ens_finite(v)) {
                 flag[e] = 0;                                                 // (every writer writes 0)
                 v = 0.f;
             }
@@ -260,12 +258,6 @@ __device__ __forceinline__ float vg_pow(float d) {
     else return m * m;
 }
 
-__device__ __forceinline__ double vg_wave_sum(double x) {                      // lane 0 holds the sum; a fixed tree
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-    return x;
-}
-
 template <int ORDER>
 __global__ void __launch_bounds__(VG_THREADS) ensemble_variogram_kernel(VarioArgs a) {
     __shared__ float mt[VG_MG * VG_MAX_CELLS];               // the staged members' tiles
@@ -305,7 +297,7 @@ __global__ void __launch_bounds__(VG_THREADS) ensemble_variogram_kernel(VarioArg
                 bool ok = false;
                 if (coff[i] >= 0) {
                     ov = obs[coff[i]];
-                    ok = em_finite(ov) && (!a.weight || a.weight[coff[i]] > 0.f);
+                    ok = ens_finite(ov) && (!a.weight || a.weight[coff[i]] > 0.f);
                 }
                 ot[c] = ov;
                 mk[c] = ok ? 1 : 0;
@@ -325,7 +317,7 @@ __global__ void __launch_bounds__(VG_THREADS) ensemble_variogram_kernel(VarioArg
                         for (int m = 0; m < gm; ++m) {
                             float v = 0.f;
                             if (coff[i] >= 0) v = mem[(size_t)(g0 + m) * a.stride + coff[i]];
-                            if (l0 == 0 && !em_finite(v)) mk[c] = 0;         // (every writer writes 0; read after the passes' barrier)
+                            if (l0 == 0 && !ens_finite(v)) mk[c] = 0;         // (every writer writes 0; read after the passes' barrier)
                             mt[m * VG_MAX_CELLS + c] = v;
                         }
                     }
@@ -356,9 +348,9 @@ __global__ void __launch_bounds__(VG_THREADS) ensemble_variogram_kernel(VarioArg
                     const float o = vg_pow<ORDER>(oi - ot[base + off]);
                     const double e = acc[l] / dK;
                     const double d = (double)o - e;
-                    const double s0 = vg_wave_sum(valid ? d * d : 0.0);
-                    const double s1 = vg_wave_sum(valid ? (double)o : 0.0);
-                    const double s2 = vg_wave_sum(valid ? e : 0.0);
+                    const double s0 = wave_sum(valid ? d * d : 0.0);
+                    const double s1 = wave_sum(valid ? (double)o : 0.0);
+                    const double s2 = wave_sum(valid ? e : 0.0);
                     const int n = (int)__popcll(__ballot(valid));
                     if ((tid & 63) == 0) {
                         double* w = wred + (wave * VG_LC + l) * 3;

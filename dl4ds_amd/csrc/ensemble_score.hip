@@ -46,8 +46,6 @@ struct EnsScoreOut {
     unsigned* cov;
 };
 
-__device__ __forceinline__ bool ens_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // false for NaN
-
 __device__ __forceinline__ int ens_tie(unsigned long long seed, unsigned long long g, int equal) {
     unsigned long long z = seed + 0x9E3779B97F4A7C15ull * (g + 1ull);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -93,15 +91,7 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_score_reg(const float* _
     ens_load<KP, VEC, FULL>(members + blk, off, K, stride, v);
     const size_t e0 = blk + off;
     float y[VEC];
-    if constexpr (VEC == 4) {
-        const float4 t = *reinterpret_cast<const float4*>(in.obs + e0);
-        y[0] = t.x; y[1] = t.y; y[2] = t.z; y[3] = t.w;
-    } else if constexpr (VEC == 2) {
-        const float2 t = *reinterpret_cast<const float2*>(in.obs + e0);
-        y[0] = t.x; y[1] = t.y;
-    } else {
-        y[0] = in.obs[e0];
-    }
+    ens_load_vec<VEC>(in.obs + e0, y);
 
     EnsElem el[VEC];
 #pragma unroll
@@ -126,13 +116,7 @@ __global__ void __launch_bounds__(ENS_THREADS) ensemble_score_reg(const float* _
         const double mean = s / (double)K;
         double m2 = 0.0;
 #pragma unroll
-        for (int k = 0; k < KP; ++k) {
-            float x = v[k][c];
-            asm("" : "+v"(x));                    // converted again, not kept (ensemble.hip: the fp64 copies cost the occupancy)
-            const double d = (double)x - mean;
-            const double m1 = m2 + d * d;
-            m2 = (FULL || k < K) ? m1 : m2;
-        }
+        for (int k = 0; k < KP; ++k) m2 = ens_m2_add(m2, v[k][c], mean, FULL || k < K);
         el[c] = EnsElem{yd, sa, mean, m2, below, equal, fin};
     }
 
@@ -189,10 +173,7 @@ __global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_score_staged(cons
     }
     for (int k = K; k < KP; ++k) s[k * ENS_STAGED_THREADS] = __builtin_inff();
     el.mean = sum / (double)K;
-    for (int k = 0; k < K; ++k) {
-        const double d = (double)s[k * ENS_STAGED_THREADS] - el.mean;
-        el.m2 += d * d;
-    }
+    el.m2 = ens_m2_column(s, K, el.mean);
     ens_sort_column(s, KP);
     double pair = 0.0;
     for (int k = 0; k < K; ++k) pair += (double)(2 * k - K + 1) * ((double)s[k * ENS_STAGED_THREADS] - el.y);
@@ -206,12 +187,6 @@ __global__ void __launch_bounds__(ENS_STAGED_THREADS) ensemble_score_staged(cons
 
 // ------------------------------------------------------------------------------------------------ stage 2
 constexpr int FOLD_THREADS = 256, FOLD_WAVES = FOLD_THREADS / 64;
-
-__device__ __forceinline__ double wave_sum(double x) {          // fixed tree over the 64 lanes; lane 0 holds the sum
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) x += __shfl_down(x, d, 64);
-    return x;
-}
 
 __global__ void __launch_bounds__(FOLD_THREADS) ens_score_fold(EnsScoreOut f, size_t per, int B, int K, int nq, double* cell_acc,
                                                                double* partial, size_t n_part, unsigned long long* rank_hist,
@@ -291,26 +266,6 @@ __global__ void __launch_bounds__(FOLD_THREADS) ens_score_sample_sum(const doubl
     if (threadIdx.x < 4) sample_out[b * 4 + threadIdx.x] = red[0][threadIdx.x];
 }
 
-template <int KP, int VEC>
-void launch_reg(hipStream_t s, const float* members, int K, size_t n, size_t stride, const EnsScoreIn& in, const EnsQ& q, int nq,
-                const EnsScoreOut& out) {
-    if constexpr (VEC > 1) {
-        // vector loads / stores need whole, aligned groups in every row; otherwise one element per lane (still coalesced)
-        auto aligned = [](const void* p) { return ((uintptr_t)p % (sizeof(float) * VEC)) == 0; };
-        if (n % VEC || stride % VEC || !aligned(members) || !aligned(in.obs) || !aligned(out.crps) || !aligned(out.sqerr) ||
-            !aligned(out.var) || !aligned(out.rank) || !aligned(out.cov))
-            return launch_reg<KP, 1>(s, members, K, n, stride, in, q, nq, out);
-    }
-    const size_t blocks = cdivz(n, (size_t)ENS_THREADS * VEC);
-    DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_score: too many elements for one launch");
-    if (K == KP)
-        DL4DS_LAUNCH((ensemble_score_reg<KP, VEC, true>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, in,
-                     q, nq, out);
-    else
-        DL4DS_LAUNCH((ensemble_score_reg<KP, VEC, false>), dim3((unsigned)blocks), dim3(ENS_THREADS), 0, s, members, K, n, stride, in,
-                     q, nq, out);
-}
-
 size_t padded(size_t n) { return (n + 3) / 4 * 4; }                 // every field of the workspace starts 16-byte aligned
 size_t n_partials(size_t per) { return cdivz(per, FOLD_THREADS) * FOLD_WAVES; }
 
@@ -347,20 +302,16 @@ void ensemble_score(hipStream_t s, const float* members, size_t K, size_t n, siz
     const double pairs = fair ? (double)K * (double)(K - 1) : (double)K * (double)K;
     const EnsScoreIn in{obs, scale, per, elem_offset, seed, K > 1 ? pairs : 1.0};
     ProfScope ps(s, "ensemble_score", (double)n * (6.0 * K), (double)n * 4.0 * (double)(K + 1 + 5 + 5));
-    if (k <= 2) launch_reg<2, 4>(s, members, k, n, member_stride, in, q, nq, out);
-    else if (k <= 4) launch_reg<4, 4>(s, members, k, n, member_stride, in, q, nq, out);
-    else if (k <= 8) launch_reg<8, 4>(s, members, k, n, member_stride, in, q, nq, out);
-    else if (k <= 16) launch_reg<16, 4>(s, members, k, n, member_stride, in, q, nq, out);
-    else if (k <= 32) launch_reg<32, 2>(s, members, k, n, member_stride, in, q, nq, out);
-    else if (k <= 64) launch_reg<64, 1>(s, members, k, n, member_stride, in, q, nq, out);
-    else {
-        const int kp = k <= 128 ? 128 : 256;
-        const size_t blocks = cdivz(n, ENS_STAGED_THREADS);
-        DL4DS_REQUIRE(blocks <= 0x7fffffffull, "ensemble_score: too many elements for one launch");
-        const size_t lds = (size_t)kp * ENS_STAGED_THREADS * sizeof(float);        // 32 KB / 64 KB
-        DL4DS_LAUNCH(ensemble_score_staged, dim3((unsigned)blocks), dim3(ENS_STAGED_THREADS), lds, s, members, k, kp, n,
-                     member_stride, in, q, nq, out);
-    }
+    ens_launch(
+        "ensemble_score", k, n, member_stride, {members, obs, out.crps, out.sqerr, out.var, out.rank, out.cov},
+        [&](auto KP, auto VEC, auto FULL, dim3 grid) {
+            DL4DS_LAUNCH((ensemble_score_reg<decltype(KP)::value, decltype(VEC)::value, decltype(FULL)::value>), grid,
+                         dim3(ENS_THREADS), 0, s, members, k, n, member_stride, in, q, nq, out);
+        },
+        [&](int kp, dim3 grid, size_t lds) {
+            DL4DS_LAUNCH(ensemble_score_staged, grid, dim3(ENS_STAGED_THREADS), lds, s, members, k, kp, n,
+                         member_stride, in, q, nq, out);
+        });
     HIP_CHECK(hipGetLastError());
     if (!sample_out && !cell_acc && !rank_hist && !covered) return;
     const size_t n_part = n_partials(per);

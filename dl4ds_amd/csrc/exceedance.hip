@@ -24,8 +24,7 @@
 //   wave, per sample: 64 VEC <= 256 elements: sum (c - K o)^2 <= 2^24 (25 bits), sum c <= 2^16 (17 bits), the counts <= 256 (10 bits)
 //   workgroup:        a sample's LDS slot <= 1024 * 65536 = 2^26;  a histogram bin <= 1024 walk < 2^26
 // Integer arithmetic only: the result does not depend on the order of the atomics, the grouping of samples or the batch size.
-#include "common.h"
-#include "ops.h"
+#include "ensemble_common.h"
 #include "prof.h"
 #include <algorithm>
 
@@ -47,36 +46,6 @@ struct ExcArgs {
     unsigned long long* cell_acc;          // [T][4][per]
     unsigned long long* table;             // [T][K + 1][2]
 };
-
-__device__ __forceinline__ bool exc_finite(float x) { return __builtin_fabsf(x) < __builtin_inff(); }      // false for NaN
-
-template <int VEC>
-__device__ __forceinline__ void exc_load(const float* p, float (&v)[VEC]) {
-    if constexpr (VEC == 4) {
-        const float4 x = *reinterpret_cast<const float4*>(p);
-        v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-    } else if constexpr (VEC == 2) {
-        const float2 x = *reinterpret_cast<const float2*>(p);
-        v[0] = x.x; v[1] = x.y;
-    } else {
-        v[0] = p[0];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void exc_store(short* p, const short (&r)[VEC]) {
-    if constexpr (VEC == 4) {
-        uint2 w;
-        __builtin_memcpy(&w, r, 8);
-        *reinterpret_cast<uint2*>(p) = w;
-    } else if constexpr (VEC == 2) {
-        unsigned w;
-        __builtin_memcpy(&w, r, 4);
-        *reinterpret_cast<unsigned*>(p) = w;
-    } else {
-        p[0] = r[0];
-    }
-}
 
 // TP: thresholds held in registers (T <= TP), VEC: consecutive cells per lane, CELL: thresholds per cell ([T][per]) or one per t
 template <int TP, int VEC, bool CELL>
@@ -104,7 +73,7 @@ __global__ void __launch_bounds__(EXC_THREADS) ensemble_exceedance_kernel(ExcArg
         for (int c = 0; c < VEC; ++c) {
             float v = __builtin_nanf("");
             if (t < T) v = CELL ? a.thr[(size_t)t * per + cc + c] : a.thr[t];
-            thr[t][c] = exc_finite(v) ? v : __builtin_nanf("");
+            thr[t][c] = ens_finite(v) ? v : __builtin_nanf("");
         }
     }
     unsigned s_no[TP][VEC], s_c[TP][VEC], s_q[TP][VEC];         // n_valid | sum o << 16, sum c, sum (c - K o)^2 of the lane's cells
@@ -119,11 +88,11 @@ __global__ void __launch_bounds__(EXC_THREADS) ensemble_exceedance_kernel(ExcArg
     for (unsigned b = b0; b < b1; ++b) {
         const size_t e0 = (size_t)b * per + cc;
         float y[VEC];
-        exc_load<VEC>(a.obs + e0, y);
+        ens_load_vec<VEC>(a.obs + e0, y);
         bool fin[VEC];
         int cnt[TP][VEC];
 #pragma unroll
-        for (int c = 0; c < VEC; ++c) fin[c] = exc_finite(y[c]);
+        for (int c = 0; c < VEC; ++c) fin[c] = ens_finite(y[c]);
 #pragma unroll
         for (int t = 0; t < TP; ++t) {
 #pragma unroll
@@ -133,11 +102,11 @@ __global__ void __launch_bounds__(EXC_THREADS) ensemble_exceedance_kernel(ExcArg
 #pragma unroll 4
         for (int k = 0; k < K; ++k) {
             float x[VEC];
-            exc_load<VEC>(row, x);
+            ens_load_vec<VEC>(row, x);
             row += a.stride;
 #pragma unroll
             for (int c = 0; c < VEC; ++c) {
-                fin[c] = fin[c] && exc_finite(x[c]);
+                fin[c] = fin[c] && ens_finite(x[c]);
 #pragma unroll
                 for (int t = 0; t < TP; ++t) cnt[t][c] += x[c] >= thr[t][c] ? 1 : 0;
             }
@@ -169,7 +138,7 @@ __global__ void __launch_bounds__(EXC_THREADS) ensemble_exceedance_kernel(ExcArg
                         if (valid && !z0 && !z1) atomicAdd(&hist[(t * K1 + cn) * 2 + o], 1u);
                     }
                 }
-                if (a.count && act) exc_store<VEC>(a.count + (size_t)t * n + e0, res);
+                if (a.count && act) ens_store<VEC, short>(a.count + (size_t)t * n + e0, res);
                 if (a.sample_out) {
                     pk = wave_sum_u64(pk);
                     if ((threadIdx.x & 63) == 0 && pk) {

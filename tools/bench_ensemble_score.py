@@ -53,10 +53,12 @@ L.check(lib.dl4ds_memcpy_h2d(obs_odd.ptr + 4, obs_host.ctypes.data, obs_host.nby
 sample, cell, cov = DeviceArray((B, 4), np.float64), DeviceArray.zeros((4, n // B), np.float64), DeviceArray.zeros((nq,), np.uint64)
 
 
-def kernel_ms(tag, runs):
+def kernel_ms(runs, *tags):
+    """ms per call of each tag (the report empties the profiler: read once)"""
     buf = ctypes.create_string_buffer(1 << 16)
     L.check(lib.dl4ds_profile_report(buf, len(buf)))
-    return json.loads(buf.value.decode())[tag]['ms'] / runs
+    rep = json.loads(buf.value.decode())
+    return [rep[tag]['ms'] / runs for tag in tags]
 
 
 for Kk in (8, 16, 32, 64):
@@ -78,7 +80,7 @@ for Kk in (8, 16, 32, 64):
     for _ in range(runs):
         score()
         reduce_()
-    ms_s, ms_r = kernel_ms('ensemble_score', runs), kernel_ms('ensemble_reduce', runs)
+    ms_s, ms_r = kernel_ms(runs, 'ensemble_score', 'ensemble_reduce')
     L.check(lib.dl4ds_profile_enable(0))
     for _ in range(3):
         narrow()
@@ -86,7 +88,7 @@ for Kk in (8, 16, 32, 64):
     L.check(lib.dl4ds_profile_enable(1))
     for _ in range(runs):
         narrow()
-    ms_n = kernel_ms('ensemble_score', runs)
+    ms_n, = kernel_ms(runs, 'ensemble_score')
     L.check(lib.dl4ds_profile_enable(0))
     by_s, by_r = (Kk + 1 + 10) * 4 * n, (Kk + 4 + nq) * 4 * n
     result['kernel'].append(dict(K=Kk, n=n, nq=nq, score_ms=round(ms_s, 4), score_gbs=round(by_s / ms_s / 1e6, 1),

@@ -42,10 +42,12 @@ obs = DeviceArray.from_numpy((281.0 + 12.0 * rng.standard_normal(n)).astype(np.f
 s_sample, s_cell, s_cov = DeviceArray((B, 4), np.float64), DeviceArray.zeros((4, per), np.float64), DeviceArray.zeros((nq,), np.uint64)
 
 
-def kernel_ms(tag, runs):
+def kernel_ms(runs, *tags):
+    """ms per call of each tag (the report empties the profiler: read once)"""
     buf = ctypes.create_string_buffer(1 << 16)
     L.check(lib.dl4ds_profile_report(buf, len(buf)))
-    return json.loads(buf.value.decode())[tag]['ms'] / runs
+    rep = json.loads(buf.value.decode())
+    return [rep[tag]['ms'] / runs for tag in tags]
 
 
 for K in (8, 32, 128):
@@ -72,7 +74,7 @@ for K in (8, 32, 128):
         for _ in range(runs):
             exc()
             score()
-        ms_e, ms_s = kernel_ms('ensemble_exceedance', runs), kernel_ms('ensemble_score', runs)
+        ms_e, ms_s = kernel_ms(runs, 'ensemble_exceedance', 'ensemble_score')
         L.check(lib.dl4ds_profile_enable(0))
         read = (K + 1) * 4 * n
         result['kernel'].append(dict(K=K, T=T, sharp=sharp, n=n, exceedance_ms=round(ms_e, 4), read_tbs=round(read / ms_e / 1e9, 3),
