@@ -551,13 +551,11 @@ __global__ void __launch_bounds__(256) rec_tail_finish_kernel(const TailFinishPa
     }
 }
 
-bool rec_tail_staged(int HW) {
-    static const bool no_staged = exp_env("DL4DS_REC_TAIL_NO_STAGED") != nullptr;
-    return HW % 256 == 0 && !no_staged;
-}
+// the form is chosen once per op, when the graph is built (tests: DL4DS_REC_TAIL_NO_STAGED=1 keeps a 256-divisible grid on the plain kernels)
+bool rec_tail_staged(int HW) { return HW % 256 == 0 && !test_env("DL4DS_REC_TAIL_NO_STAGED"); }
 template <int CX, int CS, int CO>
-void launch_fwd(hipStream_t s, const TailParams& p) {
-    if (rec_tail_staged(p.HW)) {
+void launch_fwd(hipStream_t s, const TailParams& p, bool staged) {
+    if (staged) {
         DL4DS_LAUNCH((rec_tail_fwd_staged_kernel<CX, CS, CO>), dim3((unsigned)((size_t)p.B * p.HW / 256)), dim3(256), 0, s, p);
         HIP_CHECK(hipGetLastError());
         return;
@@ -567,8 +565,8 @@ void launch_fwd(hipStream_t s, const TailParams& p) {
     HIP_CHECK(hipGetLastError());
 }
 template <int CX, int CS, int CO>
-void launch_bwd(hipStream_t s, const TailBwdParams& p) {
-    if (rec_tail_staged(p.HW)) {
+void launch_bwd(hipStream_t s, const TailBwdParams& p, bool staged) {
+    if (staged) {
         const size_t lds = (size_t)256 * (CO + (CO + 2) + 2 * (CX + 4) + (CS + 4)) * sizeof(float);
         static bool attr = false;
         if (!attr) {
@@ -591,13 +589,14 @@ struct RecTailOp : GOp {
     int x, s, out, T;
     int wt, bt, wl, bl, w, b;
     int CX, CS, CO;
+    bool staged = false;
     RecTailOp() { kind = "rec_tail"; }
     size_t frames(Graph& g, int B) const { return (size_t)B * T; }
     // The non-staged kernels (grids whose point count is no multiple of 256) address rows with 32-bit byte offsets from a descriptor
     // based at the block's first sample: a block of 256 grid points spans at most 256 / HW + 2 samples.  Independent of the batch
     // size (the round-4 check bounded B T HW and also stopped the staged kernels, which index with size_t).
     void require_row_offsets_fit(int HW) const {
-        if (rec_tail_staged(HW)) return;
+        if (staged) return;
         const size_t span = (size_t)(256 / HW + 2) * T * HW * (size_t)(CO + 2) * 4;
         DL4DS_REQUIRE(span < (1ull << 31), "rec_tail: one sample's frames exceed 32-bit row offsets (DL4DS_NO_REC_TAIL_FUSION=1 builds the separate layers)");
     }
@@ -609,7 +608,7 @@ struct RecTailOp : GOp {
     size_t carve_floats(Graph& g, int B) const {
         const size_t HW = (size_t)g.tensors[out].H * g.tensors[out].W, CZ = CO + 2;
         auto up = [](size_t v) { return (v + 3) & ~(size_t)3; };
-        if (rec_tail_staged((int)HW))           // no dz / dzs: the weight gradients come out of the backward kernel as tiles
+        if (staged)           // no dz / dzs: the weight gradients come out of the backward kernel as tiles
             return up((size_t)B * HW * 4) + up((size_t)B * HW * 2) + (size_t)B * (HW / 256) * REC_TAIL_WTILE + (size_t)WSUM_GROUPS * REC_TAIL_WTILE;
         return up(frames(g, B) * HW * CZ) + up((size_t)B * HW * CZ) + up((size_t)B * HW * 4) + up((size_t)B * HW * 2) + up((size_t)CX * CZ) +
                up((size_t)CS * CZ) + up(2 * CZ) + up(CZ);
@@ -619,7 +618,7 @@ struct RecTailOp : GOp {
         auto up = [](size_t v) { return (v + 3) & ~(size_t)3; };
         Carve c = {};
         float* p = ws;
-        if (rec_tail_staged((int)HW)) {
+        if (staged) {
             c.pl = p; p += up((size_t)B * HW * 4);
             c.pb = p; p += up((size_t)B * HW * 2);
             c.wpart = p; p += (size_t)B * (HW / 256) * REC_TAIL_WTILE;
@@ -663,7 +662,7 @@ struct RecTailOp : GOp {
         require_row_offsets_fit(p.HW);
         const double px = (double)frames(g, B) * p.HW;
         ProfScope ps(g.stream, "rec_tail_fwd", 2.0 * px * ((CX + CS) * 2 + 4 + (CX + CS + 2) * CO), 4.0 * px * (CX + CO + 4) + 4.0 * B * p.HW * CS);
-#define X(A_, B_, C_) if (CX == A_ && CS == B_ && CO == C_) { launch_fwd<A_, B_, C_>(g.stream, p); return; }
+#define X(A_, B_, C_) if (CX == A_ && CS == B_ && CO == C_) { launch_fwd<A_, B_, C_>(g.stream, p, staged); return; }
         REC_TAIL_SHAPES(X)
 #undef X
         DL4DS_REQUIRE(false, "rec_tail: shape not built");
@@ -682,7 +681,6 @@ struct RecTailOp : GOp {
         p.u = saved + f_off * 2;
         const float* lws = saved + 2 * frames(g, c.B) * HW + f_off * 2;
         p.lws = lws;
-        const bool staged = rec_tail_staged(HW);
         require_row_offsets_fit(HW);
         p.y = to.data + f_off * CO; p.dy = to.grad + f_off * CO;
         p.wt = g.wp(wt); p.wl = g.wp(wl); p.w = g.wp(w);
@@ -698,7 +696,7 @@ struct RecTailOp : GOp {
             ProfScope ps(g.stream, "rec_tail_bwd", 2.0 * px * (2 * CO + 8 + (CX + CS) * (CO + 2) + (staged ? (CX + CS + 3) * CZ : 0)),
                          staged ? 4.0 * px * (CX * (p.want_dx ? 2 : 1) + 2 * CO + 4) + 4.0 * cnt * HW * (2 * CS + 6)
                                 : 4.0 * px * (CX * (p.want_dx ? 2 : 1) + 2 * CO + CZ + 2) + 4.0 * cnt * HW * (CZ + CS + 6));
-#define X(A_, B_, C_) if (CX == A_ && CS == B_ && CO == C_) launch_bwd<A_, B_, C_>(g.stream, p);
+#define X(A_, B_, C_) if (CX == A_ && CS == B_ && CO == C_) launch_bwd<A_, B_, C_>(g.stream, p, staged);
             REC_TAIL_SHAPES(X)
 #undef X
         }
@@ -758,6 +756,7 @@ int g_rec_tail(Graph& g, int x, int s, int wt, int bt, int wl, int bl, int w, in
     op->x = x; op->s = s; op->out = out; op->T = T;
     op->wt = wt; op->bt = bt; op->wl = wl; op->bl = bl; op->w = w; op->b = b;
     op->CX = tx.C; op->CS = ts.C; op->CO = CO;
+    op->staged = rec_tail_staged((int)HW);
     op->pids = {wt, bt, wl, bl, w, b};
     // (like a Concatenate, this op applies its inputs' ReLU masks to the gradients it writes: n_masking, not n_other)
     g.tensors[x].n_masking++;

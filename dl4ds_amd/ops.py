@@ -137,21 +137,29 @@ def conv2d_transpose(x, w, stride, relu=False):
     return y.numpy()
 
 
-def conv2d_transpose_dgrad(dz, w, stride):
+def conv2d_transpose_dgrad(dz, w, stride, accumulate=None):
+    """``accumulate``: an (N, H, W, Cin) array the gradient is added to (accumulate = 1 of the entry point)."""
     ks, _, cout, cin = w.shape
     n, h, wd = dz.shape[0], dz.shape[1] // stride, dz.shape[2] // stride
     ddz, dw = _d(dz), _d(w)
-    dx = DeviceArray.zeros((n, h, wd, cin))
-    _lib.check(_lib.lib().dl4ds_op_conv2d_transpose_dgrad(ddz.ptr, dw.ptr, dx.ptr, n, h, wd, cin, cout, ks, stride, 0))
+    if accumulate is not None:
+        assert accumulate.shape == (n, h, wd, cin)
+    dx = DeviceArray.zeros((n, h, wd, cin)) if accumulate is None else _d(accumulate)
+    _lib.check(_lib.lib().dl4ds_op_conv2d_transpose_dgrad(ddz.ptr, dw.ptr, dx.ptr, n, h, wd, cin, cout, ks, stride,
+                                                          int(accumulate is not None)))
     return dx.numpy()
 
 
-def conv2d_transpose_wgrad(x, dz, ks, stride):
+def conv2d_transpose_wgrad(x, dz, ks, stride, accumulate=None):
+    """``accumulate``: a (KS, KS, Cout, Cin) array the gradient is added to (accumulate = 1 of the entry point)."""
     n, h, wd, cin = x.shape
     cout = dz.shape[-1]
     dx, ddz = _d(x), _d(dz)
-    dw = DeviceArray.zeros((ks, ks, cout, cin))
-    _lib.check(_lib.lib().dl4ds_op_conv2d_transpose_wgrad(dx.ptr, ddz.ptr, dw.ptr, n, h, wd, cin, cout, ks, stride, 0))
+    if accumulate is not None:
+        assert accumulate.shape == (ks, ks, cout, cin)
+    dw = DeviceArray.zeros((ks, ks, cout, cin)) if accumulate is None else _d(accumulate)
+    _lib.check(_lib.lib().dl4ds_op_conv2d_transpose_wgrad(dx.ptr, ddz.ptr, dw.ptr, n, h, wd, cin, cout, ks, stride,
+                                                          int(accumulate is not None)))
     return dw.numpy()
 
 
