@@ -341,6 +341,66 @@ int dl4ds_op_conv2d_wgrad(const float* x, const float* dz, float* dw, int N, int
     conv2d_wgrad(S(), xv, dzv, KS, dw, accumulate, nullptr, 0, scratch(ws), ws);
     API_END
 }
+// ---- the same convolutions on the operand forms the graph passes: channel slices, frame views, channel-affine read views
+static TView desc_view(const dl4ds_view* d, int N, int H, int W, bool affine_allowed, const char* what) {
+    DL4DS_REQUIRE(d && d->p, std::string(what) + ": view without a base pointer");
+    DL4DS_REQUIRE(d->C >= 1 && (d->ld == 0 || d->ld >= (d->d2s > 1 ? d->C / (d->d2s * d->d2s) : d->C)), std::string(what) + ": pitch below the channel count");
+    DL4DS_REQUIRE(affine_allowed || (!d->sc && !d->sh), std::string(what) + ": only a read operand (x; dz of a weight gradient) takes a channel affine");
+    DL4DS_REQUIRE(d->sc || !d->sh, std::string(what) + ": a shift needs a scale");
+    TView v;
+    if (d->d2s > 1) {
+        DL4DS_REQUIRE(d->C % (d->d2s * d->d2s) == 0, std::string(what) + ": depth_to_space needs C % r^2 == 0");
+        v = make_view_d2s(nc(d->p), N, H, W, d->C, d->d2s);
+        if (d->ld) { v.ld = d->ld; v.vec = v.vec && (d->ld & 3) == 0; }
+        v.nstride = d->nstride ? d->nstride : (size_t)H * d->d2s * W * d->d2s * v.ld;
+    } else {
+        const int ld = d->ld ? d->ld : d->C;
+        v = make_pitched_view(nc(d->p), N, H, W, d->C, ld, d->nstride ? d->nstride : (size_t)H * W * ld);
+    }
+    v.sc = d->sc; v.sh = d->sh;
+    return v;
+}
+int dl4ds_op_conv2d_views(const dl4ds_view* x, const float* w, const float* b, const dl4ds_view* add, const dl4ds_view* mask,
+                          const dl4ds_view* y, int N, int H, int W, int KS, int relu, int accumulate, int dgrad) {
+    API_BEGIN
+    const TView in = desc_view(x, N, H, W, true, "conv2d_views x");
+    const TView out = desc_view(y, N, H, W, false, "conv2d_views y");
+    ConvEpilogue ep;
+    ep.bias = b;
+    if (add) ep.add = desc_view(add, N, H, W, false, "conv2d_views add");
+    if (mask) ep.mask = desc_view(mask, N, H, W, false, "conv2d_views mask");
+    DL4DS_REQUIRE((!add || add->C == y->C) && (!mask || mask->C == y->C), "conv2d_views: add / mask have the output's channels");
+    ep.relu = relu;
+    ep.accumulate = accumulate;
+    const float* filt = w;
+    if (dgrad) {                 // w: the forward layer's [KS][KS][y.C][x.C] filter; the dgrad runs on its flipped transpose
+        float* wt = scratch((size_t)KS * KS * in.C * out.C * sizeof(float));
+        conv2d_dgrad_weights(S(), w, wt, KS, out.C, in.C);
+        filt = wt;
+    }
+    conv2d_forward(S(), in, filt, KS, out, ep);
+    API_END
+}
+int dl4ds_op_conv2d_wgrad_views(const dl4ds_view* x, const dl4ds_view* dz, float* dw, int N, int H, int W, int KS, int accumulate,
+                                float* db, int accumulate_db) {
+    API_BEGIN
+    const TView xv = desc_view(x, N, H, W, true, "conv2d_wgrad_views x");
+    const TView dzv = desc_view(dz, N, H, W, true, "conv2d_wgrad_views dz");
+    const size_t ws = conv2d_wgrad_workspace_bytes(xv, dzv, KS);
+    conv2d_wgrad(S(), xv, dzv, KS, dw, accumulate, db, accumulate_db, scratch(ws), ws);
+    API_END
+}
+int dl4ds_op_conv2d_wgrad_attention(const dl4ds_view* x, const dl4ds_view* dz, const float* scale, const float* w, float* dw, int N, int H,
+                                    int W, int KS, int accumulate, float* db, int accumulate_db, float* ds, int* launched) {
+    API_BEGIN
+    DL4DS_REQUIRE(launched != nullptr && scale && w && dw && ds, "conv2d_wgrad_attention: null operand");
+    const TView xv = desc_view(x, N, H, W, false, "conv2d_wgrad_attention x");
+    const TView dzv = desc_view(dz, N, H, W, false, "conv2d_wgrad_attention dz");
+    // (N * bpi + N) slabs with bpi <= 1024 / N blocks per image (conv_direct.hip)
+    const size_t ws = (size_t)(1024 + N) * ((size_t)KS * KS * xv.C * dzv.C + dzv.C) * sizeof(float);
+    *launched = conv2d_direct_wgrad_attention(S(), xv, dzv, KS, scale, w, dw, accumulate, db, accumulate_db, ds, scratch(ws), ws) ? 1 : 0;
+    API_END
+}
 int dl4ds_op_bias_act_bwd(float* dy, const float* y, float* db, int N, int H, int W, int C) {
     API_BEGIN
     TView dyv = make_view(dy, N, H, W, C);

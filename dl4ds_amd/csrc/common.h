@@ -77,6 +77,16 @@ __host__ __device__ inline TView make_view(float* p, int N, int H, int W, int C)
     return v;
 }
 
+// channel slice / frame view: C channels at pitch ld (>= C) with images nstride floats apart.  The ONE rule for `vec` on such views
+// (Graph::view and the dl4ds_op_conv2d*_views entry points both come here): float4 access needs C, the pitch and the base to allow it
+__host__ __device__ inline TView make_pitched_view(float* p, int N, int H, int W, int C, int ld, size_t nstride) {
+    TView v = make_view(p, N, H, W, C);
+    v.ld = ld;
+    v.nstride = nstride;
+    v.vec = v.vec && (ld & 3) == 0;
+    return v;
+}
+
 // view whose memory is the depth_to_space(r) image of the logical (N,H,W,C) tensor
 __host__ __device__ inline TView make_view_d2s(float* p, int N, int H, int W, int C, int r) {
     TView v;

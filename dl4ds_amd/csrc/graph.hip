@@ -171,11 +171,7 @@ TView Graph::view(int tid, int B, bool grad, int b_off, int b_cnt) const {
     const int cnt = (b_cnt < 0) ? B : b_cnt;
     if ((!grad || t.galias) && t.alias_of >= 0) {
         const size_t img = (size_t)t.H * t.W * t.alias_ld;
-        TView v = make_view(base + (size_t)b_off * t.nmul * img, cnt * t.nmul, t.H, t.W, t.C);
-        v.ld = t.alias_ld;
-        v.nstride = img;
-        v.vec = v.vec && (t.alias_ld & 3) == 0;
-        return v;
+        return make_pitched_view(base + (size_t)b_off * t.nmul * img, cnt * t.nmul, t.H, t.W, t.C, t.alias_ld, img);
     }
     return make_view(base + (size_t)b_off * t.per_sample(), cnt * t.nmul, t.H, t.W, t.C);
 }

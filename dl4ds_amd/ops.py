@@ -466,3 +466,106 @@ def arena_swap(a, b):
     assert da.shape == db.shape
     _lib.check(_lib.lib().dl4ds_op_arena_swap(da.ptr, db.ptr, da.shape[0]))
     return da.numpy().reshape(np.shape(a)), db.numpy().reshape(np.shape(b))
+
+
+# ---- convolutions on the operand forms the graph passes (dl4ds_op_conv2d_views, dl4ds_op_conv2d_wgrad_views) ---------------------
+class _ViewDesc(ctypes.Structure):
+    _fields_ = [('p', ctypes.c_void_p), ('C', ctypes.c_int), ('ld', ctypes.c_int), ('d2s', ctypes.c_int), ('nstride', ctypes.c_size_t),
+                ('sc', ctypes.c_void_p), ('sh', ctypes.c_void_p)]
+
+
+SLACK = 256          # floats allocated (and uploaded) behind every view buffer, as the graph's slabs leave room behind a tensor
+
+
+def slack_values(n=SLACK):
+    return (np.arange(n, dtype=np.float32) * 0.37 - 41.0).astype(np.float32)
+
+
+class View:
+    """One operand of conv2d_views / conv2d_wgrad_views: ``C`` channels from channel ``coff`` on of the float32 buffer ``buf`` --
+    (N, H, W, ld), or (B, T, H, W, ld) with frame ``t`` of every sample; with ``d2s`` = r the buffer holds depth_to_space(r) of the
+    logical tensor, (N, H*r, W*r, ld) with C / r^2 of the ld channels.  ``sc`` / ``sh``: (N, C) per-image channel affine."""
+
+    def __init__(self, buf, C=None, coff=0, t=None, d2s=0, sc=None, sh=None):
+        self.buf = np.ascontiguousarray(buf, np.float32)
+        assert self.buf.ndim == (5 if t is not None else 4)
+        r2 = d2s * d2s if d2s > 1 else 1
+        self.ld = self.buf.shape[-1]
+        self.C = int(C) if C is not None else self.ld * r2
+        self.coff, self.t, self.d2s, self.sc, self.sh = int(coff), t, int(d2s), sc, sh
+        assert self.coff + self.C // r2 <= self.ld
+
+    def upload(self, keep):
+        img = int(np.prod(self.buf.shape[-3:]))
+        dev = DeviceArray((self.buf.size + SLACK,))
+        dev.upload(self.buf.reshape(-1))
+        dev.upload(slack_values(), self.buf.size)
+        keep.append(dev)
+        d = _ViewDesc()
+        d.p = dev.ptr + 4 * ((0 if self.t is None else self.t * img) + self.coff)
+        d.C, d.ld, d.d2s = self.C, self.ld, self.d2s
+        d.nstride = 0 if self.t is None else self.buf.shape[1] * img
+        for name in ('sc', 'sh'):
+            a = getattr(self, name)
+            if a is not None:
+                keep.append(_d(np.asarray(a, np.float32).reshape(-1)))
+            setattr(d, name, None if a is None else keep[-1].ptr)
+        self._dev = dev
+        return d
+
+    def download(self):
+        """-> (the whole buffer as the device holds it now, the slack behind it)"""
+        flat = self._dev.numpy()
+        return flat[:self.buf.size].reshape(self.buf.shape), flat[self.buf.size:]
+
+
+def _run_views(call, views):
+    """Uploads every view's WHOLE buffer, runs ``call(descriptors)``, downloads every buffer again -> {name: (buffer, slack)}; a
+    refused call raises Dl4dsHipError carrying the same dict as ``.buffers``."""
+    keep = []
+    descs = {k: (None if v is None else v.upload(keep)) for k, v in views.items()}
+    try:
+        _lib.check(call({k: (None if d is None else ctypes.byref(d)) for k, d in descs.items()}))
+    except _lib.Dl4dsHipError as e:
+        e.buffers = {k: v.download() for k, v in views.items() if v is not None}
+        raise
+    return {k: v.download() for k, v in views.items() if v is not None}
+
+
+def conv2d_views(x, w, y, b=None, add=None, mask=None, relu=False, accumulate=False, dgrad=False):
+    """y = [y +] where(mask > 0, [relu](conv_same(x, w) + b + add), 0) with every activation operand a ``View``; ``dgrad``: w is the
+    forward layer's (KS, KS, y.C, x.C) filter.  -> {'x' | 'y' | 'add' | 'mask': (whole buffer after the call, slack)}."""
+    n, h, wd = (y.buf.shape[0],) + tuple(s // max(y.d2s, 1) for s in y.buf.shape[-3:-1])
+    ks = w.shape[0]
+    assert w.shape[2:] == ((y.C, x.C) if dgrad else (x.C, y.C)), (w.shape, x.C, y.C)
+    dw, db = _d(w), _d(b)
+    return _run_views(lambda d: _lib.lib().dl4ds_op_conv2d_views(d['x'], dw.ptr, _p(db), d['add'], d['mask'], d['y'], n, h, wd, ks,
+                                                                 int(relu), int(accumulate), int(dgrad)),
+                      dict(x=x, y=y, add=add, mask=mask))
+
+
+def conv2d_wgrad_views(x, dz, ks, dw0=None, db0=None, want_db=True):
+    """-> (dw, db or None, {'x' | 'dz': (buffer, slack)}).  dw0 / db0: arrays the gradients are ADDED to (accumulate /
+    accumulate_db = 1, independently); otherwise the outputs start from CANARY and must be overwritten."""
+    n, h, wd = (x.buf.shape[0],) + x.buf.shape[-3:-1]
+    cin, cout = x.C, dz.C
+    dw = _d(np.full((ks, ks, cin, cout), CANARY, np.float32) if dw0 is None else dw0)
+    db = None if not want_db else _d(np.full((cout,), CANARY, np.float32) if db0 is None else db0)
+    bufs = _run_views(lambda d: _lib.lib().dl4ds_op_conv2d_wgrad_views(d['x'], d['dz'], dw.ptr, n, h, wd, ks, int(dw0 is not None),
+                                                                       _p(db), int(db0 is not None)), dict(x=x, dz=dz))
+    return dw.numpy(), _np(db), bufs
+
+
+def conv2d_wgrad_attention(x, dz, scale, w, dw0=None, db0=None):
+    """-> (dw, db, ds, launched) of dl4ds_op_conv2d_wgrad_attention: x the RAW input view, scale (N, Cin), w (KS, KS, Cin, Cout)."""
+    n, h, wd = (x.buf.shape[0],) + x.buf.shape[-3:-1]
+    ks, _, cin, cout = w.shape
+    dw = _d(np.full(w.shape, CANARY, np.float32) if dw0 is None else dw0)
+    db = _d(np.full((cout,), CANARY, np.float32) if db0 is None else db0)
+    ds = _d(np.full((n, cin), CANARY, np.float32))
+    dsc, dwt = _d(np.asarray(scale, np.float32).reshape(-1)), _d(w)
+    ok = ctypes.c_int(0)
+    _run_views(lambda d: _lib.lib().dl4ds_op_conv2d_wgrad_attention(d['x'], d['dz'], dsc.ptr, dwt.ptr, dw.ptr, n, h, wd, ks,
+                                                                    int(dw0 is not None), db.ptr, int(db0 is not None), ds.ptr,
+                                                                    ctypes.byref(ok)), dict(x=x, dz=dz))
+    return dw.numpy(), db.numpy(), ds.numpy(), bool(ok.value)

@@ -100,6 +100,38 @@ int dl4ds_op_conv2d_dgrad(const float* dz_dev, const float* w_dev, float* dx_dev
 /* dw (+)= wgrad(x, dz) */
 int dl4ds_op_conv2d_wgrad(const float* x_dev, const float* dz_dev, float* dw_dev, int N, int H, int W,
                           int Cin, int Cout, int KS, int d2s_r, int accumulate);
+/* One operand of a convolution as the train graph passes it (csrc/common.h: TView): `C` logical channels at a pitch of `ld` floats
+ * per pixel (0: dense, ld = C; > C: a channel slice of a wider buffer, p already at the slice's first channel -- the outputs and
+ * inputs that live inside a Concatenate's buffer, blocks.py:228 / sp_preups.py:262-285), images `nstride` floats apart (0:
+ * contiguous; T*H*W*C: frame t of every sample of a (B,T,H,W,C) buffer, p already at frame t -- the TimeDistributed layers of
+ * spt_postups.py:152-157), d2s > 1: the memory holds tf.nn.depth_to_space(d2s) of the logical tensor (blocks.py:427), sc / sh
+ * (read operands only, may be NULL; sh needs sc): per-image channel affine, logical value = mem * sc[n*C + c] + sh[n*C + c] inside
+ * the image, zero padding outside -- ChannelAttention2D's broadcast scale (blocks.py:585-593) and its backward carried in the
+ * neighbouring convolution's loads.  float4 access is decided by the same rule as for the graph's own views. */
+typedef struct dl4ds_view {
+    const float* p;
+    int C, ld, d2s;
+    size_t nstride;
+    const float* sc;
+    const float* sh;
+} dl4ds_view;
+/* dl4ds_op_conv2d_epilogue on such views: y = [y_old +] mask_gt0( [relu]( conv_same_s1(x,w) + b + add ), mask ) with x, add, mask
+ * read and y written through their descriptors (Conv2D + Add + Activation, blocks.py:49-75,228).  dgrad != 0: w is the FORWARD
+ * layer's [KS][KS][y.C][x.C] filter and the call is that layer's input gradient (x = dz).  A view form the kernels cannot take
+ * (a channel affine outside the stencil / narrow-pair kernels) is an error, never ignored. */
+int dl4ds_op_conv2d_views(const dl4ds_view* x, const float* w_dev, const float* b_dev, const dl4ds_view* add, const dl4ds_view* mask,
+                          const dl4ds_view* y, int N, int H, int W, int KS, int relu, int accumulate, int dgrad);
+/* dw (+)= wgrad(x, dz) and, with db_dev, db (+)= sum_pixels dz (the bias gradient of Conv2D(use_bias=True), blocks.py:49-61, which
+ * every weight-gradient kernel family produces on the side); accumulate and accumulate_db are independent. */
+int dl4ds_op_conv2d_wgrad_views(const dl4ds_view* x, const dl4ds_view* dz, float* dw_dev, int N, int H, int W, int KS, int accumulate,
+                                float* db_dev, int accumulate_db);
+/* Weight gradient of a stencil convolution that reads its input through ChannelAttention2D's scale, y = conv(x * scale[n, ci])
+ * (blocks.py:585-593), together with the attention's d(loss)/d(scale): dw (+)= wgrad(x * scale, dz), db (+)= sum dz (db_dev may be
+ * NULL), ds[n, ci] = sum_p x[n,p,ci] * dgrad(dz, w)[n,p,ci].  x is the RAW input.  *launched = 0: the layer is not one the stencil
+ * kernels take, nothing was written. */
+int dl4ds_op_conv2d_wgrad_attention(const dl4ds_view* x, const dl4ds_view* dz, const float* scale_dev, const float* w_dev, float* dw_dev,
+                                    int N, int H, int W, int KS, int accumulate, float* db_dev, int accumulate_db, float* ds_dev,
+                                    int* launched);
 /* dz = dy * [y>0] (if y_dev) in place over dy; db = sum_pixels dz (if db_dev) */
 int dl4ds_op_bias_act_bwd(float* dy_dev, const float* y_dev, float* db_dev, int N, int H, int W, int C);
 /* Conv2DTranspose(k=KS, stride, 'same', use_bias=False) -- blocks.py:508-516; kernel HWOI */
