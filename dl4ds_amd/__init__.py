@@ -43,6 +43,7 @@ def __getattr__(name):
             'neighbourhood_ensemble_scores': '.metrics', 'verify_neighbourhood': '.inference',
             'NeighbourhoodVerifier': '.inference',
             'sal_from_objects': '.objects', 'check_object_args': '.objects',
+            'label_objects': '.objects', 'sal_scores': '.objects', 'object_scores': '.objects',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'QuantileMapper': '.postprocessing', 'quantile_map': '.postprocessing', 'check_qmap_args': '.postprocessing',

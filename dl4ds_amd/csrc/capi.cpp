@@ -66,6 +66,9 @@ void device_error_check(const char* what) {
         msg += ": the persistent ConvLSTM kernel gave up waiting for a neighbouring tile (its workgroups were not all resident, "
                "e.g. behind kernels of another stream or an RCCL collective held up by a late rank); the activations and "
                "gradients of that step are INVALID.  DL4DS_NO_CONVLSTM_SEQ=1 runs the recurrence step by step";
+    if (code & DEV_ERR_OBJECTS_WALK)
+        msg += ": a parent walk of the object labelling passed the bound its field size sets (a link that points upwards or out "
+               "of the field); the outputs of that call are INVALID";
     throw Dl4dsError(msg);
 }
 
@@ -803,6 +806,23 @@ int dl4ds_ensemble_fss(const float* members_dev, size_t K, size_t n, size_t memb
     const size_t ws = ensemble_fss_workspace_bytes(K, B, H, W, C, T);
     ensemble_fss(S(), members_dev, K, n, member_stride, obs_dev, B, H, W, C, thresholds_host, T, windows_host, n_windows, sums_dev, cont_dev,
                  valid_dev, ws ? scratch(ws) : nullptr, ws);
+    API_END
+}
+int dl4ds_label_objects(const float* x_dev, int N, int H, int W, int C, const float* thr_dev, int connectivity, int cap,
+                        int* labels_dev, int* count_dev, long long* nvalid_dev, double* field_sums_dev, long long* sums_dev,
+                        int* bbox_dev, int* first_dev, float* vmax_dev, double* mass_dev) {
+    API_BEGIN
+    objects_check_args(x_dev, N, H, W, C, thr_dev, connectivity, cap, count_dev, sums_dev, bbox_dev, first_dev, vmax_dev,
+                       mass_dev);                                                    // before the workspace is sized
+    const size_t ws = objects_workspace_bytes(N, H, W, C);
+    label_objects(S(), x_dev, N, H, W, C, thr_dev, connectivity, cap, labels_dev, count_dev, nvalid_dev, field_sums_dev, sums_dev,
+                  bbox_dev, first_dev, vmax_dev, mass_dev, scratch(ws), ws, device_error_word());
+    API_END
+}
+int dl4ds_object_thresholds(const float* x_dev, int N, int H, int W, int C, double factor, float* thr_dev) {
+    API_BEGIN
+    const size_t ws = object_thresholds_workspace_bytes(N, H, W, C);
+    object_thresholds(S(), x_dev, N, H, W, C, factor, thr_dev, ws ? scratch(ws) : nullptr, ws);
     API_END
 }
 int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, size_t L, size_t seg_stride, size_t elem_stride,

@@ -227,6 +227,20 @@ void ensemble_fss_check_args(const float* members, size_t K, size_t n, size_t me
 void ensemble_fss(hipStream_t s, const float* members, size_t K, size_t n, size_t member_stride, const float* obs, size_t B, int H,
                   int W, int C, const float* thresholds, int T, const int* windows, int S, long long* sums, long long* cont,
                   long long* valid, void* workspace, size_t workspace_bytes);
+// Object labelling (objects.hip) of the N*C fields of x (N, H, W, C) at one device threshold per field:
+// labels [F][H][W] (or null), count [F], nvalid [F], field_sums [F][3], and tables of cap rows per field: sums [F][cap][6], bbox
+// [F][cap][4], first [F][cap], vmax [F][cap], mass [F][cap][3] (null when cap == 0).  Outputs are overwritten.  err: the sticky
+// device error word (runtime.h), raised if a parent walk passes its bound.  objects_check_args throws on a request the entry
+// refuses (before the workspace is sized).  object_thresholds: thr [F] = float32(factor * max of the finite cells), 0 without one.
+size_t objects_workspace_bytes(int N, int H, int W, int C);
+void objects_check_args(const float* x, int N, int H, int W, int C, const float* thr, int connectivity, int cap, const int* count,
+                        const long long* sums, const int* bbox, const int* first, const float* vmax, const double* mass);
+void label_objects(hipStream_t s, const float* x, int N, int H, int W, int C, const float* thr, int connectivity, int cap, int* labels,
+                   int* count, long long* nvalid, double* field_sums, long long* sums, int* bbox, int* first, float* vmax,
+                   double* mass, void* workspace, size_t workspace_bytes, unsigned* err);
+size_t object_thresholds_workspace_bytes(int N, int H, int W, int C);
+void object_thresholds(hipStream_t s, const float* x, int N, int H, int W, int C, double factor, float* thr, void* workspace,
+                       size_t workspace_bytes);
 // Distribution verification (distribution.hip) of S pairs of length-L segments, element k of segment s at [s*seg_stride +
 // k*elem_stride]: per segment quant [S][2][Q] (numpy 'linear' quantiles of the valid values of y, p), w1 [S] (1-Wasserstein), ks [S]
 // (n times the two-sample KS statistic), hist [S][2][E-1] (np.histogram over the E edges; may be null when E == 0), valid [S] (n).

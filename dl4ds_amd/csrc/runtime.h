@@ -21,7 +21,7 @@ void set_last_error(const std::string& s);
 // moments untouched when it is set (the gradients of that step are invalid), so a caller that catches the exception continues
 // from the state before the failed step.  In a multi-rank job the raising rank throws out of its step and the launcher tears the
 // job down (bench.py / parallel.py propagate a rank's failure); peers blocked in a collective end at the communicator watchdog.
-enum : unsigned { DEV_ERR_CONVLSTM_SEQ_TIMEOUT = 1u };
+enum : unsigned { DEV_ERR_CONVLSTM_SEQ_TIMEOUT = 1u, DEV_ERR_OBJECTS_WALK = 2u };   // (objects.hip: a parent walk passed its bound)
 unsigned* device_error_word();
 unsigned* device_error_word_if_any();     // nullptr until some op has asked for the word (Adam skips its update when it is set)
 void device_error_check(const char* what);

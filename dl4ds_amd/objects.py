@@ -3,12 +3,15 @@ into the connected objects of its cells at or above a threshold, and the objects
 compared.  This module holds what follows from a labelling's per-object sums: `object_attributes` (area, centroid, mass, maximum,
 bounding box, orientation, aspect), `sal_from_objects` (Structure, Amplitude, Location of Wernli et al. 2008),
 `object_scores_from_objects` (attribute summary), SAL's `factor_thresholds` and the argument rules `check_object_args`.  The
-labelling itself is not in the library yet: tests/objects_ref.py is its sequential restatement.  Matching of observed and
+labelling itself runs on the device (`dl4ds_label_objects`, csrc/objects.hip; tests/objects_ref.py is its sequential restatement):
+`label_objects`, and on top of it `sal_scores` and `object_scores` for an observation and a prediction.  Matching of observed and
 predicted objects is not done here."""
+import ctypes
+
 import numpy as np
 
 from . import _exact
-from ._chunks import check_4d_shape, check_batch_size, is_int
+from ._chunks import as_4d, check_4d_shape, check_batch_size, is_device, is_int, masked, paired_chunks
 
 OBJECTS_DEFAULT_CAP = 4096
 OBJECTS_CELL_BOUND = (1 << 31) - 1                 # H*W must stay below it (int32 cell indices, -1 is background)
@@ -206,4 +209,129 @@ def object_scores_from_objects(obs_objs, pred_objs, hw):
         mv = lambda s: np.where(s['count'] > 0, np.nansum(s['vmax'], -1) / np.maximum(s['count'], 1), np.nan)
         vo, vp = mv(o), mv(p)
         res['mean_vmax_ratio'] = np.where(vo == 0, np.nan, vp / np.where(vo == 0, 1.0, vo))
+    return res
+
+
+def _raw_tables(F, cap, hw, labels):
+    """host arrays of a labelling's outputs in the order of the library call, `labels` first (None when not wanted)"""
+    H, W = hw
+    return [np.zeros((F, H, W), np.int32) if labels else None, np.zeros(F, np.int32), np.zeros(F, np.int64), np.zeros((F, 3)),
+            np.zeros((F, cap, 6), np.int64), np.zeros((F, cap, 4), np.int32), np.zeros((F, cap), np.int32),
+            np.zeros((F, cap), np.float32), np.zeros((F, cap, 3))]
+
+
+def _label(x, shape, thr, factor, connectivity, cap, batch_size, labels):
+    """The library calls of one labelling: ``x`` a float32 DeviceArray, used where it lies, or a host array, which goes up in
+    chunks of whole samples.  ``thr``: float32 (N*C,), or None for ``factor`` times each field's largest finite value, taken on the
+    device.  -> (the outputs under `object_attributes`' names, the thresholds)."""
+    from . import _lib
+    from .device import Buffers, sync
+    N, H, W, C = shape
+    F = N * C
+    lib = _lib.lib()
+    host = _raw_tables(F, cap, (H, W), labels)
+    thr_out = np.zeros(F, np.float32)
+    if thr is not None:
+        thr = np.ascontiguousarray(thr, np.float32)
+
+    def call(b, dx, dthr, outs):
+        if thr is None:
+            _lib.check(lib.dl4ds_object_thresholds(dx, b, H, W, C, ctypes.c_double(factor), dthr))
+        _lib.check(lib.dl4ds_label_objects(dx, b, H, W, C, dthr, connectivity, cap, *outs))
+        sync()                                                             # (reports a device-side error of the call)
+
+    if is_device(x):
+        with Buffers() as buf:
+            dthr = buf.alloc((F,))
+            if thr is not None:
+                dthr.upload(thr)
+            devs = [buf.alloc(h.shape, h.dtype) if h is not None else None for h in host]
+            call(N, x.ptr, dthr.ptr, [d.ptr if d is not None else None for d in devs])
+            for h, d in zip(host + [thr_out], devs + [dthr]):
+                if h is not None and h.nbytes:
+                    d.download(h)
+    else:
+        done = [0]                                                         # samples labelled so far: chunks run in ascending order
+        outputs = [thr_out] + [h for h in host if h is not None]
+
+        def chunk(b, dx, _, dthr, *outs):
+            if thr is not None:
+                _lib.check(lib.dl4ds_memcpy_h2d(dthr, thr[done[0] * C:(done[0] + b) * C].ctypes.data, 4 * b * C))
+            call(b, dx, dthr, ([] if labels else [None]) + list(outs))
+            done[0] += b
+        paired_chunks(x, None, outputs, chunk, batch_size)
+    names = ('labels', 'count', 'nvalid', 'field_sums', 'sums', 'bbox', 'first', 'vmax', 'mass')
+    return {k: h for k, h in zip(names, host) if h is not None}, thr_out
+
+
+def _checked(x, name, threshold, factor, connectivity, cap, batch_size, mask):
+    """every refusal of a labelling request, without a library call -> (x as it goes to `_label`, shape, thr or None, factor, cap)"""
+    x, shape = as_4d(x, name)
+    if mask is not None and is_device(x):
+        masked(x, mask)                                                   # (raises: a DeviceArray cannot take one)
+    if (threshold is None) == (factor is None):
+        raise ValueError('exactly one of `threshold` and `factor` must be given')
+    thr, cap = check_object_args(shape, threshold, connectivity, cap, batch_size)
+    if factor is not None:
+        factor = _check_factor(factor)
+    return masked(x, mask), check_4d_shape(shape), thr, factor, cap
+
+
+def _attributes(raw, shape, thr, connectivity, cap):
+    """`object_attributes` of tables of ``cap`` rows: objects beyond ``cap`` are left out, ``count`` stays true, ``truncated`` says
+    whether any field had more"""
+    count = raw['count']
+    res = object_attributes(dict(raw, count=np.minimum(count, cap)), shape, thr, connectivity)
+    res['count'] = count.reshape(shape[0], shape[3])
+    res['truncated'] = bool((count > cap).any())
+    return res
+
+
+def label_objects(x, threshold=None, factor=None, connectivity=1, cap=None, batch_size=None, mask=None, return_labels=True):
+    """Labels the objects of every field of ``x`` (N, H, W, C) on the device: the connected sets (``connectivity``
+    1: 4 neighbours, 2: 8) of finite cells at or above ``threshold`` (a scalar or one value per field) or, with ``factor``, above
+    ``factor`` times the field's largest finite value.  ``x``: a host array of any dtype, read as float32 and uploaded in chunks of
+    ``batch_size`` whole samples, or a float32 DeviceArray, used where it lies.  ``mask`` (host arrays only; 0 = excluded) sets
+    cells to NaN.  ``cap``: rows of the per-object tables (default 4096); objects beyond it are left out of the attributes and keep
+    their labels.  -> the dict of `object_attributes`, with ``labels`` (N, C, H, W) unless ``return_labels`` is False, ``count``
+    true also beyond ``cap`` and ``truncated`` = whether any field's count exceeds ``cap``."""
+    x, shape, thr, factor, cap = _checked(x, 'x', threshold, factor, connectivity, cap, batch_size, mask)
+    raw, thr = _label(x, shape, thr, factor, int(connectivity), cap, batch_size, bool(return_labels))
+    return _attributes(raw, shape, thr, int(connectivity), cap)
+
+
+def _both_sides(obs, pred, threshold, factor, connectivity, cap, batch_size, mask):
+    obs, shape = as_4d(obs, 'obs')
+    pred, pshape = as_4d(pred, 'pred')
+    if tuple(shape) != tuple(pshape):
+        raise ValueError(f'`obs` and `pred` must have one shape, got {tuple(shape)} and {tuple(pshape)}')
+    sides = [_checked(a, name, threshold, factor, connectivity, cap, batch_size, mask) for a, name in ((obs, 'obs'), (pred, 'pred'))]
+    out = []
+    for a, shape, thr, factor, cap in sides:                               # (both sides checked before the first library call)
+        raw, thr = _label(a, shape, thr, factor, int(connectivity), cap, batch_size, False)
+        out.append(_attributes(raw, shape, thr, int(connectivity), cap))
+    return out[0], out[1], shape
+
+
+def sal_scores(obs, pred, threshold=None, factor=SAL_DEFAULT_FACTOR, connectivity=1, cap=None, batch_size=None, mask=None):
+    """SAL (`sal_from_objects`) of a prediction against an observation, both (N, H, W, C), host arrays or float32 DeviceArrays,
+    labelled on the device as by `label_objects` (labels are not downloaded).  With ``factor`` (the default, 1/15: Wernli et al.
+    2008) each side gets its own thresholds, ``factor`` times each field's largest finite value; pass ``threshold`` and
+    ``factor=None`` for fixed ones.  ``mask`` applies to both sides.  Also in the result: ``n_objects_obs`` / ``n_objects_pred``
+    (N, C), ``thresholds_obs`` / ``thresholds_pred`` (N, C) and ``truncated`` (a side had more than ``cap`` objects in a field)."""
+    if threshold is not None and factor == SAL_DEFAULT_FACTOR:
+        factor = None                                                      # (a threshold replaces the default factor)
+    o, p, shape = _both_sides(obs, pred, threshold, factor, connectivity, cap, batch_size, mask)
+    res = sal_from_objects(o, p, shape[1:3])
+    res.update(n_objects_obs=o['count'], n_objects_pred=p['count'], thresholds_obs=o['thresholds'], thresholds_pred=p['thresholds'],
+               truncated=o['truncated'] or p['truncated'])
+    return res
+
+
+def object_scores(obs, pred, threshold, connectivity=1, cap=None, batch_size=None, mask=None):
+    """The attribute summary (`object_scores_from_objects`) of a prediction against an observation at one ``threshold`` (a scalar
+    or one value per field) for both sides, labelled on the device as by `label_objects`; ``truncated`` as in `sal_scores`."""
+    o, p, shape = _both_sides(obs, pred, threshold, None, connectivity, cap, batch_size, mask)
+    res = object_scores_from_objects(o, p, shape[1:3])
+    res['truncated'] = o['truncated'] or p['truncated']
     return res

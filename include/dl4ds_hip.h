@@ -392,6 +392,35 @@ int dl4ds_fss(const float* y_dev, const float* p_dev, int N, int H, int W, int C
 int dl4ds_ensemble_fss(const float* members_dev, size_t K, size_t n, size_t member_stride, const float* obs_dev, size_t B, int H,
                        int W, int C, const float* thresholds_host, int T, const int* windows_host, int S, long long* sums_dev,
                        long long* cont_dev, long long* valid_dev);
+/* Object labelling for object-based verification (SAL, object attributes): every field is cut into the connected objects of its
+ * cells at or above a threshold.  The reference has no such metric; the definitions are DESIGN.md section 27.  x_dev: (N, H, W, C)
+ * fp32, each of the F = N*C planes one field (f = n*C + c), read in place with stride C.  thr_dev [F]: one DEVICE threshold per
+ * field.  A cell is VALID iff finite, an EVENT iff valid and x >= thr on float32 (-0.0 >= 0.0 holds); a field whose threshold is
+ * not finite has no event.  connectivity 1 (4 neighbours) or 2 (8 neighbours), fields do not wrap.  Every output given is
+ * overwritten; labels_dev, nvalid_dev and field_sums_dev may be null, the five tables may be null when cap == 0:
+ *   labels_dev     [F][H][W]    0 background, objects 1 ... count in raster order of their first cell (scipy.ndimage.label)
+ *   count_dev      [F]          number of objects, also when it exceeds cap
+ *   nvalid_dev     [F]          number of valid cells;  field_sums_dev [F][3]  fp64 sum v, sum v*i, sum v*j over the valid cells
+ *   sums_dev       [F][cap][6]  area, sum i, sum j, sum i*i, sum j*j, sum i*j of object r + 1 (exact 64-bit integers)
+ *   bbox_dev       [F][cap][4]  min i, max i, min j, max j;  first_dev [F][cap]  the object's smallest cell index i*W + j
+ *   vmax_dev       [F][cap]     the object's largest value (exact, +0.0 above -0.0)
+ *   mass_dev       [F][cap][3]  fp64 sum v, sum v*i, sum v*j over the object's cells, every term exact
+ * Rows count ... cap are zero; objects beyond cap are left out of the tables and keep their labels.  Labels, every integer output
+ * and vmax are pure functions of the input; field_sums_dev has one fixed summation order (no float atomics) and gives the same
+ * bits every call; mass_dev is accumulated with fp64 atomic adds and may differ in the last bits between calls, within
+ * gamma_(n-1) * sum |term| of the exact sum of the object's n terms.  No workgroup waits for another and every loop is bounded by
+ * the field size; a parent walk that passed its bound would raise the sticky device error that dl4ds_sync reports.
+ * Refused (non-zero return, dl4ds_last_error) before any launch: N, H, W or C < 1, H*W >= 2^31 - 1, max(H, W) >= 2^29,
+ * H*W*max(H, W)^2 >= 2^62, connectivity not 1 or 2, cap < 0, a null x_dev, thr_dev or count_dev, cap > 0 with a null table.
+ * dl4ds_object_thresholds: SAL's thr_dev [F] = float32(factor * the largest finite value of the field), the product taken in fp64
+ * and rounded once; 0 for a field without a finite cell or with a product that is not finite; factor positive and finite.
+ * Algorithmic traffic: 4 B per cell read (twice when tables are wanted), an 8 B per cell workspace (parent links, root labels)
+ * written once and read a small number of times, 4 B per cell of labels written when wanted.  Fields go through in chunks of a
+ * fixed workspace budget. */
+int dl4ds_label_objects(const float* x_dev, int N, int H, int W, int C, const float* thr_dev, int connectivity, int cap,
+                        int* labels_dev, int* count_dev, long long* nvalid_dev, double* field_sums_dev, long long* sums_dev,
+                        int* bbox_dev, int* first_dev, float* vmax_dev, double* mass_dev);
+int dl4ds_object_thresholds(const float* x_dev, int N, int H, int W, int C, double factor, float* thr_dev);
 /* Distribution verification of a prediction against an observation: per segment the sample quantiles of either side, the
  * 1-Wasserstein distance, the two-sample Kolmogorov-Smirnov statistic, a histogram of either side and the valid count.  The
  * reference has no such metric; the definitions are DESIGN.md section 15.  Element k of segment s of either array lives at
