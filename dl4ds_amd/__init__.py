@@ -44,6 +44,8 @@ def __getattr__(name):
             'NeighbourhoodVerifier': '.inference',
             'sal_from_objects': '.objects', 'check_object_args': '.objects',
             'label_objects': '.objects', 'sal_scores': '.objects', 'object_scores': '.objects',
+            'distance_transform': '.distance', 'distance_scores': '.distance', 'distance_from_sums': '.distance',
+            'check_distance_args': '.distance',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'QuantileMapper': '.postprocessing', 'quantile_map': '.postprocessing', 'check_qmap_args': '.postprocessing',

@@ -825,6 +825,15 @@ int dl4ds_object_thresholds(const float* x_dev, int N, int H, int W, int C, doub
     object_thresholds(S(), x_dev, N, H, W, C, factor, thr_dev, ws ? scratch(ws) : nullptr, ws);
     API_END
 }
+int dl4ds_distance_scores(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
+                          double cutoff, double alpha, long long* counts_dev, double* sums_dev, int* d2_obs_dev, int* d2_pred_dev) {
+    API_BEGIN
+    distance_check_args(y_dev, p_dev, N, H, W, C, thresholds_host, T, cutoff, alpha, counts_dev, sums_dev);   // before the workspace is sized
+    const size_t ws = distance_workspace_bytes(N, H, W, C, T);
+    distance_scores(S(), y_dev, p_dev, N, H, W, C, thresholds_host, T, cutoff, alpha, counts_dev, sums_dev, d2_obs_dev, d2_pred_dev,
+                    scratch(ws), ws);
+    API_END
+}
 int dl4ds_distribution(const float* y_dev, const float* p_dev, size_t n_seg, size_t L, size_t seg_stride, size_t elem_stride,
                        const double* q_host, int Q, const float* edges_host, int E, double* quant_dev, double* w1_dev,
                        long long* ks_dev, long long* hist_dev, long long* valid_dev) {

@@ -241,6 +241,17 @@ void label_objects(hipStream_t s, const float* x, int N, int H, int W, int C, co
 size_t object_thresholds_workspace_bytes(int N, int H, int W, int C);
 void object_thresholds(hipStream_t s, const float* x, int N, int H, int W, int C, double factor, float* thr, void* workspace,
                        size_t workspace_bytes);
+// Distance-map verification (distance.hip) of the N*C fields of y, p (N, H, W, C) at T host thresholds: per
+// field and threshold counts [F][T][8] (n_valid, n_A, n_B, n_AB, max and sum of d2 from A to B and from B to A) and sums [F][T][7]
+// (sum d both ways, Pratt sums both ways, Baddeley sum w, sum w^2, max w); d2_obs / d2_pred [F][T][H][W] (or null): the squared
+// distance maps of A and B.  Outputs are overwritten.  distance_check_args throws on a request the entry refuses (before the
+// workspace is sized).
+size_t distance_workspace_bytes(int N, int H, int W, int C, int T);
+void distance_check_args(const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T, double cutoff,
+                         double alpha, const long long* counts, const double* sums);
+void distance_scores(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T,
+                     double cutoff, double alpha, long long* counts, double* sums, int* d2_obs, int* d2_pred, void* workspace,
+                     size_t workspace_bytes);
 // Distribution verification (distribution.hip) of S pairs of length-L segments, element k of segment s at [s*seg_stride +
 // k*elem_stride]: per segment quant [S][2][Q] (numpy 'linear' quantiles of the valid values of y, p), w1 [S] (1-Wasserstein), ks [S]
 // (n times the two-sample KS statistic), hist [S][2][E-1] (np.histogram over the E edges; may be null when E == 0), valid [S] (n).

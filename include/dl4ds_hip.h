@@ -421,6 +421,33 @@ int dl4ds_label_objects(const float* x_dev, int N, int H, int W, int C, const fl
                         int* labels_dev, int* count_dev, long long* nvalid_dev, double* field_sums_dev, long long* sums_dev,
                         int* bbox_dev, int* first_dev, float* vmax_dev, double* mass_dev);
 int dl4ds_object_thresholds(const float* x_dev, int N, int H, int W, int C, double factor, float* thr_dev);
+/* Distance and displacement measures on binary event fields: the exact Euclidean distance transform of the observed and of the
+ * predicted event set and, on top of the two maps, the sums of the Hausdorff distance, the mean error distances, Baddeley's Delta
+ * and Pratt's figure of merit.  The reference has no such metric; the definitions are DESIGN.md section 29.  y_dev / p_dev:
+ * observation and prediction, (N, H, W, C) fp32, read in place with stride C; each of the F = N*C planes is one field (f = n*C + c).
+ * p_dev may equal y_dev (a single-field distance transform).  thresholds_host [T] (finite): a HOST array.  A cell is VALID iff y and
+ * p are both finite there: NaN in y_dev is the masking mechanism.  A = valid & (y >= t), B = valid & (p >= t) on float32 (-0.0 >=
+ * 0.0 holds); fields do not wrap.  d2(x, S) = min over s in S of di^2 + dj^2 as int32, 2^31 - 1 when S is empty (it reads as +inf);
+ * distances pass through invalid cells, sums leave them out.  With d = sqrt(d2) in fp64, cutoff c > 0 (may be +inf), alpha
+ * positive and finite, w(x) = |min(d(x, A), c) - min(d(x, B), c)|, every output given is overwritten:
+ *   counts_dev  [F][T][8] int64  n_valid, n_A, n_B, n_AB, max over A of d2(a, B), max over B of d2(b, A), sum over A of d2(a, B),
+ *                                sum over B of d2(b, A)  (0 over an empty set; the 2^31 - 1 of an empty other side is taken as it is)
+ *   sums_dev    [F][T][7] fp64   sum over A of d(a, B), sum over B of d(b, A), sum over A of 1 / (1 + alpha d2(a, B)), sum over B of
+ *                                1 / (1 + alpha d2(b, A)), and over the valid cells sum w, sum w^2, max w
+ *   d2_obs_dev, d2_pred_dev [F][T][H][W] int32, or null: d2(x, A) and d2(x, B) at every cell
+ * Every fp64 term is built from sqrt, +, -, *, /, min and abs without FMA contraction; non-finite results are left as IEEE
+ * arithmetic gives them.  The integers and the maps are pure functions of the input.  No atomics: the fp64 sums have one summation
+ * order (a lane's cells in ascending j, a fixed tree over the lanes, the rows in a fixed order), so a repeated call gives the same
+ * bits and nothing depends on N or on how the fields go through in chunks of a fixed workspace budget.  Plain launches on one
+ * stream; every loop is bounded by H, W or the number of row segments.
+ * Refused (non-zero return, dl4ds_last_error) before any launch: a null y_dev, p_dev, thresholds_host, counts_dev or sums_dev;
+ * N, H, W, C or T < 1; (H-1)^2 + (W-1)^2 >= 2^31 - 1 or H*W >= 2^31; a threshold that is not finite; cutoff not > 0 (NaN included);
+ * alpha not positive and finite.
+ * Algorithmic traffic: 8 B per cell read once per group of 8 thresholds; per threshold and cell 2 vertical distances (2 B each)
+ * written, read and mostly rewritten by the column pass and read once by the row pass, which also reads the 8 B of
+ * y and p again (from cache) and writes 4 B per map wanted. */
+int dl4ds_distance_scores(const float* y_dev, const float* p_dev, int N, int H, int W, int C, const float* thresholds_host, int T,
+                          double cutoff, double alpha, long long* counts_dev, double* sums_dev, int* d2_obs_dev, int* d2_pred_dev);
 /* Distribution verification of a prediction against an observation: per segment the sample quantiles of either side, the
  * 1-Wasserstein distance, the two-sample Kolmogorov-Smirnov statistic, a histogram of either side and the valid count.  The
  * reference has no such metric; the definitions are DESIGN.md section 15.  Element k of segment s of either array lives at
