@@ -3,6 +3,13 @@
 //   x = y - min(y) if min(y) < 0 else y ;  q = p - min(p) if min(p) < 0 else p
 //   ssim   = tf.image.ssim(x, q, max_val=drange, 11x11 gaussian sigma 1.5, VALID, k1=.01, k2=.03)
 //   dssim  = mean_n((1 - ssim_n)/2)
+// Pivot: float32 moments of the values themselves lose sigma^2 = E[x^2] - mu^2 and sigma_xy to rounding as soon as the mean is large
+// against the range (Kelvin, Pascal, a nearly constant field: c2 = (0.03 drange)^2 is all that is left).  Every tile kernel below
+// therefore stages t - pivT and p - pivP, the batch-wide means of the two arrays (Stats; the min/max pass sums them in double, fixed
+// order, so they are wave-uniform scalars and exact for a constant array), and takes all second moments of those.  Only the luminance
+// term needs the means themselves: mu = (piv - shift) + mu', where shift is the negative minimum that the loss takes off.  The
+// backward combines the same pivoted pixels with the transposed maps (x' T(va) + 2 q' T(vb) + T(vmu)): with raw pixels its three terms
+// would cancel at the size of the offset.  Average pooling preserves a constant, so the multi-scale pyramid is built of pivoted images.
 // Kernels: (1) min/max(+arg) reduction, (2) 16x16-tile SSIM map from an LDS halo tile -- the 11x11 Gaussian is applied
 // separably (row pass over the 26 halo rows into LDS, then the column pass per output: 2 x 11 taps instead of 121) to the
 // four moments -- emitting the three per-map derivatives, (3) the transposed (again separable) filter of those
@@ -38,25 +45,39 @@ struct Stats {            // device-resident scalars
     float minT, maxT, minP, maxP;
     unsigned long long argminP, argmaxP;
     float sumS, gc1, gc2, sumdy;
+    float pivT, pivP;     // means of y_true, y_pred: the pivots of the window moments
 };
+// what a tile kernel takes off its pixels (pT, pP) and what the luminance term adds back to the pivoted means (oT, oP); `shift`:
+// the loss's min-shift is in force (it is not for image_metrics)
+struct Pivot { float pT, pP, oT, oP; };
+__device__ __forceinline__ Pivot pivot_of(const Stats* __restrict__ st, bool shift) {
+    const float shT = (shift && st->minT < 0.f) ? st->minT : 0.f, shP = (shift && st->minP < 0.f) ? st->minP : 0.f;
+    return Pivot{st->pivT, st->pivP, st->pivT - shT, st->pivP - shP};
+}
 
 __global__ void __launch_bounds__(256) minmax_kernel(const float* __restrict__ t, const float* __restrict__ p, size_t n,
-                                                     float* __restrict__ pf, unsigned long long* __restrict__ pi) {
+                                                     float* __restrict__ pf, unsigned long long* __restrict__ pi,
+                                                     double* __restrict__ ps) {
     __shared__ float s[4][256];
     __shared__ unsigned long long si[2][256];
+    __shared__ double sd[2][256];
     float mnT = 3.4e38f, mxT = -3.4e38f, mnP = 3.4e38f, mxP = -3.4e38f;
     unsigned long long amn = 0, amx = 0;
+    double sT = 0.0, sP = 0.0;
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) {
         const float a = t[e], b = p[e];
         mnT = fminf(mnT, a); mxT = fmaxf(mxT, a);
         if (b < mnP) { mnP = b; amn = e; }
         if (b > mxP) { mxP = b; amx = e; }
+        sT += (double)a; sP += (double)b;
     }
     const int i = threadIdx.x;
     s[0][i] = mnT; s[1][i] = mxT; s[2][i] = mnP; s[3][i] = mxP; si[0][i] = amn; si[1][i] = amx;
+    sd[0][i] = sT; sd[1][i] = sP;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
         if (i < o) {
+            sd[0][i] += sd[0][i + o]; sd[1][i] += sd[1][i + o];
             s[0][i] = fminf(s[0][i], s[0][i + o]);
             s[1][i] = fmaxf(s[1][i], s[1][i + o]);
             if (s[2][i + o] < s[2][i] || (s[2][i + o] == s[2][i] && si[0][i + o] < si[0][i])) { s[2][i] = s[2][i + o]; si[0][i] = si[0][i + o]; }
@@ -68,24 +89,31 @@ __global__ void __launch_bounds__(256) minmax_kernel(const float* __restrict__ t
         for (int k = 0; k < 4; ++k) pf[blockIdx.x * 4 + k] = s[k][0];
         pi[blockIdx.x * 2] = si[0][0];
         pi[blockIdx.x * 2 + 1] = si[1][0];
+        ps[blockIdx.x * 2] = sd[0][0];
+        ps[blockIdx.x * 2 + 1] = sd[1][0];
     }
 }
 __global__ void __launch_bounds__(256) minmax_finish_kernel(const float* __restrict__ pf, const unsigned long long* __restrict__ pi,
-                                                            int nb, Stats* st) {
+                                                            const double* __restrict__ ps, double inv_n, int nb, Stats* st) {
     __shared__ float s[4][256];
     __shared__ unsigned long long si[2][256];
+    __shared__ double sd[2][256];
     const int i = threadIdx.x;
     float mnT = 3.4e38f, mxT = -3.4e38f, mnP = 3.4e38f, mxP = -3.4e38f;
     unsigned long long amn = ~0ull, amx = ~0ull;
+    double sT = 0.0, sP = 0.0;
     for (int k = i; k < nb; k += 256) {
         mnT = fminf(mnT, pf[4 * k]); mxT = fmaxf(mxT, pf[4 * k + 1]);
         if (pf[4 * k + 2] < mnP || (pf[4 * k + 2] == mnP && pi[2 * k] < amn)) { mnP = pf[4 * k + 2]; amn = pi[2 * k]; }
         if (pf[4 * k + 3] > mxP || (pf[4 * k + 3] == mxP && pi[2 * k + 1] < amx)) { mxP = pf[4 * k + 3]; amx = pi[2 * k + 1]; }
+        sT += ps[2 * k]; sP += ps[2 * k + 1];
     }
     s[0][i] = mnT; s[1][i] = mxT; s[2][i] = mnP; s[3][i] = mxP; si[0][i] = amn; si[1][i] = amx;
+    sd[0][i] = sT; sd[1][i] = sP;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {          // ties go to the smallest flat index, as a serial scan would pick
         if (i < o) {
+            sd[0][i] += sd[0][i + o]; sd[1][i] += sd[1][i + o];
             s[0][i] = fminf(s[0][i], s[0][i + o]);
             s[1][i] = fmaxf(s[1][i], s[1][i + o]);
             if (s[2][i + o] < s[2][i] || (s[2][i + o] == s[2][i] && si[0][i + o] < si[0][i])) { s[2][i] = s[2][i + o]; si[0][i] = si[0][i + o]; }
@@ -96,10 +124,11 @@ __global__ void __launch_bounds__(256) minmax_finish_kernel(const float* __restr
     if (i) return;
     st->minT = s[0][0]; st->maxT = s[1][0]; st->minP = s[2][0]; st->maxP = s[3][0]; st->argminP = si[0][0]; st->argmaxP = si[1][0];
     st->sumS = 0.f; st->gc1 = 0.f; st->gc2 = 0.f; st->sumdy = 0.f;
+    st->pivT = (float)(sd[0][0] * inv_n); st->pivP = (float)(sd[1][0] * inv_n);
 }
 
 // Gaussian-filtered moments (mean x, mean q, E[xq], E[x^2 + q^2]) of this thread's output pixel of the tile: row pass of
-// all TL halo rows into h (all 256 threads; contains a barrier), then the column pass.
+// all TL halo rows into h (all 256 threads; contains a barrier), then the column pass.  sx, sq hold pivoted pixels.
 struct MsMoments { float mx, my, A, Bq; };
 __device__ __forceinline__ MsMoments sep_moments(const float (*sx)[PT], const float (*sq)[PT], float (*h)[TL][TS], const Gauss& gk) {
     for (int it = threadIdx.x; it < TL * TS; it += 256) {
@@ -203,7 +232,7 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y; b /= tiles_y;
     const int c = b % C, n = b / C;
-    const float shT = st->minT < 0.f ? st->minT : 0.f, shP = st->minP < 0.f ? st->minP : 0.f;
+    const Pivot pv = pivot_of(st, true);
     const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
     const float c1 = (0.01f * drange) * (0.01f * drange), c2 = (0.03f * drange) * (0.03f * drange);
     const int oy0 = ty * TS, ox0 = tx * TS;
@@ -213,7 +242,7 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
         float a = 0.f, q = 0.f;
         if (y < H && x < W) {
             const size_t o = (((size_t)n * H + y) * W + x) * C + c;
-            a = t[o] - shT; q = p[o] - shP;
+            a = t[o] - pv.pT; q = p[o] - pv.pP;
         }
         sx[r][cc] = a; sq[r][cc] = q;
     }
@@ -223,13 +252,14 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
     float S = 0.f, g1 = 0.f, g2 = 0.f;
     const MsMoments mom = sep_moments(sx, sq, hrow, gk);
     if (oy < Ho && ox < Wo) {
-        const float mx = mom.mx, my = mom.my, A = mom.A, Bq = mom.Bq;
+        const float mxs = mom.mx, mys = mom.my, A = mom.A, Bq = mom.Bq;      // moments of the pivoted pixels
+        const float mx = pv.oT + mxs, my = pv.oP + mys;                      // means of the shifted arrays: luminance only
         const float N1 = 2.f * mx * my + c1, D1 = mx * mx + my * my + c1;
-        const float N2 = 2.f * A - 2.f * mx * my + c2, D2 = Bq - mx * mx - my * my + c2;
+        const float N2 = 2.f * A - 2.f * mxs * mys + c2, D2 = Bq - mxs * mxs - mys * mys + c2;
         const float lum = N1 / D1, cs = N2 / D2;
         S = lum * cs;
         const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
-        float vmu = cs * (2.f * mx / D1 - N1 * 2.f * my / (D1 * D1)) + lum * (-2.f * mx / D2 + N2 * 2.f * my / (D2 * D2));
+        float vmu = cs * (2.f * mx / D1 - N1 * 2.f * my / (D1 * D1)) + lum * (-2.f * mxs / D2 + N2 * 2.f * mys / (D2 * D2));
         float va = lum * 2.f / D2;
         float vb = -lum * N2 / (D2 * D2);
         g1 = cs * (D1 - N1) / (D1 * D1);
@@ -313,7 +343,7 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y; b /= tiles_y;
     const int c = b % C, n = b / C;
-    const float shT = st->minT < 0.f ? st->minT : 0.f, shP = st->minP < 0.f ? st->minP : 0.f;
+    const Pivot pv = pivot_of(st, true);
     const int y0 = ty * TS, x0 = tx * TS;
     // input pixel (y,x) is covered by outputs (y-i, x-j), i,j in [0,10]: halo tile starts at (y0-10, x0-10)
     for (int i = threadIdx.x; i < TL * TL; i += 256) {
@@ -334,7 +364,7 @@ __global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__
     sep_transposed3(s1, s2, s3, hrow, gk, T1, T2, T3);
     if (y < H && x < W) {
         const size_t o = (((size_t)n * H + y) * W + x) * C + c;
-        const float xv = t[o] - shT, qv = p[o] - shP;
+        const float xv = t[o] - pv.pT, qv = p[o] - pv.pP;          // the pivoted pixels the moments were taken of
         g = coef * (T1 + xv * T2 + 2.f * qv * T3);
         dpred[o] = accumulate ? dpred[o] + g : g;
     }
@@ -375,7 +405,7 @@ __global__ void dssim_finish_kernel(const float* __restrict__ partial, int nb, S
     if (st->minP < 0.f) dpred[st->argminP] -= sumdy;         // q = p - min(p)
 }
 
-struct Layout { size_t stats, pf, pi, maps, part, part2, total; int nb_mm; };
+struct Layout { size_t stats, pf, pi, ps, maps, part, part2, total; int nb_mm; };
 Layout layout(int N, int H, int W, int C) {
     Layout l;
     const int Ho = H - KF + 1, Wo = W - KF + 1;
@@ -385,6 +415,7 @@ Layout layout(int N, int H, int W, int C) {
     l.stats = bump(sizeof(Stats));
     l.pf = bump((size_t)l.nb_mm * 4 * sizeof(float));
     l.pi = bump((size_t)l.nb_mm * 2 * sizeof(unsigned long long));
+    l.ps = bump((size_t)l.nb_mm * 2 * sizeof(double));
     l.maps = bump(3 * (size_t)N * C * Ho * Wo * sizeof(float));
     const size_t tiles = (size_t)N * C * cdiv(H, TS) * cdiv(W, TS);
     l.part = bump(tiles * 3 * sizeof(float));
@@ -405,10 +436,11 @@ Layout layout(int N, int H, int W, int C) {
 constexpr int MS_SCALES = 4;
 struct MsDims { int H[MS_SCALES], W[MS_SCALES]; };
 
-// dst (Hd, Wd) = 2x2 average of src (Hs, Ws) minus `shift` (scale 0 -> 1 applies the positivity shift), edge repeated
+// dst (Hd, Wd) = 2x2 average of src (Hs, Ws) less its pivot (scale 0 -> 1 reads the raw array; the coarser images are pivoted
+// already), edge repeated.  The pivot comes off each source, not off the sum: the sum of four raw values rounds at the size of the mean
 __global__ void ms_pool_kernel(const float* __restrict__ src, float* __restrict__ dst, int N, int Hs, int Ws, int Hd, int Wd,
                                int C, const Stats* __restrict__ st, int which) {      // which: 0 none, 1 y_true, 2 y_pred
-    const float sh = which == 1 ? (st->minT < 0.f ? st->minT : 0.f) : which == 2 ? (st->minP < 0.f ? st->minP : 0.f) : 0.f;
+    const float pv = which == 1 ? st->pivT : which == 2 ? st->pivP : 0.f;
     const size_t total = (size_t)N * Hd * Wd * C;
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const int c = (int)(e % C);
@@ -418,9 +450,9 @@ __global__ void ms_pool_kernel(const float* __restrict__ src, float* __restrict_
         const int n = (int)(r / Hd);
         const int y0 = 2 * y, y1 = min(2 * y + 1, Hs - 1), x0 = 2 * x, x1 = min(2 * x + 1, Ws - 1);
         const float* b = src + (size_t)n * Hs * Ws * C + c;
-        const float v = b[((size_t)y0 * Ws + x0) * C] + b[((size_t)y0 * Ws + x1) * C] + b[((size_t)y1 * Ws + x0) * C] +
-                        b[((size_t)y1 * Ws + x1) * C];
-        dst[e] = 0.25f * v - sh;
+        const float v = (b[((size_t)y0 * Ws + x0) * C] - pv) + (b[((size_t)y0 * Ws + x1) * C] - pv) +
+                        (b[((size_t)y1 * Ws + x0) * C] - pv) + (b[((size_t)y1 * Ws + x1) * C] - pv);
+        dst[e] = 0.25f * v;
     }
 }
 
@@ -441,9 +473,10 @@ __global__ void ms_unpool_add_kernel(float* __restrict__ fine, const float* __re
 }
 
 // MODE 0: partial[block] = (sum ssim, sum cs) of the tile.  MODE 1: derivative maps weighted by gs[n,c] (ssim) and gc[n,c]
-// (cs), partial[block] = (d/dc1, d/dc2).  x / q: scale images (scale 0: raw y_true / y_pred, shifted here).
+// (cs), partial[block] = (d/dc1, d/dc2).  x / q: scale images (raw: y_true / y_pred themselves, pivoted here; else images of the
+// pivoted pyramid).  shift: the loss's min-shift enters the luminance means (0 for image_metrics).
 template <int MODE>
-__global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ x, const float* __restrict__ q, int raw, int H, int W,
+__global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ x, const float* __restrict__ q, int raw, int shift, int H, int W,
                                                       int C, int Ho, int Wo, int tiles_x, int tiles_y, Gauss gk,
                                                       const Stats* __restrict__ st, const float* __restrict__ gs,
                                                       const float* __restrict__ gc, float* __restrict__ dmu, float* __restrict__ da,
@@ -454,7 +487,8 @@ __global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ 
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y; b /= tiles_y;
     const int c = b % C, n = b / C;
-    const float shT = (raw && st->minT < 0.f) ? st->minT : 0.f, shP = (raw && st->minP < 0.f) ? st->minP : 0.f;
+    const Pivot pv = pivot_of(st, shift != 0);
+    const float pT = raw ? pv.pT : 0.f, pP = raw ? pv.pP : 0.f;
     const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
     const float c1 = (0.01f * drange) * (0.01f * drange), c2 = (0.03f * drange) * (0.03f * drange);
     const int oy0 = ty * TS, ox0 = tx * TS;
@@ -464,7 +498,7 @@ __global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ 
         float a = 0.f, v = 0.f;
         if (y < H && xx < W) {
             const size_t o = (((size_t)n * H + y) * W + xx) * C + c;
-            a = x[o] - shT; v = q[o] - shP;
+            a = x[o] - pT; v = q[o] - pP;
         }
         sx[r][cc] = a; sq[r][cc] = v;
     }
@@ -474,7 +508,8 @@ __global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ 
     float r0 = 0.f, r1 = 0.f;
     const MsMoments m = sep_moments(sx, sq, hrow, gk);
     if (oy < Ho && ox < Wo) {
-        const float N1 = 2.f * m.mx * m.my + c1, D1 = m.mx * m.mx + m.my * m.my + c1;
+        const float mx = pv.oT + m.mx, my = pv.oP + m.my;          // m: moments of the pivoted pixels; mx, my: luminance only
+        const float N1 = 2.f * mx * my + c1, D1 = mx * mx + my * my + c1;
         const float N2 = 2.f * m.A - 2.f * m.mx * m.my + c2, D2 = m.Bq - m.mx * m.mx - m.my * m.my + c2;
         const float lum = N1 / D1, cs = N2 / D2;
         if (MODE == 0) {
@@ -483,7 +518,7 @@ __global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ 
             const float inv_m = 1.f / ((float)Ho * (float)Wo);
             const float ws = gs[n * C + c] * inv_m, wc = gc[n * C + c] * inv_m;
             const float dcs_dmy = -2.f * m.mx / D2 + N2 * 2.f * m.my / (D2 * D2);
-            const float dlum_dmy = 2.f * m.mx / D1 - N1 * 2.f * m.my / (D1 * D1);
+            const float dlum_dmy = 2.f * mx / D1 - N1 * 2.f * my / (D1 * D1);
             const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
             dmu[o] = ws * (cs * dlum_dmy + lum * dcs_dmy) + wc * dcs_dmy;
             da[o] = (ws * lum + wc) * 2.f / D2;
@@ -561,7 +596,7 @@ __global__ void __launch_bounds__(256) ms_bwd_kernel(const float* __restrict__ x
     const int tx = b % tiles_x; b /= tiles_x;
     const int ty = b % tiles_y; b /= tiles_y;
     const int c = b % C, n = b / C;
-    const float shT = (raw && st->minT < 0.f) ? st->minT : 0.f, shP = (raw && st->minP < 0.f) ? st->minP : 0.f;
+    const float pT = raw ? st->pivT : 0.f, pP = raw ? st->pivP : 0.f;
     const int y0 = ty * TS, x0 = tx * TS;
     for (int i = threadIdx.x; i < TL * TL; i += 256) {
         const int r = i / TL, cc = i % TL;
@@ -580,7 +615,7 @@ __global__ void __launch_bounds__(256) ms_bwd_kernel(const float* __restrict__ x
     sep_transposed3(s1, s2, s3, hrow, gk, T1, T2, T3);
     if (y < H && xx < W) {
         const size_t o = (((size_t)n * H + y) * W + xx) * C + c;
-        gq[o] = T1 + (x[o] - shT) * T2 + 2.f * (q[o] - shP) * T3;
+        gq[o] = T1 + (x[o] - pT) * T2 + 2.f * (q[o] - pP) * T3;
     }
 }
 
@@ -626,7 +661,7 @@ __global__ void __launch_bounds__(256) ms_finish_kernel(const float* __restrict_
 }
 
 struct MsLayout {
-    size_t stats, pf, pi, imgs, grads, maps, part, part2, gcp, means, gw, total;
+    size_t stats, pf, pi, ps, imgs, grads, maps, part, part2, gcp, means, gw, total;
     size_t img_off[MS_SCALES], grad_off[MS_SCALES], gcp_off[MS_SCALES];
     MsDims d;
     int nb_mm;
@@ -641,6 +676,7 @@ MsLayout ms_layout(int N, int H, int W, int C) {
     l.stats = bump(sizeof(Stats));
     l.pf = bump((size_t)l.nb_mm * 4 * sizeof(float));
     l.pi = bump((size_t)l.nb_mm * 2 * sizeof(unsigned long long));
+    l.ps = bump((size_t)l.nb_mm * 2 * sizeof(double));
     size_t img = 0, grad = 0, gcp = 0;
     for (int k = 0; k < MS_SCALES; ++k) {
         const size_t n = (size_t)N * l.d.H[k] * l.d.W[k] * C;
@@ -682,6 +718,7 @@ void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* d
     Stats* st = reinterpret_cast<Stats*>(base + l.stats);
     float* pf = reinterpret_cast<float*>(base + l.pf);
     unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + l.pi);
+    double* psum = reinterpret_cast<double*>(base + l.ps);
     const int Ho = H - KF + 1, Wo = W - KF + 1;
     const size_t msz = (size_t)N * C * Ho * Wo;
     float* dmu = reinterpret_cast<float*>(base + l.maps);
@@ -692,8 +729,8 @@ void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* d
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "dssim", 0.0, 4.0 * (double)n * 8);
     const int nb = (int)std::min<size_t>(l.nb_mm, cdivz(n, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n, pf, pi);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, nb, st);
+    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n, pf, pi, psum);
+    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n, nb, st);
     const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
     const int nbf = N * C * txo * tyo;
     const float* omega = nullptr;
@@ -765,6 +802,7 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     Stats* st = reinterpret_cast<Stats*>(base + l.stats);
     float* pf = reinterpret_cast<float*>(base + l.pf);
     unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + l.pi);
+    double* psum = reinterpret_cast<double*>(base + l.ps);
     float* imgs = reinterpret_cast<float*>(base + l.imgs);
     float* grads = reinterpret_cast<float*>(base + l.grads);
     float* maps = reinterpret_cast<float*>(base + l.maps);
@@ -777,8 +815,8 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "msdssim", 0.0, 4.0 * (double)n0 * 12);
     const int nb = (int)std::min<size_t>(l.nb_mm, cdivz(n0, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, nb, st);
+    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi, psum);
+    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n0, nb, st);
     auto ew = [](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>(cdivz(n, 256), 8192)); };
     const float* xk[MS_SCALES];
     const float* qk[MS_SCALES];
@@ -798,7 +836,7 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     for (int k = 0; k < MS_SCALES; ++k) {
         const int Ho = l.d.H[k] - KF + 1, Wo = l.d.W[k] - KF + 1;
         const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
-        DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, l.d.H[k], l.d.W[k],
+        DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, 1, l.d.H[k], l.d.W[k],
                            C, Ho, Wo, txo, tyo, gk, st, nullptr, nullptr, nullptr, nullptr, nullptr, part);
         DL4DS_LAUNCH(ms_means_kernel, dim3(NC), dim3(64), 0, s, part, txo * tyo, NC, 1.f / ((float)Ho * (float)Wo),
                            means + (size_t)k * NC, means + (size_t)(MS_SCALES + k) * NC);
@@ -816,7 +854,7 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
         float* da = dmu + msz;
         float* db = da + msz;
         const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
-        DL4DS_LAUNCH(ms_ssim_kernel<1>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, Hk, Wk, C, Ho, Wo,
+        DL4DS_LAUNCH(ms_ssim_kernel<1>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, 1, Hk, Wk, C, Ho, Wo,
                            txo, tyo, gk, st, gw + (size_t)k * NC, gw + (size_t)(MS_SCALES + k) * NC, dmu, da, db,
                            gcp + l.gcp_off[k] * 2);
         gcp_total = std::max(gcp_total, l.gcp_off[k] + (size_t)NC * txo * tyo);
@@ -844,7 +882,8 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
 // point RMSE, mean bias and Pearson correlation over the pairs.  Everything is a streaming pass over the two arrays:
 //   pair sums   : blocks of one pair reduce (|d|, d^2, x, y, xy, x^2, y^2) -> fixed-order partials -> one thread per pair;
 //   grid points : one thread per (pixel, channel) walks the pairs (coalesced across pixels);
-//   SSIM        : the tile kernel of the multi-scale loss at scale 0 (separable Gaussian moments) + its per-plane means.
+//   SSIM        : the tile kernel of the multi-scale loss at scale 0 (separable Gaussian moments of the pivoted pixels, no min-shift)
+//                 + its per-plane means.
 namespace {
 constexpr int MET_CHUNKS = 64, MET_K = 7;
 
@@ -923,7 +962,7 @@ size_t metrics_workspace_bytes(int N, int H, int W, int C) {
     const size_t per = (size_t)H * W * C;
     const int Ho = H - KF + 1, Wo = W - KF + 1;
     const size_t tiles = (Ho > 0 && Wo > 0) ? (size_t)N * C * cdiv(Ho, TS) * cdiv(Wo, TS) : 0;
-    return sizeof(Stats) + 256 + (size_t)512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long)) + 256 +
+    return sizeof(Stats) + 256 + (size_t)512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long) + 2 * sizeof(double)) + 256 +
            ((size_t)N * MET_CHUNKS * MET_K + (size_t)N * 3 + 3 * per + tiles * 2 + (size_t)2 * N * C + 64) * sizeof(float);
 }
 
@@ -936,15 +975,16 @@ void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int 
     Stats* st = reinterpret_cast<Stats*>(base);
     float* pf = reinterpret_cast<float*>(base + 256);
     unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + 256 + 512 * 4 * sizeof(float));
-    float* f = reinterpret_cast<float*>(base + 256 + 512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long)) + 256);
+    double* psum = reinterpret_cast<double*>(base + 256 + 512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long)));
+    float* f = reinterpret_cast<float*>(base + 256 + 512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long) + 2 * sizeof(double)) + 256);
     float* partial = f;                                   f += (size_t)N * MET_CHUNKS * MET_K;
     float* pair3 = f;                                     f += (size_t)N * 3;
     float* tile_part = f;
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "image_metrics", 0.0, 4.0 * (double)n0 * 6);
     const int nb = (int)std::min<size_t>(512, cdivz(n0, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, nb, st);
+    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi, psum);
+    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n0, nb, st);
     DL4DS_LAUNCH(met_pair_partial_kernel, dim3(MET_CHUNKS, N), dim3(256), 0, s, y_true, y_pred, per, partial);
     DL4DS_LAUNCH(met_pair_finish_kernel, dim3(cdiv(N, 64)), dim3(64), 0, s, partial, MET_CHUNKS, N, (double)per, pair3);
     DL4DS_LAUNCH(met_grid_kernel, dim3((unsigned)std::min<size_t>(cdivz(per, 256), 4096)), dim3(256), 0, s, y_true, y_pred, N,
@@ -956,7 +996,7 @@ void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int 
     if (Ho > 0 && Wo > 0) {
         const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
         means = tile_part + (size_t)NC * txo * tyo * 2;
-        DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, y_true, y_pred, 0, H, W, C, Ho, Wo, txo, tyo, gk, st,
+        DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, y_true, y_pred, 1, 0, H, W, C, Ho, Wo, txo, tyo, gk, st,
                            nullptr, nullptr, nullptr, nullptr, nullptr, tile_part);
         DL4DS_LAUNCH(ms_means_kernel, dim3(NC), dim3(64), 0, s, tile_part, txo * tyo, NC, 1.f / ((float)Ho * (float)Wo), means,
                            means + NC);

@@ -105,6 +105,24 @@ def test_dssim_kinds_against_the_reference(ops, shape, form, data):
         close(g, rg)
 
 
+def test_dssim_mae_on_kelvin_fields_with_a_block_of_windows_masked(ops):
+    """The weighted tile kernels take the same pivoted moments as the unweighted ones: data with a mean of 7 dynamic ranges
+    (tests/ssim_cases.py: the kelvin class), a mask that removes 7 x 10 whole windows per sample."""
+    from tests import ssim_cases as S
+    case = S.FIELD_WEIGHTED_CASE
+    t, p = S.loss_inputs(case)
+    w = np.ones(case.shape[1:3], np.float32)
+    w[S.FIELD_MASK_BLOCK] = 0.0
+    om = R.window_weights(R.broadcast_weights(w, t.shape)).numpy()
+    assert (om == 0).sum() == case.shape[0] * 7 * 10
+    v, g = ops.loss(case.kind, t, p, weights=w)
+    rv, rg = R.value_and_grad(case.kind, t, p, w)
+    print(case.id, v, rv, np.abs(g - rg).max() / np.abs(rg).max())
+    assert np.isfinite(v) and np.isfinite(g).all()
+    value_close(v, rv)
+    close(g, rg)
+
+
 # ---------------------------------------------------------------------------------------------- 5. refusal
 @pytest.mark.parametrize('kind', ['msdssim', 'msdssim_mae', 'msdssim_mae_mse'])
 def test_multiscale_kinds_with_weights_are_refused(ops, kind):

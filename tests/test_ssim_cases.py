@@ -12,6 +12,11 @@ No case has an unintended tie in a prediction extreme, and no minimum is zero or
 maximum) unless the case is about exactly that: the extremes are selected, not computed, so nothing short of equality can flip a branch.  The per-pair Pearson arithmetic of image_metrics is
 restated with and without the pivot: float partials of the raw moments miss the 2e-5 bound on the offset cases at (280, 1),
 (1000, 1) and (101325, 300) (2.3e-4 .. 1.3e-3; at (280, 5) these draws give 1.3e-5 and 7.5e-6), with the pivot the worst is 2.3e-8.
+The field classes (FIELD_CASES): the float32 arithmetic of the loss kernels is restated twice in numpy (K.loss32), with the window
+moments of the values themselves and of pivoted values.  The pivoted form holds a quarter of the loss and gradient bounds on every
+case (worst: loss 3.8e-2 of its bound on scale1e-3 / msdssim, gradient 0.15 of its bound on mixed-sign / msdssim, at the entry the
+min-shift term goes to), so the GPU test's bounds are attainable; the raw form misses both bounds on the SSIM terms of kelvin, pascal
+and offset1000 (loss 8 .. 1e5 x its bound) and a bound on near-constant's multi-scale loss, so the cases discriminate.
 Largest float64 references: ms-pool 8.7 s, ms-long 4.2 s, grid-trip 3.5 s (test_reference_times prints them).
 """
 import os
@@ -77,7 +82,11 @@ def test_constants_and_launch_expressions_match_the_source():
             ('if(st->maxP>st->maxT)dpred[st->argmaxP]+=ddr;', 2),
             ('if(st->minP<st->minT)dpred[st->argminP]-=ddr;', 2),
             ('if(st->minP<0.f)dpred[st->argminP]-=', 2),
-            ('constfloatshT=st->minT<0.f?st->minT:0.f,shP=st->minP<0.f?st->minP:0.f;', 2)):
+            ('constfloatshT=(shift&&st->minT<0.f)?st->minT:0.f,shP=(shift&&st->minP<0.f)?st->minP:0.f;', 1),
+            ('returnPivot{st->pivT,st->pivP,st->pivT-shT,st->pivP-shP};', 1),
+            ('constPivotpv=pivot_of(st,true);', 2),
+            ('constPivotpv=pivot_of(st,shift!=0);', 1),
+            ('st->pivT=(float)(sd[0][0]*inv_n);st->pivP=(float)(sd[1][0]*inv_n);', 1)):
         assert d.count(piece) == count, (piece, d.count(piece))
     capi = _src('dl4ds_amd', 'csrc', 'capi.cpp')
     assert 'loss_forward_backward(S(),kind,yt,yp,dpred,N,H,W,C,scale,loss_dev,accumulate,scratch(ws),ws);' in capi
@@ -355,6 +364,111 @@ def test_routing_cases_are_what_they_are_named_for(route):
         assert np.delete(diff, [K.R_PRED, K.R_PRED2]).max() <= 1e-4 * tol
         assert nudged[1].reshape(-1)[[K.R_PRED, K.R_PRED2]].sum() == pytest.approx(plain[1].reshape(-1)[[K.R_PRED, K.R_PRED2]].sum(),
                                                                                     rel=1e-6)
+
+
+# ------------------------------------------------------------------------------------------------------------ field classes
+_SMOOTH01 = ('smooth01', 'smooth-err', 'scale1e4', 'scale1e-3')          # the rescaled target's minimum is exactly 0: no shift either side
+
+
+@pytest.mark.parametrize('case', K.FIELD_CASES, ids=lambda c: c.id)
+def test_field_cases_are_what_they_are_named_for(case):
+    """finite float64 reference in well under a second; unique selections; the class's own property"""
+    cls = K.field_class(case)
+    yt, yp = K.loss_inputs(case)
+    assert yt.dtype == np.float32 and yp.dtype == np.float32 and not yt.flags.writeable and not yp.flags.writeable
+    ref, gref, seconds = K.loss_ref(case)
+    assert np.isfinite(ref) and np.isfinite(gref).all() and seconds < 0.5
+    minT, _, maxT, _ = _extremes(yt)
+    minP, nmin, maxP, nmax = _extremes(yp)
+    drange = float(max(maxT, maxP)) - float(min(minT, minP))
+    if cls == 'constant-both':
+        assert np.ptp(yt) == 0 and np.ptp(yp) == 0 and minP > maxT > 0          # the tie of the maxima: K._loss_ref
+        return
+    assert (nmin, nmax) == (1, 1)
+    if cls == 'identical':
+        assert yt.tobytes() == yp.tobytes() and ref == 0.0
+        _check_margins(yt, yp, ('minT', 'minP', 'min', 'max'))
+        return
+    _check_margins(yt, yp, ('minT',) if cls in _SMOOTH01 else ())
+    if cls in ('kelvin', 'pascal', 'offset1000'):
+        assert min(minT, minP) > 0 and float(yt.mean()) / drange >= 4.0
+    elif cls == 'celsius':
+        assert minP < minT < 0 and maxT > 0
+    elif cls == 'mixed-sign':
+        assert minT > 0 and (yp < 0).sum() == 1 and float(yt.mean()) / drange > 0.75
+    elif cls == 'near-constant':
+        assert np.ptp(yt) == 0 and minP < minT < maxP
+    elif cls.startswith('scale'):
+        base = next(c for c in K.FIELD_CASES if c.kind == case.kind and K.field_class(c) == 'smooth01')
+        s = {'scale1e4': 1e4, 'scale1e-3': 1e-3}[cls]
+        np.testing.assert_array_equal(yt, K.loss_inputs(base)[0] * np.float32(s))
+        if case.kind in ('dssim', 'msdssim'):          # SSIM does not see the scale; the gradient goes with 1 / scale
+            assert ref == pytest.approx(K.loss_ref(base)[0], rel=1e-5)
+            assert np.abs(gref).max() * s == pytest.approx(np.abs(K.loss_ref(base)[1]).max(), rel=1e-3)
+
+
+@pytest.mark.parametrize('case', K.FIELD_CASES, ids=lambda c: c.id)
+def test_pivoted_float32_moments_hold_a_quarter_of_the_bounds(case):
+    """the bounds of the GPU test are attainable by straightforward float32 code on every field case"""
+    loss_err, grad_err = K.field_errors(case, True)
+    print(f'{case.id}: pivoted float32, loss {loss_err:.2e} of its bound, gradient {grad_err:.2e} of max |ref|')
+    assert loss_err <= 0.25
+    if K.field_class(case) in K.ZERO_GRAD_CLASSES:
+        # nothing to be relative to: the restatement's own largest entry is the GPU test's yardstick, and it is small
+        # against a typical gradient of the smooth01 case of the same kind
+        base = next(c for c in K.FIELD_CASES if c.kind == case.kind and K.field_class(c) == 'smooth01')
+        typical = np.median(np.abs(K.loss_ref(base)[1]))
+        print(f'{case.id}: largest float32 entry {K.identical_grad32(case):.2e}, typical smooth01 entry {typical:.2e}')
+        assert 0.0 < 10.0 * K.identical_grad32(case) <= 1e-3 * typical
+    else:
+        assert grad_err <= 0.25 * K.TOL_GRAD
+
+
+_PURE_OFFSET = [c for c in K.FIELD_CASES if K.field_class(c) in K.OFFSET_CLASSES and c.kind in ('dssim', 'msdssim')]
+
+
+@pytest.mark.parametrize('case', _PURE_OFFSET, ids=lambda c: c.id)
+def test_raw_float32_moments_miss_the_bounds_on_the_offset_classes(case):
+    """The cases discriminate: moments of the values themselves (what the kernels formed before the pivot) miss both bounds on the
+    SSIM terms of kelvin, pascal and offset1000, and a bound on near-constant's multi-scale loss.  (The mixes carry the same SSIM
+    term beside pixel terms that raw float32 gets right, so their totals may pass.  near-constant at one scale passes too in the
+    kernels' filter order: the target 0.5 is a power of two, every product with a tap is exact and the target's side leaves no
+    residue -- 1.9e-2 of the loss bound, 7.6e-5 of the gradient's; the pooled scales do not have that luck.)"""
+    loss_err, grad_err = K.field_errors(case, False)
+    print(f'{case.id}: raw float32, loss {loss_err:.2e} of its bound, gradient {grad_err:.2e} of max |ref|')
+    if K.field_class(case) != 'near-constant':
+        assert loss_err > 1.0 and grad_err > K.TOL_GRAD
+    elif case.kind == 'msdssim':
+        assert loss_err > 1.0 or grad_err > K.TOL_GRAD
+
+
+def test_field_classes_each_have_both_loss_families():
+    for cls in K.FIELD_CLASSES:
+        kinds = {c.kind for c in K.FIELD_CASES if K.field_class(c) == cls}
+        assert any(k.startswith('dssim') for k in kinds) and any(k.startswith('msdssim') for k in kinds), cls
+    assert {c.shape for c in K.FIELD_CASES} == set(K.FIELD_SHAPES.values())
+    assert K.pyramid(81, 88)[-1] == (11, 11) and K.pyramid(80, 88)[-1][0] < K.KF          # 81: the least height with four scales
+    assert K.tiles_fwd(27, 43) == (3, 2) and (43 - K.KF + 1) % K.TS != 0                    # two and more tile columns, ragged
+    om = np.ones(K.FIELD_SHAPES['dssim'][1:3])
+    om[K.FIELD_MASK_BLOCK] = 0.0
+    full = [(y, x) for y in range(17) for x in range(33) if not om[y:y + 11, x:x + 11].any()]
+    assert len(full) == 7 * 10                                                               # windows the weighted case excludes
+
+
+def test_field_accumulate_case_is_sensitive():
+    case = K.FIELD_ACCUMULATE_CASE
+    g = K.loss_ref(case)[1]
+    pre = K.field_preload(case)
+    assert np.abs(pre).max() >= FACTOR * K.TOL_GRAD * np.abs(g).max()
+    assert 4 * np.finfo(np.float32).eps * np.abs(pre).max() <= 0.1 * K.TOL_GRAD * np.abs(g).max()       # the preload's rounding
+    assert np.isfinite(K.loss_ref(K.FIELD_NULL_GRAD_CASE)[0]) and K.loss_ref(K.FIELD_NULL_GRAD_CASE)[1] is None
+
+
+def test_metric_offset_cases_assert_ssim():
+    assert all(c.ssim for c in K.MET_OFFSET_CASES) and len(K.MET_OFFSET_CASES) == 8
+    for c in K.MET_CASES:
+        if c.id in ('const-point', 'const-pair'):
+            assert c.ssim == bool(np.isfinite(K.met_ref(c)[0]['ssim']).all())
 
 
 # --------------------------------------------------------------------------------------------- the pair sums of the metrics
