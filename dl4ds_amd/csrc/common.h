@@ -233,6 +233,27 @@ __device__ __forceinline__ float wave_min(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_down(v, o, 64));
     return v;
 }
+// The halving tree of a 256-thread block over LDS rows that every thread has just filled (the barrier after the fill is in here):
+// combine(i, i + o) for o = 128 .. 1, a barrier after each step; entry 0 holds the result.  A fixed order: the same bits every call
+template <class F>
+__device__ __forceinline__ void block_tree(int tid, F&& combine) {
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) combine(tid, tid + o);
+        __syncthreads();
+    }
+}
+template <class T, int K>
+__device__ __forceinline__ void block_tree_sum(T (&red)[K][256], int tid) {
+    block_tree(tid, [&](int i, int j) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) red[k][i] += red[k][j];
+    });
+}
+template <class T>
+__device__ __forceinline__ void block_tree_sum(T (&red)[256], int tid) {
+    block_tree(tid, [&](int i, int j) { red[i] += red[j]; });
+}
 
 // false for NaN and +-inf, from the exponent bits alone (no floating-point compare)
 __device__ __forceinline__ bool finite_bits(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }

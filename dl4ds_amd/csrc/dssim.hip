@@ -14,6 +14,11 @@
 // separably (row pass over the 26 halo rows into LDS, then the column pass per output: 2 x 11 taps instead of 121) to the
 // four moments -- emitting the three per-map derivatives, (3) the transposed (again separable) filter of those
 // derivatives per input pixel, (4) scalar fix-ups (drange and shift terms routed to arg-max / arg-min).
+// The loss, the multi-scale loss and image_metrics are built of one toolkit, each piece standing once: minmax_tree (both min/max
+// kernels), tile_of / stage_pair / sep_moments (forward tiles), stage_maps3 / sep_transposed3 (the one backward tile kernel,
+// ssim_bwd_kernel<WEIGHTED, REDUCE>), SsimPoint (the SSIM arithmetic of a window; ssim_fwd_kernel and ms_ssim_kernel differ in their
+// epilogues only), route_range_and_shift (both finishing kernels), block_tree_sum of common.h (every block reduction), and on the
+// host carve_stats / run_minmax / map_geom over one Bump carving, which the workspace-size functions and the launches share.
 //
 // Weighted form (dssim_forward_backward_weighted; contract in losses.hip): window weights omega = G * w over the VALID windows,
 // term = sum omega (1 - s)/2 / sum omega, windows with omega == 0 excluded by selection.  omega_kernel WRITES the omega map once per
@@ -55,12 +60,26 @@ __device__ __forceinline__ Pivot pivot_of(const Stats* __restrict__ st, bool shi
     return Pivot{st->pivT, st->pivP, st->pivT - shT, st->pivP - shP};
 }
 
+// Block result of the min/max pass: min / max of t, min / max of p with their flat indices, and the double sums of both.  Every
+// thread hands in its own; ties of p's extremes go to the smallest flat index, as a serial scan would pick.  Row [.][0] holds the result
+struct MinMaxRed { float s[4][256]; unsigned long long si[2][256]; double sd[2][256]; };
+__device__ __forceinline__ void minmax_tree(MinMaxRed& r, int i, float mnT, float mxT, float mnP, float mxP, unsigned long long amn,
+                                            unsigned long long amx, double sT, double sP) {
+    r.s[0][i] = mnT; r.s[1][i] = mxT; r.s[2][i] = mnP; r.s[3][i] = mxP; r.si[0][i] = amn; r.si[1][i] = amx;
+    r.sd[0][i] = sT; r.sd[1][i] = sP;
+    block_tree(i, [&](int i, int j) {      // i keeps, j = i + o is folded in
+        r.sd[0][i] += r.sd[0][j]; r.sd[1][i] += r.sd[1][j];
+        r.s[0][i] = fminf(r.s[0][i], r.s[0][j]);
+        r.s[1][i] = fmaxf(r.s[1][i], r.s[1][j]);
+        if (r.s[2][j] < r.s[2][i] || (r.s[2][j] == r.s[2][i] && r.si[0][j] < r.si[0][i])) { r.s[2][i] = r.s[2][j]; r.si[0][i] = r.si[0][j]; }
+        if (r.s[3][j] > r.s[3][i] || (r.s[3][j] == r.s[3][i] && r.si[1][j] < r.si[1][i])) { r.s[3][i] = r.s[3][j]; r.si[1][i] = r.si[1][j]; }
+    });
+}
+
 __global__ void __launch_bounds__(256) minmax_kernel(const float* __restrict__ t, const float* __restrict__ p, size_t n,
                                                      float* __restrict__ pf, unsigned long long* __restrict__ pi,
                                                      double* __restrict__ ps) {
-    __shared__ float s[4][256];
-    __shared__ unsigned long long si[2][256];
-    __shared__ double sd[2][256];
+    __shared__ MinMaxRed r;
     float mnT = 3.4e38f, mxT = -3.4e38f, mnP = 3.4e38f, mxP = -3.4e38f;
     unsigned long long amn = 0, amx = 0;
     double sT = 0.0, sP = 0.0;
@@ -71,33 +90,18 @@ __global__ void __launch_bounds__(256) minmax_kernel(const float* __restrict__ t
         if (b > mxP) { mxP = b; amx = e; }
         sT += (double)a; sP += (double)b;
     }
-    const int i = threadIdx.x;
-    s[0][i] = mnT; s[1][i] = mxT; s[2][i] = mnP; s[3][i] = mxP; si[0][i] = amn; si[1][i] = amx;
-    sd[0][i] = sT; sd[1][i] = sP;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (i < o) {
-            sd[0][i] += sd[0][i + o]; sd[1][i] += sd[1][i + o];
-            s[0][i] = fminf(s[0][i], s[0][i + o]);
-            s[1][i] = fmaxf(s[1][i], s[1][i + o]);
-            if (s[2][i + o] < s[2][i] || (s[2][i + o] == s[2][i] && si[0][i + o] < si[0][i])) { s[2][i] = s[2][i + o]; si[0][i] = si[0][i + o]; }
-            if (s[3][i + o] > s[3][i] || (s[3][i + o] == s[3][i] && si[1][i + o] < si[1][i])) { s[3][i] = s[3][i + o]; si[1][i] = si[1][i + o]; }
-        }
-        __syncthreads();
-    }
-    if (i == 0) {
-        for (int k = 0; k < 4; ++k) pf[blockIdx.x * 4 + k] = s[k][0];
-        pi[blockIdx.x * 2] = si[0][0];
-        pi[blockIdx.x * 2 + 1] = si[1][0];
-        ps[blockIdx.x * 2] = sd[0][0];
-        ps[blockIdx.x * 2 + 1] = sd[1][0];
+    minmax_tree(r, threadIdx.x, mnT, mxT, mnP, mxP, amn, amx, sT, sP);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < 4; ++k) pf[blockIdx.x * 4 + k] = r.s[k][0];
+        pi[blockIdx.x * 2] = r.si[0][0];
+        pi[blockIdx.x * 2 + 1] = r.si[1][0];
+        ps[blockIdx.x * 2] = r.sd[0][0];
+        ps[blockIdx.x * 2 + 1] = r.sd[1][0];
     }
 }
 __global__ void __launch_bounds__(256) minmax_finish_kernel(const float* __restrict__ pf, const unsigned long long* __restrict__ pi,
                                                             const double* __restrict__ ps, double inv_n, int nb, Stats* st) {
-    __shared__ float s[4][256];
-    __shared__ unsigned long long si[2][256];
-    __shared__ double sd[2][256];
+    __shared__ MinMaxRed r;
     const int i = threadIdx.x;
     float mnT = 3.4e38f, mxT = -3.4e38f, mnP = 3.4e38f, mxP = -3.4e38f;
     unsigned long long amn = ~0ull, amx = ~0ull;
@@ -108,23 +112,52 @@ __global__ void __launch_bounds__(256) minmax_finish_kernel(const float* __restr
         if (pf[4 * k + 3] > mxP || (pf[4 * k + 3] == mxP && pi[2 * k + 1] < amx)) { mxP = pf[4 * k + 3]; amx = pi[2 * k + 1]; }
         sT += ps[2 * k]; sP += ps[2 * k + 1];
     }
-    s[0][i] = mnT; s[1][i] = mxT; s[2][i] = mnP; s[3][i] = mxP; si[0][i] = amn; si[1][i] = amx;
-    sd[0][i] = sT; sd[1][i] = sP;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {          // ties go to the smallest flat index, as a serial scan would pick
-        if (i < o) {
-            sd[0][i] += sd[0][i + o]; sd[1][i] += sd[1][i + o];
-            s[0][i] = fminf(s[0][i], s[0][i + o]);
-            s[1][i] = fmaxf(s[1][i], s[1][i + o]);
-            if (s[2][i + o] < s[2][i] || (s[2][i + o] == s[2][i] && si[0][i + o] < si[0][i])) { s[2][i] = s[2][i + o]; si[0][i] = si[0][i + o]; }
-            if (s[3][i + o] > s[3][i] || (s[3][i + o] == s[3][i] && si[1][i + o] < si[1][i])) { s[3][i] = s[3][i + o]; si[1][i] = si[1][i + o]; }
-        }
-        __syncthreads();
-    }
+    minmax_tree(r, i, mnT, mxT, mnP, mxP, amn, amx, sT, sP);
     if (i) return;
-    st->minT = s[0][0]; st->maxT = s[1][0]; st->minP = s[2][0]; st->maxP = s[3][0]; st->argminP = si[0][0]; st->argmaxP = si[1][0];
+    st->minT = r.s[0][0]; st->maxT = r.s[1][0]; st->minP = r.s[2][0]; st->maxP = r.s[3][0]; st->argminP = r.si[0][0]; st->argmaxP = r.si[1][0];
     st->sumS = 0.f; st->gc1 = 0.f; st->gc2 = 0.f; st->sumdy = 0.f;
-    st->pivT = (float)(sd[0][0] * inv_n); st->pivP = (float)(sd[1][0] * inv_n);
+    st->pivT = (float)(r.sd[0][0] * inv_n); st->pivP = (float)(r.sd[1][0] * inv_n);
+}
+
+// block -> 16x16 tile (origin y0, x0) of plane (n, c) of a stack of C-channel planes, and this thread's pixel (ly, lx) of the tile
+struct Tile { int c, n, y0, x0, ly, lx; };
+__device__ __forceinline__ Tile tile_of(int tiles_x, int tiles_y, int C) {
+    int b = blockIdx.x;
+    const int tx = b % tiles_x; b /= tiles_x;
+    const int ty = b % tiles_y; b /= tiles_y;
+    return Tile{b % C, b / C, ty * TS, tx * TS, (int)threadIdx.x / TS, (int)threadIdx.x % TS};
+}
+// halo tile (TL x TL from the tile's origin) of the pixel pair of an NHWC array less (pT, pP), zero outside the image; ends in a barrier
+__device__ __forceinline__ void stage_pair(float (*sx)[PT], float (*sq)[PT], const float* __restrict__ t, const float* __restrict__ p,
+                                           float pT, float pP, const Tile& tl, int H, int W, int C) {
+    for (int i = threadIdx.x; i < TL * TL; i += 256) {
+        const int r = i / TL, cc = i % TL;
+        const int y = tl.y0 + r, x = tl.x0 + cc;
+        float a = 0.f, q = 0.f;
+        if (y < H && x < W) {
+            const size_t o = (((size_t)tl.n * H + y) * W + x) * C + tl.c;
+            a = t[o] - pT; q = p[o] - pP;
+        }
+        sx[r][cc] = a; sq[r][cc] = q;
+    }
+    __syncthreads();
+}
+// halo tiles of the three derivative maps (planes of Ho x Wo) for a tile of INPUT pixels: input pixel (y,x) is covered by outputs
+// (y-i, x-j), i,j in [0,10], so the halo tile starts at (y0-10, x0-10); zero outside the map; ends in a barrier
+__device__ __forceinline__ void stage_maps3(float (*s1)[PT], float (*s2)[PT], float (*s3)[PT], const float* __restrict__ dmu,
+                                            const float* __restrict__ da, const float* __restrict__ db, const Tile& tl, int Ho, int Wo,
+                                            int C) {
+    for (int i = threadIdx.x; i < TL * TL; i += 256) {
+        const int r = i / TL, cc = i % TL;
+        const int oy = tl.y0 - (KF - 1) + r, ox = tl.x0 - (KF - 1) + cc;
+        float a = 0.f, bb = 0.f, d = 0.f;
+        if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
+            const size_t o = (((size_t)tl.n * C + tl.c) * Ho + oy) * Wo + ox;
+            a = dmu[o]; bb = da[o]; d = db[o];
+        }
+        s1[r][cc] = a; s2[r][cc] = bb; s3[r][cc] = d;
+    }
+    __syncthreads();
 }
 
 // Gaussian-filtered moments (mean x, mean q, E[xq], E[x^2 + q^2]) of this thread's output pixel of the tile: row pass of
@@ -175,21 +208,49 @@ __device__ __forceinline__ void sep_transposed3(const float (*s1)[PT], const flo
     }
 }
 
+// The SSIM of one window from its moments.  m holds moments of the pivoted pixels: the contrast-structure term cs = N2 / D2 is made of
+// them alone, the luminance term lum = N1 / D1 of the means of the shifted arrays, mx = pv.oT + m.mx, my = pv.oP + m.my.  The
+// derivatives are those of any f(lum, cs), given v = df/dlum and u = df/dcs (S = lum cs: v = cs, u = lum), w.r.t. the prediction's
+// mean (dlum_dmy, dcs_dmy), the moments A = E[xq] and Bq = E[x^2 + q^2], and the constants c1, c2
+__device__ __forceinline__ float drange_of(const Stats* __restrict__ st) { return fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP); }
+struct SsimConsts { float c1, c2; };
+__device__ __forceinline__ SsimConsts ssim_consts(const Stats* __restrict__ st) {
+    const float drange = drange_of(st);
+    return SsimConsts{(0.01f * drange) * (0.01f * drange), (0.03f * drange) * (0.03f * drange)};
+}
+// d/ddrange through c1 = (k1 L)^2, c2 = (k2 L)^2, given the sums g1, g2 of the windows' d/dc1, d/dc2
+__device__ __forceinline__ float drange_grad(const Stats* __restrict__ st, float g1, float g2) {
+    const float drange = drange_of(st);
+    return g1 * 2.f * 0.01f * 0.01f * drange + g2 * 2.f * 0.03f * 0.03f * drange;
+}
+struct SsimPoint {
+    float mxs, mys, mx, my, N1, D1, N2, D2, lum, cs;
+    __device__ __forceinline__ SsimPoint(MsMoments m, Pivot pv, SsimConsts k) {
+        mxs = m.mx; mys = m.my;
+        mx = pv.oT + m.mx; my = pv.oP + m.my;
+        N1 = 2.f * mx * my + k.c1; D1 = mx * mx + my * my + k.c1;
+        N2 = 2.f * m.A - 2.f * m.mx * m.my + k.c2; D2 = m.Bq - m.mx * m.mx - m.my * m.my + k.c2;
+        lum = N1 / D1; cs = N2 / D2;
+    }
+    __device__ __forceinline__ float dlum_dmy() const { return 2.f * mx / D1 - N1 * 2.f * my / (D1 * D1); }
+    __device__ __forceinline__ float dcs_dmy() const { return -2.f * mxs / D2 + N2 * 2.f * mys / (D2 * D2); }
+    __device__ __forceinline__ float dS_dA(float u) const { return u * 2.f / D2; }
+    __device__ __forceinline__ float dS_dB(float u) const { return -u * N2 / (D2 * D2); }
+    __device__ __forceinline__ float dS_dc1(float v) const { return v * (D1 - N1) / (D1 * D1); }
+    __device__ __forceinline__ float dS_dc2(float u) const { return u * (D2 - N2) / (D2 * D2); }
+};
+
 // omega[(m, c), oy, ox] = sum_ij g[i] g[j] w[m, oy + i, ox + j, c]; one block = one 16x16 tile of plane (m, c) of the w_batch x cw
 // weight planes; partial[block] = the tile's sum of omega.  All taps and weights are >= 0: omega == 0 iff the whole window is masked.
 __global__ void __launch_bounds__(256) omega_kernel(const float* __restrict__ w, int H, int W, int cw, int Ho, int Wo, int tiles_x,
                                                     int tiles_y, Gauss gk, float* __restrict__ omega, float* __restrict__ partial) {
     __shared__ float sw[TL][PT], h[TL][TS];
     __shared__ float red[256];
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; b /= tiles_y;
-    const int c = b % cw, m = b / cw;
-    const int oy0 = ty * TS, ox0 = tx * TS;
+    const Tile tl = tile_of(tiles_x, tiles_y, cw);          // n: the map m
     for (int i = threadIdx.x; i < TL * TL; i += 256) {
         const int r = i / TL, cc = i % TL;
-        const int y = oy0 + r, x = ox0 + cc;
-        sw[r][cc] = (y < H && x < W) ? w[(((size_t)m * H + y) * W + x) * cw + c] : 0.f;
+        const int y = tl.y0 + r, x = tl.x0 + cc;
+        sw[r][cc] = (y < H && x < W) ? w[(((size_t)tl.n * H + y) * W + x) * cw + tl.c] : 0.f;
     }
     __syncthreads();
     for (int it = threadIdx.x; it < TL * TS; it += 256) {
@@ -200,20 +261,15 @@ __global__ void __launch_bounds__(256) omega_kernel(const float* __restrict__ w,
         h[r][cx] = a;
     }
     __syncthreads();
-    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
-    const int oy = oy0 + ly, ox = ox0 + lx;
+    const int oy = tl.y0 + tl.ly, ox = tl.x0 + tl.lx;
     float om = 0.f;
     if (oy < Ho && ox < Wo) {
 #pragma unroll
-        for (int i = 0; i < KF; ++i) om += gk.g[i] * h[ly + i][lx];
-        omega[(((size_t)m * cw + c) * Ho + oy) * Wo + ox] = om;
+        for (int i = 0; i < KF; ++i) om += gk.g[i] * h[tl.ly + i][tl.lx];
+        omega[(((size_t)tl.n * cw + tl.c) * Ho + oy) * Wo + ox] = om;
     }
     red[threadIdx.x] = om;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -228,30 +284,18 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
                                                        int cw) {
     __shared__ float sx[TL][PT], sq[TL][PT], hrow[4][TL][TS];
     __shared__ float red[3][256];
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; b /= tiles_y;
-    const int c = b % C, n = b / C;
+    const Tile tl = tile_of(tiles_x, tiles_y, C);
+    const int c = tl.c, n = tl.n;
     const Pivot pv = pivot_of(st, true);
-    const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
-    const float c1 = (0.01f * drange) * (0.01f * drange), c2 = (0.03f * drange) * (0.03f * drange);
-    const int oy0 = ty * TS, ox0 = tx * TS;
-    for (int i = threadIdx.x; i < TL * TL; i += 256) {
-        const int r = i / TL, cc = i % TL;
-        const int y = oy0 + r, x = ox0 + cc;
-        float a = 0.f, q = 0.f;
-        if (y < H && x < W) {
-            const size_t o = (((size_t)n * H + y) * W + x) * C + c;
-            a = t[o] - pv.pT; q = p[o] - pv.pP;
-        }
-        sx[r][cc] = a; sq[r][cc] = q;
-    }
-    __syncthreads();
-    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
-    const int oy = oy0 + ly, ox = ox0 + lx;
+    const SsimConsts kc = ssim_consts(st);
+    stage_pair(sx, sq, t, p, pv.pT, pv.pP, tl, H, W, C);
+    const int oy = tl.y0 + tl.ly, ox = tl.x0 + tl.lx;
     float S = 0.f, g1 = 0.f, g2 = 0.f;
     const MsMoments mom = sep_moments(sx, sq, hrow, gk);
     if (oy < Ho && ox < Wo) {
+        // SsimPoint's arithmetic, written out: through the struct the compiler packs the column pass of the WEIGHTED instantiation
+        // in pairs and fuses fewer of its multiply-adds, which moves the last bits of the loss
+        const float c1 = kc.c1, c2 = kc.c2;
         const float mxs = mom.mx, mys = mom.my, A = mom.A, Bq = mom.Bq;      // moments of the pivoted pixels
         const float mx = pv.oT + mxs, my = pv.oP + mys;                      // means of the shifted arrays: luminance only
         const float N1 = 2.f * mx * my + c1, D1 = mx * mx + my * my + c1;
@@ -274,12 +318,7 @@ __global__ void __launch_bounds__(256) ssim_fwd_kernel(const float* __restrict__
         db[o] = vb;
     }
     red[0][threadIdx.x] = S; red[1][threadIdx.x] = g1; red[2][threadIdx.x] = g2;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0)
         for (int k = 0; k < 3; ++k) partial[(size_t)blockIdx.x * 3 + k] = red[k][0];
 }
@@ -300,13 +339,7 @@ __global__ void __launch_bounds__(256) compact_partials_kernel(const float* __re
         for (int k = 0; k < K; ++k) a[k] += (double)in[(size_t)r * K + k];
 #pragma unroll
     for (int k = 0; k < K; ++k) red[k][threadIdx.x] = a[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-#pragma unroll
-            for (int k = 0; k < K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0)
 #pragma unroll
         for (int k = 0; k < K; ++k) out[(size_t)blockIdx.x * K + k] = (float)red[k][0];
@@ -318,63 +351,51 @@ __global__ void sum3_kernel(const float* __restrict__ partial, int nb, Stats* st
     for (int k = threadIdx.x; k < nb; k += 256)
         for (int j = 0; j < 3; ++j) a[j] += partial[(size_t)k * 3 + j];
     for (int j = 0; j < 3; ++j) red[j][threadIdx.x] = a[j];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0) { st->sumS = (float)red[0][0]; st->gc1 = (float)red[1][0]; st->gc2 = (float)red[2][0]; }
 }
 
-// one block = one 16x16 tile of INPUT pixels of plane (n,c): transposed 11x11 filter of the derivative maps.  WEIGHTED: the maps
-// already carry omega; coef (-weight / 2 here) is completed by 1 / sum omega from the device scalar
-template <bool WEIGHTED>
-__global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__ t, const float* __restrict__ p, int H, int W,
+// one block = one 16x16 tile of INPUT pixels of plane (n,c): transposed 11x11 filter of the derivative maps, combined with the pivoted
+// pixels the moments were taken of (raw: t, p are y_true / y_pred themselves, pivoted here; else images of the pivoted pyramid);
+// dpred (+)= coef * that.  WEIGHTED: the maps already carry omega; coef (-weight / 2 here) is completed by 1 / sum omega from the
+// device scalar.  REDUCE: partial[block] = the tile's sum (for the min-shift term); the pyramid levels of the multi-scale loss run
+// without it, with coef = 1 and accumulate = 0 (both exact)
+template <bool WEIGHTED, bool REDUCE>
+__global__ void __launch_bounds__(256) ssim_bwd_kernel(const float* __restrict__ t, const float* __restrict__ p, int raw, int H, int W,
                                                        int C, int Ho, int Wo, int tiles_x, int tiles_y, Gauss gk,
                                                        const Stats* __restrict__ st, const float* __restrict__ dmu,
                                                        const float* __restrict__ da, const float* __restrict__ db,
                                                        float coef, float* __restrict__ dpred, int accumulate,
                                                        float* __restrict__ partial, const float* __restrict__ inv_so) {
     __shared__ float s1[TL][PT], s2[TL][PT], s3[TL][PT], hrow[3][TL][TS];
-    __shared__ float red[256];
     if (WEIGHTED) coef *= inv_so[0];
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; b /= tiles_y;
-    const int c = b % C, n = b / C;
-    const Pivot pv = pivot_of(st, true);
-    const int y0 = ty * TS, x0 = tx * TS;
-    // input pixel (y,x) is covered by outputs (y-i, x-j), i,j in [0,10]: halo tile starts at (y0-10, x0-10)
-    for (int i = threadIdx.x; i < TL * TL; i += 256) {
-        const int r = i / TL, cc = i % TL;
-        const int oy = y0 - (KF - 1) + r, ox = x0 - (KF - 1) + cc;
-        float a = 0.f, bb = 0.f, d = 0.f;
-        if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
-            const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
-            a = dmu[o]; bb = da[o]; d = db[o];
-        }
-        s1[r][cc] = a; s2[r][cc] = bb; s3[r][cc] = d;
-    }
-    __syncthreads();
-    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
-    const int y = y0 + ly, x = x0 + lx;
+    const Tile tl = tile_of(tiles_x, tiles_y, C);
+    const float pT = raw ? st->pivT : 0.f, pP = raw ? st->pivP : 0.f;
+    stage_maps3(s1, s2, s3, dmu, da, db, tl, Ho, Wo, C);
+    const int y = tl.y0 + tl.ly, x = tl.x0 + tl.lx;
     float g = 0.f;
     float T1, T2, T3;
     sep_transposed3(s1, s2, s3, hrow, gk, T1, T2, T3);
     if (y < H && x < W) {
-        const size_t o = (((size_t)n * H + y) * W + x) * C + c;
-        const float xv = t[o] - pv.pT, qv = p[o] - pv.pP;          // the pivoted pixels the moments were taken of
+        const size_t o = (((size_t)tl.n * H + y) * W + x) * C + tl.c;
+        const float xv = t[o] - pT, qv = p[o] - pP;
         g = coef * (T1 + xv * T2 + 2.f * qv * T3);
         dpred[o] = accumulate ? dpred[o] + g : g;
     }
-    red[threadIdx.x] = g;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
+    if constexpr (REDUCE) {
+        __shared__ float red[256];
+        red[threadIdx.x] = g;
+        block_tree_sum(red, threadIdx.x);
+        if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
     }
-    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+// the scalar terms of the gradient, each added to one element of dpred: ddr (the range, through c1 and c2 of every window) where the
+// prediction sets that end of the range, sumdy (the min-shift q = p - min(p)) at the prediction's minimum
+__device__ __forceinline__ void route_range_and_shift(const Stats* __restrict__ st, float ddr, float sumdy, float* __restrict__ dpred) {
+    if (st->maxP > st->maxT) dpred[st->argmaxP] += ddr;      // tf.maximum routes ties to its first argument (y_true)
+    if (st->minP < st->minT) dpred[st->argminP] -= ddr;
+    if (st->minP < 0.f) dpred[st->argminP] -= sumdy;
 }
 
 // WEIGHTED: inv_m and the completion of coef (-weight / 2 here) are 1 / sum omega from the device scalar; a zero sum gives loss 0
@@ -386,41 +407,62 @@ __global__ void dssim_finish_kernel(const float* __restrict__ partial, int nb, S
     double a = 0;
     for (int k = threadIdx.x; k < nb; k += 256) a += partial[k];
     red[threadIdx.x] = a;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x != 0) return;
     const float sumdy = (float)red[0];
     if (WEIGHTED) { inv_m = inv_so[0]; coef *= inv_m; }
     const float v = (WEIGHTED && inv_m == 0.f) ? 0.f : weight * (0.5f - 0.5f * st->sumS * inv_m);
     loss_out[0] = accumulate_loss ? loss_out[0] + v : v;
     if (!dpred) return;
-    const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
-    // dL/ddrange through c1=(k1*L)^2, c2=(k2*L)^2
-    const float ddr = coef * (st->gc1 * 2.f * 0.01f * 0.01f * drange + st->gc2 * 2.f * 0.03f * 0.03f * drange);
-    if (st->maxP > st->maxT) dpred[st->argmaxP] += ddr;      // tf.maximum routes ties to its first argument (y_true)
-    if (st->minP < st->minT) dpred[st->argminP] -= ddr;
-    if (st->minP < 0.f) dpred[st->argminP] -= sumdy;         // q = p - min(p)
+    route_range_and_shift(st, coef * drange_grad(st, st->gc1, st->gc2), sumdy, dpred);
 }
 
-struct Layout { size_t stats, pf, pi, ps, maps, part, part2, total; int nb_mm; };
-Layout layout(int N, int H, int W, int C) {
-    Layout l;
-    const int Ho = H - KF + 1, Wo = W - KF + 1;
-    l.nb_mm = 512;
+// ---- host: the workspace.  Bump carves 256-byte-aligned arrays off a base in order; the size functions run the same carving on a
+// null base and read the end offset, so a size and its carving cannot disagree
+struct Bump {
+    uintptr_t base;
     size_t o = 0;
-    auto bump = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    l.stats = bump(sizeof(Stats));
-    l.pf = bump((size_t)l.nb_mm * 4 * sizeof(float));
-    l.pi = bump((size_t)l.nb_mm * 2 * sizeof(unsigned long long));
-    l.ps = bump((size_t)l.nb_mm * 2 * sizeof(double));
-    l.maps = bump(3 * (size_t)N * C * Ho * Wo * sizeof(float));
-    const size_t tiles = (size_t)N * C * cdiv(H, TS) * cdiv(W, TS);
-    l.part = bump(tiles * 3 * sizeof(float));
-    l.part2 = bump((size_t)COMPACT_G * 3 * sizeof(float));
-    l.total = o;
+    explicit Bump(void* ws) : base(reinterpret_cast<uintptr_t>(ws)) {}
+    template <class T> T* take(size_t count) {
+        T* r = reinterpret_cast<T*>(base + o);
+        o += (count * sizeof(T) + 255) & ~(size_t)255;
+        return r;
+    }
+};
+// head of every workspace here: the Stats and the nb_mm per-block results of the min/max pass
+struct StatsScratch { Stats* st; float* pf; unsigned long long* pi; double* ps; int nb_mm; };
+StatsScratch carve_stats(Bump& b) {
+    StatsScratch h;
+    h.nb_mm = 512;
+    h.st = b.take<Stats>(1);
+    h.pf = b.take<float>((size_t)h.nb_mm * 4);
+    h.pi = b.take<unsigned long long>((size_t)h.nb_mm * 2);
+    h.ps = b.take<double>((size_t)h.nb_mm * 2);
+    return h;
+}
+// Stats of the n elements of (t, p): extremes, the prediction's arg-extremes, the pivots; the loss sums zeroed
+void run_minmax(hipStream_t s, const float* t, const float* p, size_t n, const StatsScratch& h) {
+    const int nb = (int)std::min<size_t>(h.nb_mm, cdivz(n, 256));
+    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, t, p, n, h.pf, h.pi, h.ps);
+    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, h.pf, h.pi, h.ps, 1.0 / (double)n, nb, h.st);
+}
+// the VALID map of an (H, W) image and its tiles
+struct MapGeom { int Ho, Wo, txo, tyo; };
+MapGeom map_geom(int H, int W) {
+    const int Ho = H - KF + 1, Wo = W - KF + 1;
+    return MapGeom{Ho, Wo, cdiv(Wo, TS), cdiv(Ho, TS)};
+}
+
+struct Layout { StatsScratch hdr; MapGeom g; float *maps, *part, *part2; size_t total; };
+Layout layout(void* ws, int N, int H, int W, int C) {
+    Bump b(ws);
+    Layout l;
+    l.g = map_geom(H, W);
+    l.hdr = carve_stats(b);
+    l.maps = b.take<float>(3 * (size_t)N * C * l.g.Ho * l.g.Wo);
+    l.part = b.take<float>((size_t)N * C * cdiv(H, TS) * cdiv(W, TS) * 3);
+    l.part2 = b.take<float>((size_t)COMPACT_G * 3);
+    l.total = b.o;
     return l;
 }
 
@@ -483,56 +525,33 @@ __global__ void __launch_bounds__(256) ms_ssim_kernel(const float* __restrict__ 
                                                       float* __restrict__ db, float* __restrict__ partial) {
     __shared__ float sx[TL][PT], sq[TL][PT], hrow[4][TL][TS];
     __shared__ float red[2][256];
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; b /= tiles_y;
-    const int c = b % C, n = b / C;
+    const Tile tl = tile_of(tiles_x, tiles_y, C);
+    const int c = tl.c, n = tl.n;
     const Pivot pv = pivot_of(st, shift != 0);
-    const float pT = raw ? pv.pT : 0.f, pP = raw ? pv.pP : 0.f;
-    const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
-    const float c1 = (0.01f * drange) * (0.01f * drange), c2 = (0.03f * drange) * (0.03f * drange);
-    const int oy0 = ty * TS, ox0 = tx * TS;
-    for (int i = threadIdx.x; i < TL * TL; i += 256) {
-        const int r = i / TL, cc = i % TL;
-        const int y = oy0 + r, xx = ox0 + cc;
-        float a = 0.f, v = 0.f;
-        if (y < H && xx < W) {
-            const size_t o = (((size_t)n * H + y) * W + xx) * C + c;
-            a = x[o] - pT; v = q[o] - pP;
-        }
-        sx[r][cc] = a; sq[r][cc] = v;
-    }
-    __syncthreads();
-    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
-    const int oy = oy0 + ly, ox = ox0 + lx;
+    const SsimConsts kc = ssim_consts(st);
+    stage_pair(sx, sq, x, q, raw ? pv.pT : 0.f, raw ? pv.pP : 0.f, tl, H, W, C);
+    const int oy = tl.y0 + tl.ly, ox = tl.x0 + tl.lx;
     float r0 = 0.f, r1 = 0.f;
     const MsMoments m = sep_moments(sx, sq, hrow, gk);
     if (oy < Ho && ox < Wo) {
-        const float mx = pv.oT + m.mx, my = pv.oP + m.my;          // m: moments of the pivoted pixels; mx, my: luminance only
-        const float N1 = 2.f * mx * my + c1, D1 = mx * mx + my * my + c1;
-        const float N2 = 2.f * m.A - 2.f * m.mx * m.my + c2, D2 = m.Bq - m.mx * m.mx - m.my * m.my + c2;
-        const float lum = N1 / D1, cs = N2 / D2;
+        const SsimPoint s(m, pv, kc);
         if (MODE == 0) {
-            r0 = lum * cs; r1 = cs;
+            r0 = s.lum * s.cs; r1 = s.cs;
         } else {
             const float inv_m = 1.f / ((float)Ho * (float)Wo);
             const float ws = gs[n * C + c] * inv_m, wc = gc[n * C + c] * inv_m;
-            const float dcs_dmy = -2.f * m.mx / D2 + N2 * 2.f * m.my / (D2 * D2);
-            const float dlum_dmy = 2.f * mx / D1 - N1 * 2.f * my / (D1 * D1);
+            const float dcs_dmy = s.dcs_dmy(), dlum_dmy = s.dlum_dmy();
             const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
-            dmu[o] = ws * (cs * dlum_dmy + lum * dcs_dmy) + wc * dcs_dmy;
-            da[o] = (ws * lum + wc) * 2.f / D2;
-            db[o] = -(ws * lum + wc) * N2 / (D2 * D2);
-            r0 = ws * cs * (D1 - N1) / (D1 * D1);                        // d/dc1
-            r1 = (ws * lum + wc) * (D2 - N2) / (D2 * D2);                // d/dc2
+            const float v = ws * s.cs, u = ws * s.lum + wc;              // d/dlum, d/dcs of ws lum cs + wc cs
+            dmu[o] = ws * (s.cs * dlum_dmy + s.lum * dcs_dmy) + wc * dcs_dmy;
+            da[o] = s.dS_dA(u);
+            db[o] = s.dS_dB(u);
+            r0 = s.dS_dc1(v);
+            r1 = s.dS_dc2(u);
         }
     }
     red[0][threadIdx.x] = r0; red[1][threadIdx.x] = r1;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) { red[0][threadIdx.x] += red[0][threadIdx.x + o]; red[1][threadIdx.x] += red[1][threadIdx.x + o]; }
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0) { partial[(size_t)blockIdx.x * 2] = red[0][0]; partial[(size_t)blockIdx.x * 2 + 1] = red[1][0]; }
 }
 
@@ -575,47 +594,10 @@ __global__ void __launch_bounds__(256) ms_combine_kernel(const float* __restrict
         }
     }
     red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0) {
         const float v = weight * (0.5f - 0.5f * (float)(red[0] / NC));
         loss_out[0] = accumulate_loss ? loss_out[0] + v : v;
-    }
-}
-
-// transposed 11x11 filter of the derivative maps -> gradient w.r.t. the scale's q image (stored, not accumulated)
-__global__ void __launch_bounds__(256) ms_bwd_kernel(const float* __restrict__ x, const float* __restrict__ q, int raw, int H, int W, int C,
-                                                     int Ho, int Wo, int tiles_x, int tiles_y, Gauss gk, const Stats* __restrict__ st,
-                                                     const float* __restrict__ dmu, const float* __restrict__ da,
-                                                     const float* __restrict__ db, float* __restrict__ gq) {
-    __shared__ float s1[TL][PT], s2[TL][PT], s3[TL][PT], hrow[3][TL][TS];
-    int b = blockIdx.x;
-    const int tx = b % tiles_x; b /= tiles_x;
-    const int ty = b % tiles_y; b /= tiles_y;
-    const int c = b % C, n = b / C;
-    const float pT = raw ? st->pivT : 0.f, pP = raw ? st->pivP : 0.f;
-    const int y0 = ty * TS, x0 = tx * TS;
-    for (int i = threadIdx.x; i < TL * TL; i += 256) {
-        const int r = i / TL, cc = i % TL;
-        const int oy = y0 - (KF - 1) + r, ox = x0 - (KF - 1) + cc;
-        float a = 0.f, bb = 0.f, d = 0.f;
-        if (oy >= 0 && oy < Ho && ox >= 0 && ox < Wo) {
-            const size_t o = (((size_t)n * C + c) * Ho + oy) * Wo + ox;
-            a = dmu[o]; bb = da[o]; d = db[o];
-        }
-        s1[r][cc] = a; s2[r][cc] = bb; s3[r][cc] = d;
-    }
-    __syncthreads();
-    const int ly = threadIdx.x / TS, lx = threadIdx.x % TS;
-    const int y = y0 + ly, xx = x0 + lx;
-    float T1, T2, T3;
-    sep_transposed3(s1, s2, s3, hrow, gk, T1, T2, T3);
-    if (y < H && xx < W) {
-        const size_t o = (((size_t)n * H + y) * W + xx) * C + c;
-        gq[o] = T1 + (x[o] - pT) * T2 + 2.f * (q[o] - pP) * T3;
     }
 }
 
@@ -630,11 +612,7 @@ __global__ void __launch_bounds__(256) ms_apply_kernel(const float* __restrict__
         s += g;
     }
     red[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
@@ -646,100 +624,82 @@ __global__ void __launch_bounds__(256) ms_finish_kernel(const float* __restrict_
     for (int k = threadIdx.x; k < nb_sum; k += 256) a += sum_partial[k];
     for (int k = threadIdx.x; k < ng; k += 256) { g1 += gcp[(size_t)k * 2]; g2 += gcp[(size_t)k * 2 + 1]; }
     red[0][threadIdx.x] = a; red[1][threadIdx.x] = g1; red[2][threadIdx.x] = g2;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int j = 0; j < 3; ++j) red[j][threadIdx.x] += red[j][threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x != 0) return;
-    const float drange = fmaxf(st->maxT, st->maxP) - fminf(st->minT, st->minP);
-    const float ddr = (float)red[1][0] * 2.f * 0.01f * 0.01f * drange + (float)red[2][0] * 2.f * 0.03f * 0.03f * drange;
-    if (st->maxP > st->maxT) dpred[st->argmaxP] += ddr;
-    if (st->minP < st->minT) dpred[st->argminP] -= ddr;
-    if (st->minP < 0.f) dpred[st->argminP] -= (float)red[0][0];
+    route_range_and_shift(st, drange_grad(st, (float)red[1][0], (float)red[2][0]), (float)red[0][0], dpred);
 }
 
 struct MsLayout {
-    size_t stats, pf, pi, ps, imgs, grads, maps, part, part2, gcp, means, gw, total;
-    size_t img_off[MS_SCALES], grad_off[MS_SCALES], gcp_off[MS_SCALES];
+    StatsScratch hdr;
+    float *imgs, *grads, *maps, *part, *part2, *gcp, *means, *gw;
+    size_t total, img_off[MS_SCALES], grad_off[MS_SCALES], gcp_off[MS_SCALES];      // offsets in floats
     MsDims d;
-    int nb_mm;
+    MapGeom g[MS_SCALES];
 };
-MsLayout ms_layout(int N, int H, int W, int C) {
+MsLayout ms_layout(void* ws, int N, int H, int W, int C) {
+    Bump b(ws);
     MsLayout l;
     l.d.H[0] = H; l.d.W[0] = W;
     for (int k = 1; k < MS_SCALES; ++k) { l.d.H[k] = (l.d.H[k - 1] + 1) / 2; l.d.W[k] = (l.d.W[k - 1] + 1) / 2; }
-    l.nb_mm = 512;
-    size_t o = 0;
-    auto bump = [&](size_t bytes) { size_t r = o; o += (bytes + 255) & ~(size_t)255; return r; };
-    l.stats = bump(sizeof(Stats));
-    l.pf = bump((size_t)l.nb_mm * 4 * sizeof(float));
-    l.pi = bump((size_t)l.nb_mm * 2 * sizeof(unsigned long long));
-    l.ps = bump((size_t)l.nb_mm * 2 * sizeof(double));
+    l.hdr = carve_stats(b);
     size_t img = 0, grad = 0, gcp = 0;
     for (int k = 0; k < MS_SCALES; ++k) {
         const size_t n = (size_t)N * l.d.H[k] * l.d.W[k] * C;
         if (k > 0) { l.img_off[k] = img; img += 2 * n; } else l.img_off[k] = 0;      // x_k then q_k (k >= 1)
         l.grad_off[k] = grad; grad += n;
         l.gcp_off[k] = gcp;
-        gcp += (size_t)N * C * cdiv(l.d.H[k] - KF + 1, TS) * cdiv(l.d.W[k] - KF + 1, TS);
+        l.g[k] = map_geom(l.d.H[k], l.d.W[k]);
+        gcp += (size_t)N * C * l.g[k].tyo * l.g[k].txo;
     }
-    l.imgs = bump(img * sizeof(float));
-    l.grads = bump(grad * sizeof(float));
-    l.maps = bump(3 * (size_t)N * C * (H - KF + 1) * (W - KF + 1) * sizeof(float));
-    l.part = bump(std::max<size_t>((size_t)N * C * cdiv(H - KF + 1, TS) * cdiv(W - KF + 1, TS) * 2, 4096) * sizeof(float));
-    l.part2 = bump((size_t)COMPACT_G * 2 * sizeof(float));
-    l.gcp = bump(gcp * 2 * sizeof(float));
-    l.means = bump((size_t)2 * MS_SCALES * N * C * sizeof(float));
-    l.gw = bump((size_t)2 * MS_SCALES * N * C * sizeof(float));
-    l.total = o;
+    l.imgs = b.take<float>(img);
+    l.grads = b.take<float>(grad);
+    l.maps = b.take<float>(3 * (size_t)N * C * l.g[0].Ho * l.g[0].Wo);
+    l.part = b.take<float>(std::max<size_t>((size_t)N * C * l.g[0].tyo * l.g[0].txo * 2, 4096));
+    l.part2 = b.take<float>((size_t)COMPACT_G * 2);
+    l.gcp = b.take<float>(gcp * 2);
+    l.means = b.take<float>((size_t)2 * MS_SCALES * N * C);      // [ssim: scales x NC][cs: scales x NC]
+    l.gw = b.take<float>((size_t)2 * MS_SCALES * N * C);         // [gs: scales x NC][gc: scales x NC]
+    l.total = b.o;
     return l;
 }
 }  // namespace
 
-size_t dssim_workspace_bytes(int N, int H, int W, int C) { return layout(N, H, W, C).total; }
+size_t dssim_workspace_bytes(int N, int H, int W, int C) { return layout(nullptr, N, H, W, C).total; }
 
 void weight_sum_finish(hipStream_t s, const float* partial, int nb, double mult, float* inv_out);     // losses.hip
 
 namespace {
 // the weight side of one weighted call: maps, their batch / channel counts, the device scalar 1 / sum omega, and the extra workspace
 struct DssimWeights { const float* w; int wb, cw; float* inv_so; float* ext; };
-size_t omega_floats(int H, int W, int wb, int cw) { return ((size_t)wb * cw * (H - KF + 1) * (W - KF + 1) + 63) & ~(size_t)63; }
-size_t omega_tiles(int H, int W, int wb, int cw) { return (size_t)wb * cw * cdiv(H - KF + 1, TS) * cdiv(W - KF + 1, TS); }
+size_t omega_floats(const MapGeom& g, int wb, int cw) { return ((size_t)wb * cw * g.Ho * g.Wo + 63) & ~(size_t)63; }
+size_t omega_tiles(const MapGeom& g, int wb, int cw) { return (size_t)wb * cw * g.tyo * g.txo; }
 
 template <bool WEIGHTED>
 void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W, int C, float weight,
                float* loss_out, int accumulate_loss, float* workspace, size_t workspace_bytes, const DssimWeights& dw) {
     DL4DS_REQUIRE(H >= KF && W >= KF, "dssim needs grids of at least 11x11");
-    Layout l = layout(N, H, W, C);
+    const Layout l = layout(workspace, N, H, W, C);
     DL4DS_REQUIRE(workspace_bytes >= l.total, "dssim workspace too small");
-    char* base = reinterpret_cast<char*>(workspace);
-    Stats* st = reinterpret_cast<Stats*>(base + l.stats);
-    float* pf = reinterpret_cast<float*>(base + l.pf);
-    unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + l.pi);
-    double* psum = reinterpret_cast<double*>(base + l.ps);
-    const int Ho = H - KF + 1, Wo = W - KF + 1;
+    Stats* st = l.hdr.st;
+    const int Ho = l.g.Ho, Wo = l.g.Wo, txo = l.g.txo, tyo = l.g.tyo;
     const size_t msz = (size_t)N * C * Ho * Wo;
-    float* dmu = reinterpret_cast<float*>(base + l.maps);
+    float* dmu = l.maps;
     float* da = dmu + msz;
     float* db = da + msz;
-    float* part = reinterpret_cast<float*>(base + l.part);
+    float* part = l.part;
+    float* part2 = l.part2;
     const size_t n = (size_t)N * H * W * C;
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "dssim", 0.0, 4.0 * (double)n * 8);
-    const int nb = (int)std::min<size_t>(l.nb_mm, cdivz(n, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n, pf, pi, psum);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n, nb, st);
-    const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
+    run_minmax(s, y_true, y_pred, n, l.hdr);
     const int nbf = N * C * txo * tyo;
     const float* omega = nullptr;
     const float* inv_so = nullptr;
     int wrep = 1, cw = 1;
     if (WEIGHTED) {
         float* om = dw.ext;
-        float* opart = dw.ext + omega_floats(H, W, dw.wb, dw.cw);
-        const int nbo = (int)omega_tiles(H, W, dw.wb, dw.cw);
+        float* opart = dw.ext + omega_floats(l.g, dw.wb, dw.cw);
+        const int nbo = (int)omega_tiles(l.g, dw.wb, dw.cw);
         DL4DS_LAUNCH(omega_kernel, dim3(nbo), dim3(256), 0, s, dw.w, H, W, dw.cw, Ho, Wo, txo, tyo, gk, om, opart);
         // sum over samples, windows and channels = the planes' sum times how often each plane is used
         weight_sum_finish(s, opart, nbo, (double)(N / dw.wb) * (double)(C / dw.cw), dw.inv_so);
@@ -747,7 +707,6 @@ void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* d
     }
     DL4DS_LAUNCH(ssim_fwd_kernel<WEIGHTED>, dim3(nbf), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txo, tyo, gk, st, dmu, da,
                        db, part, omega, wrep, cw);
-    float* part2 = reinterpret_cast<float*>(base + l.part2);
     DL4DS_LAUNCH(compact_partials_kernel<3>, dim3(COMPACT_G), dim3(256), 0, s, part, nbf, part2);
     DL4DS_LAUNCH(sum3_kernel, dim3(1), dim3(256), 0, s, part2, COMPACT_G, st);
     const float inv_m = 1.f / (float)msz;
@@ -756,8 +715,8 @@ void dssim_run(hipStream_t s, const float* y_true, const float* y_pred, float* d
     if (dpred) {
         const int txi = cdiv(W, TS), tyi = cdiv(H, TS);
         nbb = N * C * txi * tyi;
-        DL4DS_LAUNCH(ssim_bwd_kernel<WEIGHTED>, dim3(nbb), dim3(256), 0, s, y_true, y_pred, H, W, C, Ho, Wo, txi, tyi, gk, st, dmu,
-                           da, db, coef, dpred, 1, part, inv_so);
+        DL4DS_LAUNCH((ssim_bwd_kernel<WEIGHTED, true>), dim3(nbb), dim3(256), 0, s, y_true, y_pred, 1, H, W, C, Ho, Wo, txi, tyi, gk, st,
+                           dmu, da, db, coef, dpred, 1, part, inv_so);
     }
     if (nbb) DL4DS_LAUNCH(compact_partials_kernel<1>, dim3(COMPACT_G), dim3(256), 0, s, part, nbb, part2);
     DL4DS_LAUNCH(dssim_finish_kernel<WEIGHTED>, dim3(1), dim3(256), 0, s, part2, nbb ? COMPACT_G : 0, st, weight, inv_m, coef, dpred,
@@ -775,7 +734,8 @@ void dssim_forward_backward(hipStream_t s, const float* y_true, const float* y_p
 size_t dssim_weighted_workspace_bytes(int N, int H, int W, int C, int w_batch, int w_channels) {
     (void)N; (void)C;
     if (H < KF || W < KF) return 0;
-    return (omega_floats(H, W, w_batch, w_channels) + omega_tiles(H, W, w_batch, w_channels)) * sizeof(float);
+    const MapGeom g = map_geom(H, W);
+    return (omega_floats(g, w_batch, w_channels) + omega_tiles(g, w_batch, w_channels)) * sizeof(float);
 }
 
 // w: w_batch maps (H, W, w_channels) (contract in losses.hip); inv_so_dev: one device float that receives 1 / sum omega; ext: the
@@ -790,33 +750,21 @@ void dssim_forward_backward_weighted(hipStream_t s, const float* y_true, const f
                     DssimWeights{w, w_batch, w_channels, inv_so_dev, ext});
 }
 
-size_t msdssim_workspace_bytes(int N, int H, int W, int C) { return ms_layout(N, H, W, C).total; }
+size_t msdssim_workspace_bytes(int N, int H, int W, int C) { return ms_layout(nullptr, N, H, W, C).total; }
 
 void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y_pred, float* dpred, int N, int H, int W, int C,
                               float weight, float* loss_out, int accumulate_loss, float* workspace, size_t workspace_bytes) {
     DL4DS_REQUIRE(((H + 7) / 8) >= KF && ((W + 7) / 8) >= KF,
                   "msdssim needs grids of at least 81x81 (four scales, 11-tap filter on the coarsest)");
-    const MsLayout l = ms_layout(N, H, W, C);
+    const MsLayout l = ms_layout(workspace, N, H, W, C);
     DL4DS_REQUIRE(workspace_bytes >= l.total, "msdssim workspace too small");
-    char* base = reinterpret_cast<char*>(workspace);
-    Stats* st = reinterpret_cast<Stats*>(base + l.stats);
-    float* pf = reinterpret_cast<float*>(base + l.pf);
-    unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + l.pi);
-    double* psum = reinterpret_cast<double*>(base + l.ps);
-    float* imgs = reinterpret_cast<float*>(base + l.imgs);
-    float* grads = reinterpret_cast<float*>(base + l.grads);
-    float* maps = reinterpret_cast<float*>(base + l.maps);
-    float* part = reinterpret_cast<float*>(base + l.part);
-    float* gcp = reinterpret_cast<float*>(base + l.gcp);
-    float* means = reinterpret_cast<float*>(base + l.means);       // [ssim: scales x NC][cs: scales x NC]
-    float* gw = reinterpret_cast<float*>(base + l.gw);             // [gs: scales x NC][gc: scales x NC]
+    Stats* st = l.hdr.st;
+    float *imgs = l.imgs, *grads = l.grads, *part = l.part, *part2 = l.part2, *gcp = l.gcp, *means = l.means, *gw = l.gw;
     const int NC = N * C;
     const size_t n0 = (size_t)N * H * W * C;
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "msdssim", 0.0, 4.0 * (double)n0 * 12);
-    const int nb = (int)std::min<size_t>(l.nb_mm, cdivz(n0, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi, psum);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n0, nb, st);
+    run_minmax(s, y_true, y_pred, n0, l.hdr);
     auto ew = [](size_t n) { return (int)std::max<size_t>(1, std::min<size_t>(cdivz(n, 256), 8192)); };
     const float* xk[MS_SCALES];
     const float* qk[MS_SCALES];
@@ -834,8 +782,7 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     }
     // ---- per-scale (ssim, cs) means
     for (int k = 0; k < MS_SCALES; ++k) {
-        const int Ho = l.d.H[k] - KF + 1, Wo = l.d.W[k] - KF + 1;
-        const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
+        const int Ho = l.g[k].Ho, Wo = l.g[k].Wo, txo = l.g[k].txo, tyo = l.g[k].tyo;
         DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, 1, l.d.H[k], l.d.W[k],
                            C, Ho, Wo, txo, tyo, gk, st, nullptr, nullptr, nullptr, nullptr, nullptr, part);
         DL4DS_LAUNCH(ms_means_kernel, dim3(NC), dim3(64), 0, s, part, txo * tyo, NC, 1.f / ((float)Ho * (float)Wo),
@@ -846,22 +793,21 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     HIP_CHECK(hipGetLastError());
     if (!dpred) return;
     // ---- per-scale gradients (coarse to fine), pooled scales folded into the finer one
-    float* dmu = maps;
+    float* dmu = l.maps;
     size_t gcp_total = 0;
     for (int k = MS_SCALES - 1; k >= 0; --k) {
-        const int Hk = l.d.H[k], Wk = l.d.W[k], Ho = Hk - KF + 1, Wo = Wk - KF + 1;
+        const int Hk = l.d.H[k], Wk = l.d.W[k], Ho = l.g[k].Ho, Wo = l.g[k].Wo, txo = l.g[k].txo, tyo = l.g[k].tyo;
         const size_t msz = (size_t)NC * Ho * Wo;
         float* da = dmu + msz;
         float* db = da + msz;
-        const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
         DL4DS_LAUNCH(ms_ssim_kernel<1>, dim3(NC * txo * tyo), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, 1, Hk, Wk, C, Ho, Wo,
                            txo, tyo, gk, st, gw + (size_t)k * NC, gw + (size_t)(MS_SCALES + k) * NC, dmu, da, db,
                            gcp + l.gcp_off[k] * 2);
         gcp_total = std::max(gcp_total, l.gcp_off[k] + (size_t)NC * txo * tyo);
         const int txi = cdiv(Wk, TS), tyi = cdiv(Hk, TS);
         float* gk_img = grads + l.grad_off[k];
-        DL4DS_LAUNCH(ms_bwd_kernel, dim3(NC * txi * tyi), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, Hk, Wk, C, Ho, Wo, txi,
-                           tyi, gk, st, dmu, da, db, gk_img);
+        DL4DS_LAUNCH((ssim_bwd_kernel<false, false>), dim3(NC * txi * tyi), dim3(256), 0, s, xk[k], qk[k], k == 0 ? 1 : 0, Hk, Wk, C, Ho,
+                           Wo, txi, tyi, gk, st, dmu, da, db, 1.f, gk_img, 0, nullptr, nullptr);
         if (k < MS_SCALES - 1) {
             const size_t n = (size_t)N * Hk * Wk * C;
             DL4DS_LAUNCH(ms_unpool_add_kernel, dim3(ew(n)), dim3(256), 0, s, gk_img, grads + l.grad_off[k + 1], N, Hk, Wk,
@@ -870,7 +816,6 @@ void msdssim_forward_backward(hipStream_t s, const float* y_true, const float* y
     }
     const int nba = (int)std::min<size_t>(cdivz(n0, 256), 2048);
     DL4DS_LAUNCH(ms_apply_kernel, dim3(nba), dim3(256), 0, s, grads + l.grad_off[0], dpred, n0, 1, part);
-    float* part2 = reinterpret_cast<float*>(base + l.part2);
     DL4DS_LAUNCH(compact_partials_kernel<2>, dim3(COMPACT_G), dim3(256), 0, s, gcp, (int)gcp_total, part2);
     DL4DS_LAUNCH(ms_finish_kernel, dim3(1), dim3(256), 0, s, part, nba, part2, COMPACT_G, st, dpred);
     HIP_CHECK(hipGetLastError());
@@ -904,12 +849,7 @@ __global__ void __launch_bounds__(256) met_pair_partial_kernel(const float* __re
         s[0] += fabs(d); s[1] += d * d; s[2] += x; s[3] += y; s[4] += x * y; s[5] += x * x; s[6] += y * y;
     }
     for (int k = 0; k < MET_K; ++k) red[k][threadIdx.x] = s[k];
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o)
-            for (int k = 0; k < MET_K; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
-        __syncthreads();
-    }
+    block_tree_sum(red, threadIdx.x);
     if (threadIdx.x < MET_K) partial[((size_t)n * gridDim.x + blockIdx.x) * MET_K + threadIdx.x] = (float)red[threadIdx.x][0];
 }
 // out[n] = (mae, mse, pearson over the grid); a pair with a constant side has exact zero moments on that side (the shift above) and
@@ -956,46 +896,46 @@ __global__ void met_assemble_kernel(const float* __restrict__ pair3, const float
     out[n * 4 + 2] = pair3[n * 3 + 2];
     out[n * 4 + 3] = sm / (float)C;
 }
+
+// has_ssim: the grid holds an 11x11 window
+struct MetLayout { StatsScratch hdr; MapGeom g; bool has_ssim; float *partial, *pair3, *tile_part, *means; size_t total; };
+MetLayout met_layout(void* ws, int N, int H, int W, int C) {
+    Bump b(ws);
+    MetLayout l;
+    l.g = map_geom(H, W);
+    l.has_ssim = l.g.Ho > 0 && l.g.Wo > 0;
+    l.hdr = carve_stats(b);
+    l.partial = b.take<float>((size_t)N * MET_CHUNKS * MET_K);
+    l.pair3 = b.take<float>((size_t)N * 3);
+    l.tile_part = b.take<float>(l.has_ssim ? (size_t)N * C * l.g.tyo * l.g.txo * 2 : 0);
+    l.means = b.take<float>((size_t)2 * N * C);
+    b.take<float>(3 * (size_t)H * W * C);      // unused: the size has always counted the three grid maps, which go to grid_out_dev
+    l.total = b.o;
+    return l;
+}
 }  // namespace
 
-size_t metrics_workspace_bytes(int N, int H, int W, int C) {
-    const size_t per = (size_t)H * W * C;
-    const int Ho = H - KF + 1, Wo = W - KF + 1;
-    const size_t tiles = (Ho > 0 && Wo > 0) ? (size_t)N * C * cdiv(Ho, TS) * cdiv(Wo, TS) : 0;
-    return sizeof(Stats) + 256 + (size_t)512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long) + 2 * sizeof(double)) + 256 +
-           ((size_t)N * MET_CHUNKS * MET_K + (size_t)N * 3 + 3 * per + tiles * 2 + (size_t)2 * N * C + 64) * sizeof(float);
-}
+size_t metrics_workspace_bytes(int N, int H, int W, int C) { return met_layout(nullptr, N, H, W, C).total; }
 
 // pair_out: [N][4] = (mae, mse, pearson, ssim)   grid_out: [3][H*W*C] = (rmse, mean bias, pearson)   stats_out: Stats
 void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int N, int H, int W, int C, float* pair_out_dev,
                    float* grid_out_dev, float* range_out_dev, float* workspace, size_t workspace_bytes) {
-    DL4DS_REQUIRE(workspace_bytes >= metrics_workspace_bytes(N, H, W, C), "metrics workspace too small");
+    const MetLayout l = met_layout(workspace, N, H, W, C);
+    DL4DS_REQUIRE(workspace_bytes >= l.total, "metrics workspace too small");
     const size_t per = (size_t)H * W * C, n0 = per * N;
-    char* base = reinterpret_cast<char*>(workspace);
-    Stats* st = reinterpret_cast<Stats*>(base);
-    float* pf = reinterpret_cast<float*>(base + 256);
-    unsigned long long* pi = reinterpret_cast<unsigned long long*>(base + 256 + 512 * 4 * sizeof(float));
-    double* psum = reinterpret_cast<double*>(base + 256 + 512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long)));
-    float* f = reinterpret_cast<float*>(base + 256 + 512 * (4 * sizeof(float) + 2 * sizeof(unsigned long long) + 2 * sizeof(double)) + 256);
-    float* partial = f;                                   f += (size_t)N * MET_CHUNKS * MET_K;
-    float* pair3 = f;                                     f += (size_t)N * 3;
-    float* tile_part = f;
+    Stats* st = l.hdr.st;
+    float *partial = l.partial, *pair3 = l.pair3, *tile_part = l.tile_part, *means = l.means;
     static const Gauss gk = make_gauss();
     ProfScope ps(s, "image_metrics", 0.0, 4.0 * (double)n0 * 6);
-    const int nb = (int)std::min<size_t>(512, cdivz(n0, 256));
-    DL4DS_LAUNCH(minmax_kernel, dim3(nb), dim3(256), 0, s, y_true, y_pred, n0, pf, pi, psum);
-    DL4DS_LAUNCH(minmax_finish_kernel, dim3(1), dim3(256), 0, s, pf, pi, psum, 1.0 / (double)n0, nb, st);
+    run_minmax(s, y_true, y_pred, n0, l.hdr);
     DL4DS_LAUNCH(met_pair_partial_kernel, dim3(MET_CHUNKS, N), dim3(256), 0, s, y_true, y_pred, per, partial);
     DL4DS_LAUNCH(met_pair_finish_kernel, dim3(cdiv(N, 64)), dim3(64), 0, s, partial, MET_CHUNKS, N, (double)per, pair3);
     DL4DS_LAUNCH(met_grid_kernel, dim3((unsigned)std::min<size_t>(cdivz(per, 256), 4096)), dim3(256), 0, s, y_true, y_pred, N,
                        per, grid_out_dev);
     // SSIM per pair = mean over channels of the per-plane mean SSIM (needs an 11x11 window)
-    const int Ho = H - KF + 1, Wo = W - KF + 1;
-    float* means = tile_part;           // set below when the window fits
     const int NC = N * C;
-    if (Ho > 0 && Wo > 0) {
-        const int txo = cdiv(Wo, TS), tyo = cdiv(Ho, TS);
-        means = tile_part + (size_t)NC * txo * tyo * 2;
+    if (l.has_ssim) {
+        const int Ho = l.g.Ho, Wo = l.g.Wo, txo = l.g.txo, tyo = l.g.tyo;
         DL4DS_LAUNCH(ms_ssim_kernel<0>, dim3(NC * txo * tyo), dim3(256), 0, s, y_true, y_pred, 1, 0, H, W, C, Ho, Wo, txo, tyo, gk, st,
                            nullptr, nullptr, nullptr, nullptr, nullptr, tile_part);
         DL4DS_LAUNCH(ms_means_kernel, dim3(NC), dim3(64), 0, s, tile_part, txo * tyo, NC, 1.f / ((float)Ho * (float)Wo), means,
@@ -1003,7 +943,7 @@ void image_metrics(hipStream_t s, const float* y_true, const float* y_pred, int 
     }
     HIP_CHECK(hipGetLastError());
     // assemble [N][4] and the range on the device (tiny)
-    DL4DS_LAUNCH(met_assemble_kernel, dim3(cdiv(N, 64)), dim3(64), 0, s, pair3, means, N, C, (Ho > 0 && Wo > 0) ? 1 : 0, st, pair_out_dev,
+    DL4DS_LAUNCH(met_assemble_kernel, dim3(cdiv(N, 64)), dim3(64), 0, s, pair3, means, N, C, l.has_ssim ? 1 : 0, st, pair_out_dev,
                        range_out_dev);
     HIP_CHECK(hipGetLastError());
 }

@@ -2,9 +2,11 @@
 
 csrc/dssim.hip picks its launch geometry from the array shape (N, H, W, C) alone:
 
-  min/max      n = N H W C elements; nb = min(512, cdiv(n, 256)) blocks of 256 walk them with a grid stride (a second trip when
-               n > 131072); minmax_finish_kernel reads the nb block results, thread k, k + 256, ... (a second trip when nb > 256)
-  SSIM tiles   16 x 16 tiles over the (H - 10, W - 10) map, forward; 16 x 16 tiles over (H, W), backward; one block per tile and plane
+  min/max      run_minmax: n = N H W C elements; nb = min(512, cdiv(n, 256)) blocks of minmax_kernel walk them with a grid stride (a
+               second trip when n > 131072); minmax_finish_kernel reads the nb block results, thread k, k + 256, ... (a second trip
+               when nb > 256)
+  SSIM tiles   16 x 16 tiles over the (H - 10, W - 10) map (map_geom), forward: ssim_fwd_kernel, ms_ssim_kernel; 16 x 16 tiles over
+               (H, W), backward: ssim_bwd_kernel, for the loss and for every pyramid level; one block per tile and plane
   compaction   compact_partials_kernel: 64 blocks, block g sums rows [g chunk, (g + 1) chunk) of the per-tile partials,
                chunk = cdiv(rows, 64), thread r, r + 256, ... (a second trip when rows > 16384)
   multi-scale  four scales, sizes halved upwards; ms_means_kernel: one wavefront per plane, lane k, k + 64, ... over the plane's tiles;

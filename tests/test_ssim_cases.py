@@ -48,19 +48,20 @@ def test_constants_and_launch_expressions_match_the_source():
             (f'constexprintCOMPACT_G={K.COMPACT_G};', 1),
             (f'constexprintMS_SCALES={K.MS_SCALES};', 1),
             (f'constexprintMET_CHUNKS={K.MET_CHUNKS},MET_K=7;', 1),
-            (f'l.nb_mm={K.MM_CAP};', 2),
-            ('constintnb=(int)std::min<size_t>(l.nb_mm,cdivz(n,256));', 1),
-            ('constintnb=(int)std::min<size_t>(l.nb_mm,cdivz(n0,256));', 1),
-            (f'constintnb=(int)std::min<size_t>({K.MM_CAP},cdivz(n0,256));', 1),
+            (f'h.nb_mm={K.MM_CAP};', 1),                                                   # carve_stats
+            ('constintnb=(int)std::min<size_t>(h.nb_mm,cdivz(n,256));', 1),               # run_minmax, the one min/max launch pair
+            ('DL4DS_LAUNCH(minmax_kernel,dim3(nb),dim3(256)', 1),
+            ('run_minmax(s,y_true,y_pred,', 3),
             ('for(size_te=(size_t)blockIdx.x*256+threadIdx.x;e<n;e+=(size_t)gridDim.x*256){constfloata=t[e],b=p[e];', 1),
             ('for(intk=i;k<nb;k+=256){mnT=fminf(mnT,pf[4*k]);', 1),
             ('constintchunk=(nb+(int)gridDim.x-1)/(int)gridDim.x;constintr0=blockIdx.x*chunk,r1=min(r0+chunk,nb);', 1),
             ('for(intr=r0+threadIdx.x;r<r1;r+=256)', 1),
             ('dim3(COMPACT_G),dim3(256)', 3),
-            ('constinttxo=cdiv(Wo,TS),tyo=cdiv(Ho,TS);', 4),
+            ('returnMapGeom{Ho,Wo,cdiv(Wo,TS),cdiv(Ho,TS)};', 1),                          # map_geom: txo, tyo of every launch
             ('constinttxi=cdiv(W,TS),tyi=cdiv(H,TS);', 1),
             ('constinttxi=cdiv(Wk,TS),tyi=cdiv(Hk,TS);', 1),
-            ('constintHo=H-KF+1,Wo=W-KF+1;', 4),
+            ('constintHo=H-KF+1,Wo=W-KF+1;', 1),
+            ('l.g[k]=map_geom(l.d.H[k],l.d.W[k]);', 1),
             ('for(intk=1;k<MS_SCALES;++k){l.d.H[k]=(l.d.H[k-1]+1)/2;l.d.W[k]=(l.d.W[k-1]+1)/2;}', 1),
             ('DL4DS_REQUIRE(((H+7)/8)>=KF&&((W+7)/8)>=KF,', 1),
             ('__launch_bounds__(64)ms_means_kernel(', 1),
@@ -79,15 +80,19 @@ def test_constants_and_launch_expressions_match_the_source():
             ('DL4DS_LAUNCH(met_pair_finish_kernel,dim3(cdiv(N,64)),dim3(64)', 1),
             ('DL4DS_LAUNCH(met_assemble_kernel,dim3(cdiv(N,64)),dim3(64)', 1),
             (f'dim3((unsigned)std::min<size_t>(cdivz(per,256),{K.MET_GRID_CAP})),dim3(256)', 1),
-            ('if(st->maxP>st->maxT)dpred[st->argmaxP]+=ddr;', 2),
-            ('if(st->minP<st->minT)dpred[st->argminP]-=ddr;', 2),
-            ('if(st->minP<0.f)dpred[st->argminP]-=', 2),
+            ('if(st->maxP>st->maxT)dpred[st->argmaxP]+=ddr;', 1),                          # route_range_and_shift
+            ('if(st->minP<st->minT)dpred[st->argminP]-=ddr;', 1),
+            ('if(st->minP<0.f)dpred[st->argminP]-=sumdy;', 1),
+            ('route_range_and_shift(st,', 2),
             ('constfloatshT=(shift&&st->minT<0.f)?st->minT:0.f,shP=(shift&&st->minP<0.f)?st->minP:0.f;', 1),
             ('returnPivot{st->pivT,st->pivP,st->pivT-shT,st->pivP-shP};', 1),
-            ('constPivotpv=pivot_of(st,true);', 2),
+            ('constPivotpv=pivot_of(st,true);', 1),
+            ('constfloatpT=raw?st->pivT:0.f,pP=raw?st->pivP:0.f;', 1),                    # the one backward tile kernel
             ('constPivotpv=pivot_of(st,shift!=0);', 1),
-            ('st->pivT=(float)(sd[0][0]*inv_n);st->pivP=(float)(sd[1][0]*inv_n);', 1)):
+            ('st->pivT=(float)(r.sd[0][0]*inv_n);st->pivP=(float)(r.sd[1][0]*inv_n);', 1)):
         assert d.count(piece) == count, (piece, d.count(piece))
+    tree = 'for(into=128;o>0;o>>=1)'                 # the block reduction tree has one home: block_tree of common.h
+    assert d.count(tree) == 0 and _src('dl4ds_amd', 'csrc', 'common.h').count(tree) == 1
     capi = _src('dl4ds_amd', 'csrc', 'capi.cpp')
     assert 'loss_forward_backward(S(),kind,yt,yp,dpred,N,H,W,C,scale,loss_dev,accumulate,scratch(ws),ws);' in capi
     losses = _src('dl4ds_amd', 'csrc', 'losses.hip')
