@@ -1260,6 +1260,12 @@ int dl4ds_graph_fusion_report(dl4ds_graph* g, int B, char* json_buf, size_t bufl
     std::memcpy(json_buf, out.c_str(), out.size() + 1);
     API_END
 }
+int dl4ds_graph_aux_launches(dl4ds_graph* g, long* n) {
+    API_BEGIN
+    DL4DS_REQUIRE(g && n, "graph / result pointer missing");
+    *n = g->g.aux_wgrad_launches;
+    API_END
+}
 int dl4ds_graph_bucket_plan(dl4ds_graph* g, char* buf, size_t buflen) {
     API_BEGIN
     DL4DS_REQUIRE(g && g->g.finalized, "graph not finalized");

@@ -115,7 +115,8 @@ struct Graph {
     float* aux_workspace = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool aux_used = false;
-    void fork_aux();            // aux_stream waits for everything enqueued on `stream` so far
+    long aux_wgrad_launches = 0;    // weight-gradient calls issued on aux_stream since the graph was created (dl4ds_graph_aux_launches)
+    void fork_aux();           // aux_stream waits for everything enqueued on `stream` so far
     void join_aux();            // `stream` waits for everything enqueued on aux_stream
     hipStream_t stream = nullptr;
     std::vector<float*> allocations;

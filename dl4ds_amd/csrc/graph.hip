@@ -544,10 +544,12 @@ struct ConvOp : GOp {
                                                      g.workspace_bytes);
                 att_before->ds_ready = done;
             }
-            if (!done)
+            if (!done) {
                 conv2d_wgrad(ws_stream, in_view(g, c.B, c.b_off, c.b_cnt), dY, KS, g.gp(w),
                              g.params[w].grad_written, need_db ? g.gp(b) : nullptr,
                              need_db ? (int)g.params[b].grad_written : 0, ws_buf, g.workspace_bytes);
+                if (on_aux) g.aux_wgrad_launches += 1;
+            }
             g.params[w].grad_written = true;
             if (need_db) g.params[b].grad_written = true;
         }

@@ -377,6 +377,12 @@ class GraphBuilder:
             self.param(name + '/moving_mean', (channels,), 'zeros', trainable=False)
             self.param(name + '/moving_variance', (channels,), 'ones', trainable=False)
 
+    def aux_launches(self):
+        """Weight-gradient calls issued on the second stream since the graph was created (0 without DL4DS_AUX_STREAM)."""
+        n = ctypes.c_long()
+        _lib.check(self._l.dl4ds_graph_aux_launches(self.h, ctypes.byref(n)))
+        return n.value
+
     # ---------------------------------------------------------------- dropout noise (tests / reproducibility)
     def dropout_count(self):
         n = ctypes.c_int()
