@@ -399,8 +399,7 @@ int dl4ds_op_conv2d_wgrad_attention(const dl4ds_view* x, const dl4ds_view* dz, c
     DL4DS_REQUIRE(launched != nullptr && scale && w && dw && ds, "conv2d_wgrad_attention: null operand");
     const TView xv = desc_view(x, N, H, W, false, "conv2d_wgrad_attention x");
     const TView dzv = desc_view(dz, N, H, W, false, "conv2d_wgrad_attention dz");
-    // (N * bpi + N) slabs with bpi <= 1024 / N blocks per image (conv_direct.hip)
-    const size_t ws = (size_t)(1024 + N) * ((size_t)KS * KS * xv.C * dzv.C + dzv.C) * sizeof(float);
+    const size_t ws = conv2d_direct_wgrad_attention_workspace_bytes(xv, dzv, KS);
     *launched = conv2d_direct_wgrad_attention(S(), xv, dzv, KS, scale, w, dw, accumulate, db, accumulate_db, ds, scratch(ws), ws) ? 1 : 0;
     API_END
 }

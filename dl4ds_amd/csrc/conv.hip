@@ -14,7 +14,7 @@
 // Replaces (third-party in the reference): tf.keras.layers.Conv2D forward and the Conv2DBackpropInput /
 // Conv2DBackpropFilter TF autodiff would have produced -- call sites dl4ds/models/blocks.py:49-61,208,
 // 249-259,299,414-416,479,582-583; sp_postups.py:134,156; discriminator.py:35-65.
-#include "ops.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "conv_kernels.h"
 #include "conv_cache.h"
@@ -1525,10 +1525,14 @@ void conv2d_forward(hipStream_t s, const TView& in, const float* w, int KS, cons
                     const ConvEpilogue& ep) {
     DL4DS_REQUIRE(in.N == out.N && in.H == out.H && in.W == out.W, "conv2d: stride-1 SAME shapes differ");
     DL4DS_REQUIRE(!ep.sum_out.p && !ep.out2.p, "conv2d: a second output pair goes through conv2d_forward_fused");
-    if (conv2d_direct_forward(s, in, w, KS, out, ep)) return;      // a handful of channels: HBM-bound stencil
-    if (!exp_env("DL4DS_NO_NARROW") && conv2d_narrow_forward(s, in, w, KS, out, ep)) return;
-    DL4DS_REQUIRE(!in.sc && !ep.pool, "conv2d: channel-affine input / pooling partials are only implemented by the direct "
-                                     "and narrow-pair kernels (the caller must check conv2d_direct_eligible / conv2d_narrow_pair_ok)");
+    const ConvFwdRoute route = conv2d_forward_route(in, out, KS, ep);
+    DL4DS_REQUIRE(!route.refusal, route.refusal);
+    switch (route.family) {
+        case ConvFwdFamily::Direct: return conv2d_direct_forward(s, in, w, out, ep);      // a handful of channels: HBM-bound stencil
+        case ConvFwdFamily::NarrowPair: return conv2d_narrow_forward(s, in, w, out, ep, true);
+        case ConvFwdFamily::Narrow: return conv2d_narrow_forward(s, in, w, out, ep, false);
+        case ConvFwdFamily::Rest: break;      // the try-and-launch families, in this order:
+    }
     if (KS == 3 && conv2d_split_forward(s, in, w, out, ep)) return; // 40 / 48-channel 3x3 layers: fp32 products as six bf16 MFMA terms
     if (KS == 3 && conv2d_wino_forward(s, in, w, out, ep)) return;  // MFMA-bound 3x3 layers: Winograd F(2x2, 3x3)
     // small grids, many channels: GEMM over the flattened pixels of the batch -- up to 16 x 16 ahead of the streaming kernels (which
@@ -1634,77 +1638,65 @@ void conv2d_dgrad_weights(hipStream_t s, const float* w, float* wt, int KS, int 
     HIP_CHECK(hipGetLastError());
 }
 
-// 9 .. 16 input channels with <= 8 outputs (13 -> 8: ConvBlock_att's first layer in the recurrent nets; 16 -> 8 U-Net decoder
-// layers): the general kernel runs these with the eight output channels on half of the MFMA's rows (nine MFMAs per pixel quad);
-// conv_narrow_wgrad_kernel<8> on the channel slices [0, 8) and [8, C) takes 2 x 3 (rows 8-15 carry the pixel below).  The slices are
-// plain views of the same pixels (pitch = the tensor's); the slab sums scatter into the [9][C][Cout] gradient.
-static TView channel_slice(const TView& x, int c0, int c1) {
-    TView v = x;
-    v.p = x.p + c0; v.C = c1 - c0; v.cp = v.C;
-    v.vec = ((v.C & 3) == 0) && ((x.ld & 3) == 0) && ((((uintptr_t)v.p) & 15) == 0);
-    return v;
-}
-static int narrow_wgrad_split_slabs(const TView& x, const TView& dz, int KS) {
-    static const bool off = exp_env("DL4DS_NO_WGRAD_SPLIT") != nullptr;                 // (A/B)
-    if (off || KS != 3 || x.C <= 8 || x.C > 16 || dz.C > 8 || x.sc || x.d2s > 1 || dz.d2s > 1 || !dz.vec) return 0;
-    if (conv2d_direct_wgrad_slabs(x, dz, KS) || exp_env("DL4DS_NO_NARROW")) return 0;
-    return conv2d_narrow_wgrad_slabs(channel_slice(x, 0, 8), dz, KS);
-}
-
+// Callers size with a dz view on a null pointer (float4-loadable whenever its channel count allows) while the call itself may bring a dz at
+// an unaligned base or pitch, which the narrow families decline: those are sized for whichever of their plan and the general one needs more.
 size_t conv2d_wgrad_workspace_bytes(const TView& x, const TView& dz, int KS) {
     const size_t slab = ((size_t)KS * KS * x.C * dz.C + dz.C) * sizeof(float);
-    if (const int ds = conv2d_direct_wgrad_slabs(x, dz, KS)) return (size_t)ds * slab;
-    // (the narrow path can be switched off for A/B runs: size for whichever of the two plans needs more)
+    const WgradRoute r = conv2d_wgrad_route(x, dz, KS);
+    if (r.family == WgradFamily::Direct) return (size_t)r.slabs * slab;
     const size_t general = (size_t)plan_wgrad(x, dz, KS).S * slab;
-    if (const int ns = conv2d_narrow_wgrad_slabs(x, dz, KS)) return std::max((size_t)ns * slab, general);
-    if (const int ns = narrow_wgrad_split_slabs(x, dz, KS)) return std::max((size_t)2 * ns * slab, general);     // (two slices, each < slab)
+    if (r.family == WgradFamily::Narrow) return std::max((size_t)r.slabs * slab, general);
+    if (r.family == WgradFamily::NarrowSlices) return std::max((size_t)2 * r.slabs * slab, general);     // (two slices, each < slab)
     return general;
+}
+
+// dw / db (+)= the sum of `slabs` partial slabs of n = nw + Cout values (rowlen > 0: of a channel slice, see reduce_slabs_kernel).  Small
+// filters (a 3x3 8 -> 8 layer has 584 values in up to 1024 slabs): 16 elements per block would leave 37 blocks walking 64 slabs per thread one
+// latency after the other (13 us); 4 elements per block put 64 slabs in flight per block.  One rule serves whole filters and slices: a slice
+// has n = 9 * Cs * Cout + Cout <= 584, so n < 4096 holds there and the 8192-block cap is out of reach (DL4DS_REDUCE16: whole filters only).
+static void reduce_slabs(hipStream_t s, const float* partial, float* dw, float* db, size_t nw, size_t n, int slabs, int acc, int acc_db,
+                         int rowlen, int dstride, int doff) {
+    ProfScope ps(s, "wgrad_reduce_slabs", 0.0, 4.0 * (double)n * (slabs + 1));
+    if (n < 4096 && slabs >= 128 && !(rowlen == 0 && exp_env("DL4DS_REDUCE16"))) {
+        const int blocks = (int)std::max<size_t>(1, cdivz(n, 4));
+        DL4DS_LAUNCH(reduce_slabs_kernel<4>, dim3(blocks), dim3(256), 0, s, partial, dw, db, nw, n, slabs, acc, acc_db, rowlen, dstride, doff);
+    } else {
+        const int blocks = (int)std::max<size_t>(1, std::min<size_t>(cdivz(n, 16), 8192));
+        DL4DS_LAUNCH(reduce_slabs_kernel<16>, dim3(blocks), dim3(256), 0, s, partial, dw, db, nw, n, slabs, acc, acc_db, rowlen, dstride, doff);
+    }
+    HIP_CHECK(hipGetLastError());
 }
 
 void conv2d_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* dw, int accumulate, float* db,
                   int accumulate_db, float* workspace, size_t workspace_bytes) {
     DL4DS_REQUIRE(x.N == dz.N && x.H == dz.H && x.W == dz.W, "wgrad: shapes differ");
     if (KS == 3 && conv2d_wino_wgrad(s, x, dz, dw, accumulate, db, accumulate_db)) return;     // MFMA-bound 3x3 layers: Winograd
-    if (const int ns = narrow_wgrad_split_slabs(x, dz, KS)) {
-        float* ws = workspace;
+    const WgradRoute r = conv2d_wgrad_route(x, dz, KS);
+    DL4DS_REQUIRE(!r.refusal, r.refusal);
+    if (r.family == WgradFamily::NarrowSlices) {
+        float* ws = workspace;      // (plain views of the same pixels at the tensor's pitch; the slab sums scatter into the [9][C][Cout] gradient)
         for (int c0 = 0; c0 < x.C; c0 += 8) {
-            const TView xs = channel_slice(x, c0, std::min(c0 + 8, x.C));
+            const TView xs = conv_route::channel_slice(x, c0, std::min(c0 + 8, x.C));
             const size_t nws = (size_t)9 * xs.C * dz.C, ns_n = nws + dz.C;
-            DL4DS_REQUIRE((size_t)(ws - workspace) * sizeof(float) + (size_t)ns * ns_n * sizeof(float) <= workspace_bytes, "wgrad: workspace too small");
-            const int got = conv2d_narrow_wgrad(s, xs, dz, KS, ws, ns);
-            ProfScope ps(s, "wgrad_reduce_slabs", 0.0, 4.0 * (double)ns_n * (got + 1));
-            float* dbs = c0 == 0 ? db : nullptr;                                           // (every slice sums the same dz)
-            if (got >= 128) {
-                DL4DS_LAUNCH(reduce_slabs_kernel<4>, dim3((int)cdivz(ns_n, 4)), dim3(256), 0, s, ws, dw, dbs, nws, ns_n, got, accumulate,
-                             accumulate_db, xs.C * dz.C, x.C * dz.C, c0 * dz.C);
-            } else {
-                DL4DS_LAUNCH(reduce_slabs_kernel<16>, dim3((int)cdivz(ns_n, 16)), dim3(256), 0, s, ws, dw, dbs, nws, ns_n, got, accumulate,
-                             accumulate_db, xs.C * dz.C, x.C * dz.C, c0 * dz.C);
-            }
-            HIP_CHECK(hipGetLastError());
-            ws += (size_t)ns * ns_n;
+            DL4DS_REQUIRE((size_t)(ws - workspace) * sizeof(float) + (size_t)r.slabs * ns_n * sizeof(float) <= workspace_bytes, "wgrad: workspace too small");
+            const int got = conv2d_narrow_wgrad(s, xs, dz, KS, ws, r.slabs);      // (every slice sums the same dz: db from the first)
+            reduce_slabs(s, ws, dw, c0 == 0 ? db : nullptr, nws, ns_n, got, accumulate, accumulate_db, xs.C * dz.C, x.C * dz.C, c0 * dz.C);
+            ws += (size_t)r.slabs * ns_n;
         }
         return;
     }
-    WgradPlan pl = plan_wgrad(x, dz, KS);
-    const size_t nw = (size_t)KS * KS * x.C * dz.C;
-    const size_t n = nw + dz.C;
-    const int direct_slabs = conv2d_direct_wgrad_slabs(x, dz, KS);
-    const int narrow_slabs = (direct_slabs || exp_env("DL4DS_NO_NARROW")) ? 0 : conv2d_narrow_wgrad_slabs(x, dz, KS);
-    DL4DS_REQUIRE(direct_slabs || ((!x.sc) && (narrow_slabs || !dz.sc)),
-                  "wgrad: channel-affine operands are only implemented by the direct (x) and narrow (dz) kernels");
-    int nslabs = direct_slabs ? direct_slabs : (narrow_slabs ? narrow_slabs : pl.S);
+    const WgradPlan pl = plan_wgrad(x, dz, KS);
+    const size_t nw = (size_t)KS * KS * x.C * dz.C, n = nw + dz.C;
+    int nslabs = r.family == WgradFamily::General ? pl.S : r.slabs;
     DL4DS_REQUIRE(workspace_bytes >= (size_t)nslabs * n * sizeof(float), "wgrad: workspace too small");
-    WgradParams p;
-    p.x = x; p.dz = dz; p.partial = workspace;
-    p.Cin = x.C; p.Cout = dz.C; p.H = x.H; p.W = x.W;
-    p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles; p.S = pl.S;
-    p.m_tx = div_magic(p.tiles_x); p.m_ty = div_magic(p.tiles_y);
-    if (direct_slabs) {
-        nslabs = conv2d_direct_wgrad(s, x, dz, KS, workspace, direct_slabs);
-    } else if (narrow_slabs) {
-        nslabs = conv2d_narrow_wgrad(s, x, dz, KS, workspace, narrow_slabs);
-    } else {
+    if (r.family == WgradFamily::Direct) nslabs = conv2d_direct_wgrad(s, x, dz, KS, workspace, r.slabs);
+    else if (r.family == WgradFamily::Narrow) nslabs = conv2d_narrow_wgrad(s, x, dz, KS, workspace, r.slabs);
+    else {
+        WgradParams p;
+        p.x = x; p.dz = dz; p.partial = workspace;
+        p.Cin = x.C; p.Cout = dz.C; p.H = x.H; p.W = x.W;
+        p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.ntiles = pl.ntiles; p.S = pl.S;
+        p.m_tx = div_magic(p.tiles_x); p.m_ty = div_magic(p.tiles_y);
         switch (KS) {
             case 1: dispatch_wgrad<1>(s, p, pl); break;
             case 3: dispatch_wgrad<3>(s, p, pl); break;
@@ -1713,17 +1705,5 @@ void conv2d_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float*
             default: throw Dl4dsError("wgrad: kernel size not supported (1,3,5,7)");
         }
     }
-    ProfScope ps(s, "wgrad_reduce_slabs", 0.0, 4.0 * (double)n * (nslabs + 1));
-    // small filters (a 3x3 8 -> 8 layer has 584 values in up to 1024 slabs): 16 elements per block would leave 37 blocks walking
-    // 64 slabs per thread one latency after the other (13 us); 4 elements per block put 64 slabs in flight per block
-    if (n < 4096 && nslabs >= 128 && !exp_env("DL4DS_REDUCE16")) {
-        const int blocks = (int)std::max<size_t>(1, cdivz(n, 4));
-        DL4DS_LAUNCH(reduce_slabs_kernel<4>, dim3(blocks), dim3(256), 0, s, workspace, dw, db, nw, n, nslabs, accumulate,
-                           accumulate_db, 0, 0, 0);
-    } else {
-        const int blocks = (int)std::max<size_t>(1, std::min<size_t>(cdivz(n, 16), 8192));
-        DL4DS_LAUNCH(reduce_slabs_kernel<16>, dim3(blocks), dim3(256), 0, s, workspace, dw, db, nw, n, nslabs, accumulate,
-                           accumulate_db, 0, 0, 0);
-    }
-    HIP_CHECK(hipGetLastError());
+    reduce_slabs(s, workspace, dw, db, nw, n, nslabs, accumulate, accumulate_db, 0, 0, 0);
 }

@@ -14,14 +14,14 @@
 // dgrad is the same kernel run on the flipped/transposed weights (conv2d_dgrad_weights), exactly as for the MFMA path.
 // The weight gradient accumulates the KK*CI*CO (+CO bias) sums per thread over a persistent loop and writes one
 // partial slab per block in the layout conv2d_wgrad's deterministic slab reduction already consumes.
-#include "ops.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "launch.h"
 #include <algorithm>
 
 namespace {
 
-constexpr int DTX = 32, DTY = 8;        // output tile (one pixel per thread, 256 threads)
+using namespace conv_route;             // DTX x DTY: the output tile (one pixel per thread, 256 threads); pad_pow2
 
 struct DirectParams {
     TView in, out, add, mask;
@@ -820,22 +820,17 @@ bool direct2_ok(const DirectParams& p, int ci) {
     return (long)cdiv(p.W, DTX) * cdiv(p.H, D2Y) * p.in.N < (1l << 20);
 }
 
-inline int pad_pow2(int c) { int p = 1; while (p < c) p <<= 1; return p; }
-
-bool eligible(const TView& in, const TView& out, int KS) {
-    if (KS != 3) return false;
-    if (in.d2s > 1 || out.d2s > 1) return false;
-    if (in.C < 1 || out.C < 1) return false;
-    if ((long)cdiv(in.W, DTX) * cdiv(in.H, DTY) * in.N >= (1l << 20)) return false;      // fast_div range
-    return pad_pow2(in.C) * pad_pow2(out.C) <= 8;
-}
-
-void fill_tiles(DirectParams& p, int N) {
-    p.tiles_x = cdiv(p.W, DTX);
-    p.tiles_y = cdiv(p.H, DTY);
-    p.ntiles = p.tiles_x * p.tiles_y * N;
-    p.m_tx = div_magic(p.tiles_x);
-    p.m_ty = div_magic(p.tiles_y);
+// forward / dgrad: out = epilogue(conv(in, w)); weight gradient: in = x, out = dz, an empty epilogue and the slabs in `partial`
+DirectParams direct_params(const TView& in, const TView& out, const float* w, const ConvEpilogue& ep, float* partial) {
+    DirectParams p;
+    p.in = in; p.out = out; p.add = ep.add; p.mask = ep.mask;
+    p.w = w; p.bias = ep.bias; p.partial = partial;
+    p.Cin = in.C; p.Cout = out.C; p.H = in.H; p.W = in.W;
+    p.relu = ep.relu; p.accumulate = ep.accumulate;
+    p.tiles_x = cdiv(p.W, DTX); p.tiles_y = cdiv(p.H, DTY);
+    p.ntiles = p.tiles_x * p.tiles_y * in.N;
+    p.m_tx = div_magic(p.tiles_x); p.m_ty = div_magic(p.tiles_y);
+    return p;
 }
 
 template <int KS, int CI, int CO>
@@ -904,32 +899,11 @@ int dispatch_direct(hipStream_t s, const DirectParams& p, bool wgrad, int blocks
 
 }  // namespace
 
-// a view with a channel affine is only read by the float4 staging path (Cin % 4 == 0, 16-byte aligned)
-static bool affine_ok(const TView& v) { return !v.sc || (v.vec && (v.C & 3) == 0 && v.C >= 4); }
-
-bool conv2d_direct_eligible(const TView& in, const TView& out, int KS) { return eligible(in, out, KS) && affine_ok(in); }
-
-bool conv2d_direct_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
-                           const ConvEpilogue& ep) {
-    if (!eligible(in, out, KS)) return false;
-    DL4DS_REQUIRE(affine_ok(in) && !ep.pool, "conv_direct: channel-affine input needs float4-loadable channels; no pooling partials");
-    if ((ep.add.p && ep.add.d2s > 1) || (ep.mask.p && ep.mask.d2s > 1)) return false;
-    DirectParams p;
-    p.in = in; p.out = out; p.add = ep.add; p.mask = ep.mask;
-    p.w = w; p.bias = ep.bias; p.partial = nullptr;
-    p.Cin = in.C; p.Cout = out.C; p.H = in.H; p.W = in.W;
-    p.relu = ep.relu; p.accumulate = ep.accumulate;
-    fill_tiles(p, in.N);
-    if (p.ntiles == 0) return true;
+// launch half of the stencil path: conv2d_forward_route (conv_route.h) says which calls come here
+void conv2d_direct_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep) {
+    const DirectParams p = direct_params(in, out, w, ep, nullptr);
+    if (p.ntiles == 0) return;
     dispatch_direct(s, p, false, p.ntiles);
-    return true;
-}
-
-int conv2d_direct_wgrad_slabs(const TView& x, const TView& dz, int KS) {
-    if (!eligible(x, dz, KS)) return 0;
-    DL4DS_REQUIRE(affine_ok(x) && !dz.sc, "conv_direct wgrad: only a float4-loadable x operand may carry a channel affine");
-    const int ntiles = cdiv(x.W, DTX) * cdiv(x.H, DTY) * x.N;
-    return std::max(1, std::min(ntiles, 1024));
 }
 
 namespace {
@@ -984,22 +958,21 @@ __global__ void __launch_bounds__(256) att_wgrad_combine_kernel(const float* __r
 //   dW[tap,ci,co]  = sum_n s[n,ci] * R_n[tap,ci,co],   R_n = wgrad(x_n, dz_n)  (the RAW, un-scaled input)
 //   ds[n,ci]       = sum_p x_n[p,ci] * dgrad(dz_n)[p,ci] = sum_{tap,co} W[tap,ci,co] * R_n[tap,ci,co]
 // so the per-image raw weight gradients give both, and the attention backward needs no pass over (dy * x) at all.
-// workspace: (N*bpi + N) * (KK*Cin*Cout + Cout) floats.  Returns false if the layer is not eligible (caller falls back).
+// workspace: (N*bpi + N) * (KK*Cin*Cout + Cout) floats, bpi <= 1024 / N blocks per image; callers size it by the bound below (N * bpi <= 1024).
+// Returns false if the layer is not eligible (caller falls back).
+size_t conv2d_direct_wgrad_attention_workspace_bytes(const TView& x_raw, const TView& dz, int KS) {
+    return (size_t)(1024 + x_raw.N) * ((size_t)KS * KS * x_raw.C * dz.C + dz.C) * sizeof(float);
+}
 bool conv2d_direct_wgrad_attention(hipStream_t s, const TView& x_raw, const TView& dz, int KS, const float* scale, const float* w,
                                    float* dw, int accumulate, float* db, int accumulate_db, float* ds, float* workspace,
                                    size_t workspace_bytes) {
-    if (!eligible(x_raw, dz, KS) || x_raw.sc || dz.sc || !affine_ok(x_raw)) return false;
+    if (conv2d_wgrad_route(x_raw, dz, KS).family != WgradFamily::Direct || x_raw.sc || dz.sc) return false;
     const int N = x_raw.N;
     const int nw = KS * KS * x_raw.C * dz.C, n_el = nw + dz.C;
     const int bpi = std::max(1, std::min(1024 / std::max(N, 1), cdiv(x_raw.W, DTX) * cdiv(x_raw.H, DTY)));
-    if (N > 1024 || (size_t)(N * bpi + N) * n_el * sizeof(float) > workspace_bytes || n_el * sizeof(float) > 48 * 1024) return false;
-    DirectParams p;
-    p.in = x_raw; p.out = dz; p.add = TView{nullptr, 0, 0, 0, 0, 0, 0, 0}; p.mask = p.add;
-    p.w = nullptr; p.bias = nullptr; p.partial = workspace;
-    p.Cin = x_raw.C; p.Cout = dz.C; p.H = x_raw.H; p.W = x_raw.W;
-    p.relu = 0; p.accumulate = 0;
+    if (N > 1024 || conv2d_direct_wgrad_attention_workspace_bytes(x_raw, dz, KS) > workspace_bytes || n_el * sizeof(float) > 48 * 1024) return false;
+    DirectParams p = direct_params(x_raw, dz, nullptr, ConvEpilogue(), workspace);
     p.bpi = bpi;
-    fill_tiles(p, N);
     dispatch_direct(s, p, true, N * bpi, /*exact_grid=*/true);
     float* perimg = workspace + (size_t)N * bpi * n_el;
     DL4DS_LAUNCH(att_wgrad_per_image_kernel, dim3(N), dim3(256), n_el * sizeof(float), s, workspace, perimg, w, ds, bpi, n_el,
@@ -1012,11 +985,5 @@ bool conv2d_direct_wgrad_attention(hipStream_t s, const TView& x_raw, const TVie
 }
 
 int conv2d_direct_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* partial, int slabs) {
-    DirectParams p;
-    p.in = x; p.out = dz; p.add = TView{nullptr, 0, 0, 0, 0, 0, 0, 0}; p.mask = p.add;
-    p.w = nullptr; p.bias = nullptr; p.partial = partial;
-    p.Cin = x.C; p.Cout = dz.C; p.H = x.H; p.W = x.W;
-    p.relu = 0; p.accumulate = 0;
-    fill_tiles(p, x.N);
-    return dispatch_direct(s, p, true, slabs);
+    return dispatch_direct(s, direct_params(x, dz, nullptr, ConvEpilogue(), partial), true, slabs);
 }

@@ -15,7 +15,7 @@
 //   * 16 x 32-pixel tiles, 4 waves x 8 rows, persistent over tiles, several blocks per CU so that staging and the
 //     epilogue of one block overlap with another block's MFMAs.
 // Forward and dgrad (flipped/transposed filter) both run through it; the epilogue is the shared conv_epilogue.
-#include "ops.h"
+#include "conv_route.h"
 #include "prof.h"
 #include "conv_kernels.h"
 #include "launch.h"
@@ -25,7 +25,8 @@
 
 namespace {
 
-constexpr int NTW = 16, NTH = 32, NROWS = 8;      // tile width / height, rows per wave
+using namespace conv_route;                       // NTW x NTH: tile width / height
+constexpr int NROWS = 8;                          // rows per wave
 #ifndef NARROW_PAIR_ROWS
 #define NARROW_PAIR_ROWS 4
 #endif
@@ -1743,19 +1744,7 @@ __global__ void __launch_bounds__(256, PZ == 8 ? 4 : 2) conv_narrow_wgrad_kernel
     }
 }
 
-bool narrow_wgrad_eligible(const TView& x, const TView& dz, int KS) {
-    if (x.sc) return false;                                   // only the dz operand takes a channel affine here
-    if (KS != 3 || x.C > 8 || dz.C > 16 || x.d2s > 1 || dz.d2s > 1 || !dz.vec) return false;    // x may be unaligned / Cin % 4 != 0
-    return (long)cdiv(x.W, NTW) * cdiv(x.H, NTH) * x.N < (1l << 20);                   // fast_div range
-}
-
 }  // namespace
-
-int conv2d_narrow_wgrad_slabs(const TView& x, const TView& dz, int KS) {
-    if (!narrow_wgrad_eligible(x, dz, KS)) return 0;
-    const int ntiles = cdiv(x.W, NTW) * cdiv(x.H, NTH) * x.N;
-    return std::max(1, std::min(ntiles, 1024));
-}
 
 int conv2d_narrow_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* partial, int max_slabs) {
     NarrowWgradParams p;
@@ -1786,27 +1775,10 @@ int conv2d_narrow_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, 
     return blocks;
 }
 
-// <= 8 x <= 8 channels with float4-able outputs: two pixels per MFMA column (1.5x fewer MFMAs, all lanes store);
-// the only variant that also takes inputs whose channel count is not a multiple of 4.  Also the only narrow variant that
-// reads a view with a channel affine (float4-loadable inputs only) and emits the pooling partial sums.
-bool conv2d_narrow_pair_ok(const TView& in, const TView& out, int KS, const ConvEpilogue& ep) {
-    if (KS != 3 || in.d2s > 1 || exp_env("DL4DS_NO_PAIR") || exp_env("DL4DS_NO_NARROW")) return false;
-    if ((long)cdiv(in.W, NTW) * cdiv(in.H, NTH) * in.N >= (1l << 20)) return false;    // fast_div range
-    return in.C <= 8 && out.C <= 8 && (out.C & 3) == 0 && out.vec && (!ep.add.p || ep.add.vec) &&
-           (!ep.mask.p || ep.mask.vec) && ((((uintptr_t)ep.bias) & 15) == 0) && (!in.sc || (in.vec && (in.C & 3) == 0));
-}
 int conv2d_narrow_pair_tiles_per_image(int H, int W) { return cdiv(W, 32) * cdiv(H, 4 * NARROW_PAIR_ROWS); }
 
-bool conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
-                           const ConvEpilogue& ep) {
-    if (KS != 3 || in.C > 16 || out.C > 16 || in.d2s > 1) return false;
-    const bool pair_ok = conv2d_narrow_pair_ok(in, out, KS, ep);
-    // 9..16 input channels that are not a multiple of four (the 13-channel ConvBlock behind TransitionLast 26 -> 13): the halo
-    // staging's float4 loads only need dword alignment; channels beyond Cin are masked when the tile is written to LDS
-    const bool unaligned_ok = in.C > 8 && in.d2s <= 1 && !in.sc && !ep.pool && !exp_env("DL4DS_NO_NARROW_UNALIGNED");
-    if (!in.vec && !pair_ok && !unaligned_ok) return false;
-    if ((long)cdiv(in.W, NTW) * cdiv(in.H, NTH) * in.N >= (1l << 20)) return false;    // fast_div range
-    DL4DS_REQUIRE(pair_ok || (!in.sc && !ep.pool), "conv_narrow: channel-affine input / pooling partials need the pair kernel");
+// launch half of the narrow path: conv2d_forward_route (conv_route.h) says which calls come here and which of them are the pair kernel's
+void conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep, bool pair_ok) {
     ConvParams p;
     p.in = in; p.out = out; p.add = ep.add; p.mask = ep.mask;
     p.w = w; p.bias = ep.bias;
@@ -1816,12 +1788,9 @@ bool conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, int K
     p.pool = ep.pool;
     if (pair_ok) {
         launch_narrow_pair<NARROW_PAIR_ROWS>(s, p, in.N);
-        return true;
+        return;
     }
-    if (in.C > 8 && out.C <= 8 && launch_narrow_pair16(s, p, in.N)) return true;
-    {
-        const bool done = launch_narrow16_ws<4>(s, p, in.N);
-        if (!done) { if (in.C <= 8) launch_narrow<8>(s, p, in.N); else launch_narrow<16>(s, p, in.N); }
-    }
-    return true;
+    if (in.C > 8 && out.C <= 8 && launch_narrow_pair16(s, p, in.N)) return;
+    if (launch_narrow16_ws<4>(s, p, in.N)) return;
+    if (in.C <= 8) launch_narrow<8>(s, p, in.N); else launch_narrow<16>(s, p, in.N);
 }

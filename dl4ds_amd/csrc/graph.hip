@@ -1,5 +1,6 @@
 // Graph runtime + op implementations (forward and hand-written backward) -- see graph.h.
 #include "graph.h"
+#include "conv_route.h"
 #include <cstdlib>
 #include "prof.h"
 #include "conv_cache.h"
@@ -483,8 +484,8 @@ struct ConvOp : GOp {
     size_t workspace_bytes(Graph& g, int B) override {
         TView x = g.view(in, B, false);
         TView dz = make_view(nullptr, x.N, x.H, x.W, Cout);
-        const size_t att_ws = (size_t)(1024 + x.N) * ((size_t)KS * KS * x.C * Cout + Cout) * sizeof(float);   // per-image slabs
-        return std::max(std::max(conv2d_wgrad_workspace_bytes(x, dz, KS), bias_grad_workspace_bytes(dz)), att_before ? att_ws : 0);
+        const size_t att_ws = att_before ? conv2d_direct_wgrad_attention_workspace_bytes(x, dz, KS) : 0;      // per-image slabs
+        return std::max(std::max(conv2d_wgrad_workspace_bytes(x, dz, KS), bias_grad_workspace_bytes(dz)), att_ws);
     }
     void backward(Graph& g, const BwdCtx& c) override {
         if (!g.tensors[out].grad_written) return;      // nothing flowed into this op
@@ -663,14 +664,15 @@ struct ChAttOp : GOp {
             ep.bias = producer->b >= 0 ? g.wp(producer->b) : nullptr;
             if (producer->add >= 0) ep.add = g.view(producer->add, B, false);
             TView pin = producer->in_view(g, B, 0, -1), pout = g.view(in, B, false);
-            fz.fuse_pool = !conv2d_direct_eligible(pin, pout, producer->KS) && conv2d_narrow_pair_ok(pin, pout, producer->KS, ep);
+            fz.fuse_pool = conv2d_forward_route(pin, pout, producer->KS, ep).family == ConvFwdFamily::NarrowPair;
         }
         // ---- scale applied by the consumer's loads: `out` has exactly one reader, a 3x3 convolution on the stencil kernels
         if (consumer && !is_output(out) && to.n_conv_in == 1 && to.n_add_in == 0 && to.n_masking == 0 && to.n_other == 0 && consumer->KS == 3) {
             TView x = g.view(in, B, false);
             x.sc = scale;
             TView y = make_view(nullptr, x.N, x.H, x.W, consumer->Cout);
-            fz.fuse_scale = conv2d_direct_eligible(x, y, 3);
+            const ConvFwdRoute r = conv2d_forward_route(x, y, 3, ConvEpilogue());
+            fz.fuse_scale = r.family == ConvFwdFamily::Direct && !r.refusal;
         }
         // ---- dX applied by the producer's backward loads: linear producer without a residual operand, narrow kernels
         if (producer && in_private && producer->relu == 0 && producer->add < 0 && producer->d2s <= 1 && producer->KS == 3 &&
@@ -678,18 +680,15 @@ struct ChAttOp : GOp {
             TView dz = g.view(out, B, true);
             dz.sc = scale; dz.sh = dmean;
             TView px = producer->in_view(g, B, 0, -1);
-            TView dz_plain = dz;
-            dz_plain.sc = dz_plain.sh = nullptr;
             // weight gradient: the narrow kernel takes the affine on its dz operand (the stencil wgrad does not)
-            bool ok = !px.sc && !conv2d_direct_eligible(px, dz_plain, 3) && conv2d_narrow_wgrad_slabs(px, dz, 3) > 0;
+            const bool ok = conv2d_wgrad_route(px, dz, 3).family == WgradFamily::Narrow;
             // input gradient = convolution of dY: stencil or pair kernel, both read the affine
             ConvEpilogue ep;
             const GTensor& tpi = g.tensors[producer->in];
             TView dx = make_view(tpi.grad ? tpi.grad : tpi.data, px.N, px.H, px.W, px.C);
             if (tpi.grad_masked) ep.mask = g.view(producer->in, B, false);
-            ok = ok && (conv2d_direct_eligible(dz, dx, 3) ||
-                        (!conv2d_direct_eligible(dz_plain, dx, 3) && conv2d_narrow_pair_ok(dz, dx, 3, ep)));
-            fz.fuse_dx = ok;
+            const ConvFwdRoute rd = conv2d_forward_route(dz, dx, 3, ep);
+            fz.fuse_dx = ok && !rd.refusal && (rd.family == ConvFwdFamily::Direct || rd.family == ConvFwdFamily::NarrowPair);
         }
     }
     void forward(Graph& g, int B, bool) override {

@@ -13,7 +13,7 @@ struct ConvEpilogue {
     int accumulate = 0;            // out += result (gradient accumulation)
     // optional [tiles][8] per-tile channel sums of the stored values (tiles of one image contiguous, see
     // conv2d_narrow_pair_tiles_per_image): the pooling of a ChannelAttention2D that consumes this output.  Only the
-    // narrow pair kernel emits it; callers check conv2d_narrow_pair_ok first, every other path rejects it.
+    // narrow pair kernel emits it (conv2d_forward_route(..).family == NarrowPair, conv_route.h), every other path rejects it.
     float* pool = nullptr;
     // Second output pairs (both with the output's shape and layout; conv2d_forward_fused only, see there):
     //   sum_out = v + sum_add, v the value stored to `out` (AFTER the activation -- not `add`, which comes before it): an Add that
@@ -40,25 +40,22 @@ void conv2d_dgrad_weights_batched(hipStream_t s, const DgradWeightsJob* jobs_dev
 size_t conv2d_wgrad_workspace_bytes(const TView& x, const TView& dz, int KS);
 void conv2d_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* dw, int accumulate, float* db,
                   int accumulate_db, float* workspace, size_t workspace_bytes);
-// Stencil (VALU) path for 3x3 layers with pad2(Cin)*pad2(Cout) <= 8 (conv_direct.hip); conv2d_forward / conv2d_wgrad
-// route to it themselves.  forward returns false when the layer is not eligible; wgrad_slabs returns 0.
-bool conv2d_direct_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
-                           const ConvEpilogue& ep);
-// 3x3, Cin <= 16, Cout <= 16: register-resident filter, persistent MFMA kernel (conv_narrow.hip)
-bool conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
-                           const ConvEpilogue& ep);
+// Which family takes a layer is stated once, by conv2d_forward_route / conv2d_wgrad_route (conv_route.h): conv2d_forward / conv2d_wgrad
+// follow them, a caller that plans around a family (pooling partials, a channel-affine view) asks them; the entry points below only launch.
+// Stencil (VALU) path for 3x3 layers with pad2(Cin)*pad2(Cout) <= 8 (conv_direct.hip)
+void conv2d_direct_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
+// 3x3, Cin <= 16, Cout <= 16: register-resident filter, persistent MFMA kernel (conv_narrow.hip); pair_ok: the route is NarrowPair
+void conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep, bool pair_ok);
 // 1x1 layers whose channel counts are not multiples of four (conv_point.hip): contiguous staging + MFMA + contiguous store
 bool conv2d_point_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out, const ConvEpilogue& ep);
-bool conv2d_narrow_pair_ok(const TView& in, const TView& out, int KS, const ConvEpilogue& ep);
 int conv2d_narrow_pair_tiles_per_image(int H, int W);
-bool conv2d_direct_eligible(const TView& in, const TView& out, int KS);
 // weight gradient of a stencil convolution behind a ChannelAttention2D scale + the attention's d(loss)/d(scale), both from
 // per-image raw weight gradients (conv_direct.hip); false: not eligible, nothing was launched
 bool conv2d_direct_wgrad_attention(hipStream_t s, const TView& x_raw, const TView& dz, int KS, const float* scale, const float* w,
                                    float* dw, int accumulate, float* db, int accumulate_db, float* ds, float* workspace,
                                    size_t workspace_bytes);
+size_t conv2d_direct_wgrad_attention_workspace_bytes(const TView& x_raw, const TView& dz, int KS);      // (what it asks of `workspace`)
 // 3x3 wgrad with Cin <= 8, Cout <= 16 (two taps per MFMA tile); same slab protocol as the direct path
-int conv2d_narrow_wgrad_slabs(const TView& x, const TView& dz, int KS);
 int conv2d_narrow_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* partial, int max_slabs);
 // 3x3, Cin >= 16: filter streamed from L2 into the MFMA operands, no barriers in the K loop (conv_stream.hip)
 // small grids (H W <= max_hw) with many channels as a GEMM over flattened pixels (conv_gemm.hip); false = not eligible
@@ -85,7 +82,6 @@ void split_filters_release(const float* lo, const float* hi);
 bool conv2d_wino_wgrad(hipStream_t s, const TView& x, const TView& dy, float* dw, int accumulate, float* db, int accumulate_db);
 bool conv2d_stream_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out,
                            const ConvEpilogue& ep);
-int conv2d_direct_wgrad_slabs(const TView& x, const TView& dz, int KS);
 // writes at most `slabs` partial slabs (the workspace bound); returns how many it wrote
 int conv2d_direct_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float* partial, int slabs);
 // Conv2DTranspose(k, stride s, 'same', no bias), kernel HWOI [k*k][Cout][Cin] (blocks.py:508-516)

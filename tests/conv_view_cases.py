@@ -32,11 +32,11 @@ T_FRAMES, T_PICK = 3, 1
 
 # refusal messages (substrings of dl4ds_last_error)
 R_ENTRY = 'only a read operand'                               # capi.cpp desc_view: y / add / mask descriptors with sc
-R_DIRECT = 'conv_direct: channel-affine input needs float4-loadable channels'       # conv_direct.hip conv2d_direct_forward
-R_NARROW = 'conv_narrow: channel-affine input / pooling partials need the pair kernel'  # conv_narrow.hip conv2d_narrow_forward
-R_CONV = 'conv2d: channel-affine input / pooling partials are only implemented'     # conv.hip conv2d_forward
-R_WGRAD = 'wgrad: channel-affine operands are only implemented'                     # conv.hip conv2d_wgrad
-R_DIRECT_WG = 'conv_direct wgrad: only a float4-loadable x operand may carry a channel affine'   # conv_direct.hip ..._wgrad_slabs
+R_DIRECT = 'conv_direct: channel-affine input needs float4-loadable channels'       # conv_route.h conv2d_forward_route
+R_NARROW = 'conv_narrow: channel-affine input / pooling partials need the pair kernel'  # conv_route.h conv2d_forward_route
+R_CONV = 'conv2d: channel-affine input / pooling partials are only implemented'     # conv_route.h conv2d_forward_route
+R_WGRAD = 'wgrad: channel-affine operands are only implemented'                     # conv_route.h conv2d_wgrad_route
+R_DIRECT_WG = 'conv_direct wgrad: only a float4-loadable x operand may carry a channel affine'   # conv_route.h conv2d_wgrad_route
 
 
 def run(tag):
@@ -306,28 +306,28 @@ def _cells(roles, forms, outcome):
 
 
 _fam('direct_3_1', 'fwd', (2, 9, 33, 3, 1, 3), 'conv_direct<3,4,1>', outcomes=_affine_all(R_DIRECT), dgrad_tag='conv_direct<3,1,4>',
-     why={'affine': 'conv_direct.hip affine_ok (conv2d_direct_forward requires it): Cin = 3 is not float4-loadable'})
+     why={'affine': 'conv_route.h affine_ok (conv2d_forward_route requires it): Cin = 3 is not float4-loadable'})
 _fam('direct_1_3', 'fwd', (2, 8, 32, 1, 3, 3), 'conv_direct<3,1,4>', outcomes=_affine_all(R_DIRECT), dgrad_tag='conv_direct<3,4,1>',
-     why={'affine': 'conv_direct.hip affine_ok: Cin = 1 is not float4-loadable'})
+     why={'affine': 'conv_route.h affine_ok: Cin = 1 is not float4-loadable'})
 # (not in test_gpu_ops' CONV_CASES as a forward shape: test_conv2d_fused_epilogues_stencil_path's 8 -> 1 grid, the one stencil
 # shape whose input a channel affine can ride on)
 _fam('direct_8_1', 'fwd', (2, 19, 45, 8, 1, 3), 'conv_direct<3,8,1>', dgrad_tag='conv_direct<3,1,8>',
      outcomes=_merge(_affine_all(R_DIRECT), _cells('x', ('affine_s', 'affine_sh'), run('conv_direct<3,8,1>'))),
-     why={'affine': 'conv_direct.hip affine_ok holds (Cin = 8, float4-loadable): conv_direct_kernel / conv_direct2_kernel apply sc / sh'})
+     why={'affine': 'conv_route.h affine_ok holds (Cin = 8, float4-loadable): conv_direct_kernel / conv_direct2_kernel apply sc / sh'})
 _fam('pair_8_8', 'fwd', (2, 21, 70, 8, 8, 3), 'conv_narrow_pair_ws<', dgrad_slice1_tag=IGEMM,
      outcomes=_merge(_affine_all(R_CONV), _cells('x', ('affine_s', 'affine_sh'), run('conv_narrow_pair_ws<')),
                      _cells(OUT_SIDE, ('slice1',), run('conv_narrow<8>'))),
-     why={'affine': 'conv_narrow.hip conv2d_narrow_pair_ok / narrow_pair_ws_ok: float4-loadable input with Cin % 4 == 0 -> PAIR_EPI_AFF forms',
-          'slice1': 'conv_narrow.hip conv2d_narrow_pair_ok: out / add / mask must be float4-accessible -> conv_narrow_kernel<8>; as a '
+     why={'affine': 'conv_route.h narrow_pair_ok / conv_narrow.hip narrow_pair_ws_ok: float4-loadable input with Cin % 4 == 0 -> PAIR_EPI_AFF forms',
+          'slice1': 'conv_route.h narrow_pair_ok: out / add / mask must be float4-accessible -> conv_narrow_kernel<8>; as a '
                     'dgrad with every operand at that pitch the input is not float4-loadable either and the narrow path declines'})
 _fam('pair_5_8', 'fwd', (2, 21, 70, 5, 8, 3), 'conv_narrow_pair_ws<', dgrad_tag='conv_narrow16_ws<', dgrad_slice1_tag=IGEMM,
      outcomes=_merge(_affine_all(R_CONV), _cells(OUT_SIDE, ('slice1',), run(IGEMM))),
-     why={'affine': 'conv_narrow.hip conv2d_narrow_pair_ok: sc needs Cin % 4 == 0; conv2d_narrow_forward then declines (no float4 input, '
-                    'not the pair kernel) and conv.hip conv2d_forward refuses',
-          'slice1': 'conv_narrow.hip conv2d_narrow_forward: !in.vec && !pair_ok && Cin <= 8 -> declined; no other family takes 5 channels'})
+     why={'affine': 'conv_route.h narrow_pair_ok: sc needs Cin % 4 == 0; conv2d_forward_route then passes the narrow family by (no float4 input, '
+                    'not the pair kernel) and refuses',
+          'slice1': 'conv_route.h conv2d_forward_route: !in.vec && !pair && Cin <= 8 -> not the narrow family; no other family takes 5 channels'})
 _fam('narrow16', 'fwd', (2, 17, 16, 15, 16, 3), 'conv_narrow16_ws<',
      outcomes=_merge(_affine_all(R_CONV), _cells(OUT_SIDE, PITCHED, run('conv_narrow<16>'))),
-     why={'affine': 'conv_narrow.hip narrow16_ws_ok / conv2d_narrow_forward: no channel affine outside the pair kernel',
+     why={'affine': 'conv_narrow.hip narrow16_ws_ok / conv_route.h conv2d_forward_route: no channel affine outside the pair kernel',
           'pitched': 'conv_narrow.hip narrow16_ws_ok: add and mask must share the output\'s layout (same_layout); with ONE of the three '
                      'at another pitch the older conv_narrow_kernel<16> runs.  All three at one pitch (the all-roles cell) stay.'})
 _fam('pair16', 'fwd', (2, 20, 33, 13, 8, 3), 'conv_narrow_pair16_ws<', dgrad_tag='conv_narrow16_ws<', dgrad_slice1_tag=IGEMM,
@@ -376,20 +376,20 @@ _fam('wg_general_1', 'wgrad', (4, 64, 64, 8, 48, 1), 'conv_wgrad_rows<1,', outco
 _fam('wg_general_3', 'wgrad', (2, 24, 24, 50, 40, 3), 'conv_wgrad_rows<3,3,', outcomes=_WG_NONE, why=_WG_WHY)
 _fam('wg_general_5', 'wgrad', (2, 16, 16, 6, 12, 5), 'conv_wgrad_rows<5,', outcomes=_WG_NONE, why=_WG_WHY)
 _fam('wg_direct', 'wgrad', (2, 9, 33, 3, 1, 3), 'conv_direct_wgrad<3,4,1>', outcomes=_wg_affine(refused(R_DIRECT_WG), refused(R_DIRECT_WG)),
-     why={'affine': 'conv_direct.hip conv2d_direct_wgrad_slabs: affine_ok(x) fails on Cin = 3; dz never takes one'})
+     why={'affine': 'conv_route.h conv2d_wgrad_route: affine_ok(x) fails on Cin = 3; dz never takes one'})
 _fam('wg_direct2', 'wgrad', (2, 19, 45, 8, 1, 3), 'conv_direct_wgrad<3,8,1>', bits_differ=[('x', 'slice1')],
      outcomes=_wg_affine(run('conv_direct_wgrad<3,8,1>'), refused(R_DIRECT_WG)),
-     why={'affine': 'conv_direct.hip conv2d_direct_wgrad_slabs: a float4-loadable x may carry one, dz never',
+     why={'affine': 'conv_route.h conv2d_wgrad_route: a float4-loadable x may carry one, dz never',
           'bits': 'conv_direct.hip direct2_ok: Cin >= 4 needs in.vec, so x at a pitch of 13 floats runs conv_direct_wgrad_kernel (first '
                   'generation, other tile height and summation order) under the SAME tag as conv_direct2_wgrad_kernel'})
 _fam('wg_narrow8', 'wgrad', (2, 21, 70, 8, 8, 3), 'conv_narrow_wgrad<8>',
      outcomes=_merge(_wg_affine(refused(R_WGRAD), run('conv_narrow_wgrad<8>')), {('dz', 'slice1'): run('conv_wgrad_rows<3,1,')}),
-     why={'affine': 'conv_narrow.hip conv2d_narrow_wgrad_slabs: x.sc declines, dz.sc is applied in the staging loads',
-          'slice1': 'conv_narrow.hip conv2d_narrow_wgrad_slabs: !dz.vec declines -> the general kernel'})
+     why={'affine': 'conv_route.h narrow_wgrad_eligible: x.sc declines, dz.sc is applied in the staging loads',
+          'slice1': 'conv_route.h narrow_wgrad_eligible: !dz.vec declines -> the general kernel'})
 _fam('wg_two_slice', 'wgrad', (2, 20, 33, 13, 8, 3), 'conv_narrow_wgrad<8>',
      outcomes=_merge(_wg_affine(refused(R_WGRAD), run('conv_narrow_wgrad<8>')), {('dz', 'slice1'): run('conv_wgrad_rows<3,1,')}),
-     why={'affine': 'conv.hip narrow_wgrad_split_slabs: x.sc declines; dz.sc goes through conv_narrow_wgrad_kernel<8> of both slices',
-          'slice1': 'conv.hip narrow_wgrad_split_slabs: !dz.vec declines -> the general kernel'})
+     why={'affine': 'conv_route.h conv2d_wgrad_route (NarrowSlices): x.sc declines; dz.sc goes through conv_narrow_wgrad_kernel<8> of both slices',
+          'slice1': 'conv_route.h conv2d_wgrad_route (NarrowSlices): !dz.vec declines -> the general kernel'})
 _fam('wg_rows', 'wgrad', (2, 17, 16, 8, 32, 3), 'conv_wgrad_rows<3,1,', outcomes=_WG_NONE, why=_WG_WHY)
 _fam('wg_wino', 'wgrad', (2, 17, 19, 24, 32, 3), 'conv_wino_wgrad<', env={'DL4DS_WINO_FORCE': 'all'},
      outcomes=_merge(_WG_NONE, _cells(WG_ROLES, ('slice1',), run('conv_wgrad_rows<3,2,'))),

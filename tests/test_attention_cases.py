@@ -87,16 +87,25 @@ def test_launcher_conditions_match_the_source():
     narrow = _src('conv_narrow.hip')
     assert f'#defineNARROW_PAIR_ROWS{K.NARROW_PAIR_ROWS}#endif' in narrow
     assert f'returncdiv(W,{K.POOL_TILE_W})*cdiv(H,4*NARROW_PAIR_ROWS);' in narrow
-    assert 'returnin.C<=8&&out.C<=8&&(out.C&3)==0&&out.vec&&' in narrow
-    direct = _src('conv_direct.hip')
-    assert 'returnpad_pow2(in.C)*pad_pow2(out.C)<=8;' in direct
-    assert 'staticboolaffine_ok(constTView&v){return!v.sc||(v.vec&&(v.C&3)==0&&v.C>=4);}' in direct
+    # which family takes a layer is stated once, in conv_route.h: the families' conditions ...
+    route = _src('conv_route.h')
+    assert 'returnin.C<=8&&out.C<=8&&(out.C&3)==0&&out.vec&&' in route
+    assert 'returnpad_pow2(in.C)*pad_pow2(out.C)<=8;' in route
+    assert 'inlineboolaffine_ok(constTView&v){return!v.sc||(v.vec&&(v.C&3)==0&&v.C>=4);}' in route
+    # ... the order in which the routes ask them (the stencil kernels first, the pair kernel before the other narrow ones) ...
+    for piece in ('if(eligible(in,out,KS)){if(!affine_ok(in)||ep.pool)return{ConvFwdFamily::Direct,"conv_direct:',
+                  'if(pair)return{ConvFwdFamily::NarrowPair,nullptr};',
+                  'if(eligible(x,dz,KS))return{WgradFamily::Direct,slabs(DTX,DTY),(affine_ok(x)&&!dz.sc)?nullptr:"conv_directwgrad:',
+                  'if(narrow_wgrad_eligible(x,dz,KS))return{WgradFamily::Narrow,slabs(NTW,NTH),nullptr};'):
+        assert piece in route, piece
+    # ... and the planner's three decisions as questions put to the routes
     gr = _src('graph.hip')
     for piece in ('if(producer&&producer->d2s<=1&&ti.C<=8){',
-                  'fz.fuse_pool=!conv2d_direct_eligible(pin,pout,producer->KS)&&conv2d_narrow_pair_ok(pin,pout,producer->KS,ep);',
-                  'fz.fuse_scale=conv2d_direct_eligible(x,y,3);',
-                  'boolok=!px.sc&&!conv2d_direct_eligible(px,dz_plain,3)&&conv2d_narrow_wgrad_slabs(px,dz,3)>0;',
-                  'ok=ok&&(conv2d_direct_eligible(dz,dx,3)||(!conv2d_direct_eligible(dz_plain,dx,3)&&conv2d_narrow_pair_ok(dz,dx,3,ep)));',
+                  'fz.fuse_pool=conv2d_forward_route(pin,pout,producer->KS,ep).family==ConvFwdFamily::NarrowPair;',
+                  'constConvFwdRouter=conv2d_forward_route(x,y,3,ConvEpilogue());fz.fuse_scale=r.family==ConvFwdFamily::Direct&&!r.refusal;',
+                  'constboolok=conv2d_wgrad_route(px,dz,3).family==WgradFamily::Narrow;',
+                  'constConvFwdRouterd=conv2d_forward_route(dz,dx,3,ep);'
+                  'fz.fuse_dx=ok&&!rd.refusal&&(rd.family==ConvFwdFamily::Direct||rd.family==ConvFwdFamily::NarrowPair);',
                   'if(T5>0||test_env("DL4DS_NO_TAIL_FUSION"))return;',
                   'g.tensors[in].grad_written,shape(g,c.B)',                    # accumulate_dx
                   'constintaccw=g.params[w1].grad_written;'):                    # accumulate_dw
