@@ -46,6 +46,8 @@ def __getattr__(name):
             'label_objects': '.objects', 'sal_scores': '.objects', 'object_scores': '.objects',
             'distance_transform': '.distance', 'distance_scores': '.distance', 'distance_from_sums': '.distance',
             'check_distance_args': '.distance',
+            'Regridder': '.regrid', 'regrid': '.regrid', 'axis_table': '.regrid', 'check_regrid_args': '.regrid',
+            'consistency_scores': '.regrid', 'consistency_from_sums': '.regrid',
             'distribution_scores': '.metrics', 'quantile_maps': '.metrics',
             'spectral_scores': '.metrics', 'power_spectrum': '.metrics',
             'QuantileMapper': '.postprocessing', 'quantile_map': '.postprocessing', 'check_qmap_args': '.postprocessing',

@@ -9,6 +9,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <mutex>
+#include <set>
 #include <vector>
 
 // ---- internal functions defined in other translation units
@@ -558,6 +559,59 @@ int dl4ds_tile_merge(const float* tiles_dev, int n, int th, int tw, int C, const
     const int* d_lists = upload_tile_lists(src, 5, n);
     tile_merge(S(), tiles_dev, wy_dev, wx_dev, out_dev, d_lists, d_lists + n, d_lists + 2 * n, d_lists + 3 * n, d_lists + 4 * n, n, th,
                tw, C, H, W, vec);
+    API_END
+}
+// ---- regridding (regrid.hip).  A handle is valid from plan_create to plan_destroy: the live ones are kept here, so that a null, a
+// destroyed or a foreign handle is refused rather than followed.
+static std::set<const void*>& regrid_plans() {
+    static std::set<const void*> live;
+    return live;
+}
+static RegridPlan* regrid_plan_of(const char* what, const dl4ds_regrid_plan* plan) {
+    DL4DS_REQUIRE(plan && regrid_plans().count(plan), std::string(what) + ": null or destroyed plan");
+    return reinterpret_cast<RegridPlan*>(const_cast<dl4ds_regrid_plan*>(plan));
+}
+int dl4ds_regrid_plan_create(int H, int W, int Ho, int Wo, const int* yptr_host, const int* yidx_host, const double* yw_host,
+                             const int* xptr_host, const int* xidx_host, const double* xw_host, const double* ay_host,
+                             const double* ax_host, dl4ds_regrid_plan** plan) {
+    API_BEGIN
+    DL4DS_REQUIRE(plan, "regrid_plan_create: null handle pointer");
+    *plan = nullptr;
+    RegridPlan* p = regrid_plan_create(S(), H, W, Ho, Wo, yptr_host, yidx_host, yw_host, xptr_host, xidx_host, xw_host, ay_host, ax_host);
+    regrid_plans().insert(p);
+    *plan = reinterpret_cast<dl4ds_regrid_plan*>(p);
+    API_END
+}
+int dl4ds_regrid_plan_destroy(dl4ds_regrid_plan* plan) {
+    API_BEGIN
+    RegridPlan* p = regrid_plan_of("regrid_plan_destroy", plan);
+    regrid_plans().erase(plan);
+    regrid_plan_destroy(S(), p);
+    API_END
+}
+int dl4ds_regrid_apply(const dl4ds_regrid_plan* plan, const float* x_dev, int N, int C, int skipna, double min_valid, float* out_dev) {
+    API_BEGIN
+    const RegridPlan* p = regrid_plan_of("regrid_apply", plan);
+    regrid_check_call("regrid_apply", p, x_dev, N, C, min_valid);
+    DL4DS_REQUIRE(out_dev, "regrid_apply: null output pointer");
+    DL4DS_REQUIRE(out_dev != x_dev, "regrid_apply: the output must not alias the input");
+    // a kernel of an earlier call raised the device error word: what this call would read is invalid.  The word stays set; the next
+    // host-side wait (dl4ds_sync) reports and clears it.
+    DL4DS_REQUIRE(!g_err_host || *reinterpret_cast<volatile unsigned*>(g_err_host) == 0u,
+                  "regrid_apply: device error word set (dl4ds_sync reports and clears it)");
+    regrid_apply(S(), p, x_dev, N, C, skipna != 0, min_valid, out_dev);
+    API_END
+}
+int dl4ds_regrid_consistency(const dl4ds_regrid_plan* plan, const float* x_dev, const float* ref_dev, int N, int C, int skipna,
+                             double min_valid, double* sums_dev, long long* counts_dev, float* resid_dev) {
+    API_BEGIN
+    const RegridPlan* p = regrid_plan_of("regrid_consistency", plan);
+    regrid_check_call("regrid_consistency", p, x_dev, N, C, min_valid);
+    DL4DS_REQUIRE(ref_dev && sums_dev && counts_dev, "regrid_consistency: null pointer");
+    DL4DS_REQUIRE(!g_err_host || *reinterpret_cast<volatile unsigned*>(g_err_host) == 0u,
+                  "regrid_consistency: device error word set (dl4ds_sync reports and clears it)");
+    const size_t ws = regrid_consistency_workspace_bytes(p, N, C);
+    regrid_consistency(S(), p, x_dev, ref_dev, N, C, skipna != 0, min_valid, sums_dev, counts_dev, resid_dev, scratch(ws));
     API_END
 }
 int dl4ds_op_depth_to_space(const float* x, float* y, int N, int H, int W, int C, int r) {

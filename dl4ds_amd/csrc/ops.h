@@ -248,6 +248,20 @@ void distance_check_args(const float* y, const float* p, int N, int H, int W, in
 void distance_scores(hipStream_t s, const float* y, const float* p, int N, int H, int W, int C, const float* thresholds, int T,
                      double cutoff, double alpha, long long* counts, double* sums, int* d2_obs, int* d2_pred, void* workspace,
                      size_t workspace_bytes);
+// Regridding between rectilinear grids (regrid.hip).  A plan holds the two axis tables (CSR, fp64 weights) and
+// the destination cell measures on the device; plan_create validates the host tables and throws before anything is allocated.
+// apply: x (N, H, W, C) -> out (N, H', W', C).  consistency: sums [N][C][6], counts [N][C][2] of the regridded x against ref
+// (N, H', W', C), resid (or null) the fp32 residual; workspace: regrid_consistency_workspace_bytes.  regrid_check_call throws on a
+// call the entries refuse.
+struct RegridPlan;
+RegridPlan* regrid_plan_create(hipStream_t s, int H, int W, int Ho, int Wo, const int* yptr, const int* yidx, const double* yw,
+                               const int* xptr, const int* xidx, const double* xw, const double* ay, const double* ax);
+void regrid_plan_destroy(hipStream_t s, RegridPlan* p);
+void regrid_check_call(const char* what, const RegridPlan* p, const float* x, int N, int C, double min_valid);
+size_t regrid_consistency_workspace_bytes(const RegridPlan* p, int N, int C);
+void regrid_apply(hipStream_t s, const RegridPlan* p, const float* x, int N, int C, bool skipna, double min_valid, float* out);
+void regrid_consistency(hipStream_t s, const RegridPlan* p, const float* x, const float* ref, int N, int C, bool skipna,
+                        double min_valid, double* sums, long long* counts, float* resid, void* workspace);
 // Distribution verification (distribution.hip) of S pairs of length-L segments, element k of segment s at [s*seg_stride +
 // k*elem_stride]: per segment quant [S][2][Q] (numpy 'linear' quantiles of the valid values of y, p), w1 [S] (1-Wasserstein), ks [S]
 // (n times the two-sample KS statistic), hist [S][2][E-1] (np.histogram over the E edges; may be null when E == 0), valid [S] (n).

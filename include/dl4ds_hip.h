@@ -953,6 +953,52 @@ int dl4ds_tile_pool(const float* tiles_dev, int n, int th, int tw, int C, const 
 int dl4ds_graph_chatt_info(dl4ds_graph* g, int index, int* tensor_in, int* channels, int* contiguous);
 int dl4ds_graph_chatt_set_mean(dl4ds_graph* g, int index, const float* mean_dev);
 
+/* ---------------------------------------------------------------- regridding between rectilinear grids
+ * No counterpart in the reference, whose one route between a coarse and a fine grid is the index-space resize of create_pair_hr_lr
+ * (dl4ds_batch_gather).  x [N][H][W][C] fp32 -> out [N][H'][W'][C] fp32 through one table per axis.  A table is CSR: the taps of
+ * destination index d are ptr[d] ... ptr[d + 1] - 1 (int), tap t reads source index idx[t] (int) with weight w[t] >= 0 (fp64);
+ * conservative, bilinear and nearest regridding on rectilinear grids all have this form (dl4ds_amd/regrid.py builds them).
+ *
+ * plan_create: host tables of both axes (y: H' + 1 ptr entries over sources 0 ... H - 1; x: W' + 1 over 0 ... W - 1) and the
+ * destination cell measures ay_host [H'], ax_host [W'] (fp64; the area of cell (i', j') is ay[i'] * ax[j'], used by the consistency
+ * sums only) -> a handle.  Refused before anything is allocated or uploaded: an extent < 1, H*W or H'*W' >= 2^31, a null table, a
+ * ptr that does not start at 0 or decreases, a source index out of range, a weight or measure that is negative or not finite.  The
+ * tables are uploaded once, synchronously.  plan_destroy waits for the library stream and frees them; the handle is dead afterwards.
+ *
+ * apply: one thread per output element (n, i', j', c) walks the y-taps a of i' in table order and inside each the x-taps b of j' in
+ * table order, in fp64 with every operation rounded on its own (no FMA contraction):
+ *     w = wy[a] * wx[b];   tot = tot + w
+ *     skipna and x not finite:  continue
+ *     num = num + w * (double)x[n, iy[a], ix[b], c];   den = den + w
+ *     out = (den > 0 and den >= min_valid * tot) ? (float)(num / den) : NaN
+ * Without skipna every tap is taken (den == tot; non-finite inputs propagate by IEEE rules); with it NaN and +-inf are dropped (the
+ * masking convention of dl4ds_quantile_table) and min_valid in [0, 1] is the share of the weight that must remain.  An output
+ * without taps is NaN; every NaN stored is the canonical quiet NaN 0x7fc00000.  No atomics: the result is a pure function of the input and the tables, the same bits for any N and any
+ * split of the samples into calls.  64-bit offsets.  16-byte accesses where C is a multiple of 4 and both pointers are 16-byte
+ * aligned (then W*C and W'*C are multiples of 4 too), 4-byte accesses otherwise.  The x-taps of a workgroup's columns sit in LDS
+ * (up to 2048 of them; beyond that they are read from the table in global memory), the y-taps of its row in scalar registers.
+ * Algorithmic traffic: 4 * N * C * (H W + H' W') bytes, one read of the input and one write of the output; when refining, the taps
+ * of neighbouring outputs overlap and the re-reads come from cache.  Asynchronous on the library stream; out_dev must not alias x_dev.
+ *
+ * consistency: r = the value apply stores (rounded to fp32), y = ref_dev[n, i', j', c] ([N][H'][W'][C] fp32).  A cell is valid where
+ * both are finite; there d = (double)r - (double)y and A = ay[i'] * ax[j'].  sums_dev [N][C][6] fp64: sum A, sum A*d, sum A*(d*d),
+ * sum A*y, sum A*r, max |d|;  counts_dev [N][C][2] int64: valid cells, cells where exactly one side is finite;  resid_dev (or NULL)
+ * [N][H'][W'][C] fp32: r - y, NaN where the cell is not valid.  ONE summation order (regrid_core.h): lane t of 256 joins the cells
+ * j' = t, t + 256, ... of a row in ascending j'; a fixed tree (o = 128 ... 1: lane t < o joins lane t + o) joins the lanes; the rows are
+ * joined in ascending i' from zero.  A repeated call, any N and any split of the samples give the same bits.  Outputs are
+ * overwritten.  Algorithmic traffic: 4 * N * C * (H W + H' W') bytes read (+ the residual written).  Asynchronous on the library stream.
+ *
+ * apply and consistency refuse, before anything is launched: a null or destroyed plan, null required pointers, N or C < 1, min_valid
+ * outside [0, 1] or NaN, and a call made while the device error word is set (it stays set for dl4ds_sync to report). */
+typedef struct dl4ds_regrid_plan dl4ds_regrid_plan;
+int dl4ds_regrid_plan_create(int H, int W, int Ho, int Wo, const int* yptr_host, const int* yidx_host, const double* yw_host,
+                             const int* xptr_host, const int* xidx_host, const double* xw_host, const double* ay_host,
+                             const double* ax_host, dl4ds_regrid_plan** plan);
+int dl4ds_regrid_plan_destroy(dl4ds_regrid_plan* plan);
+int dl4ds_regrid_apply(const dl4ds_regrid_plan* plan, const float* x_dev, int N, int C, int skipna, double min_valid, float* out_dev);
+int dl4ds_regrid_consistency(const dl4ds_regrid_plan* plan, const float* x_dev, const float* ref_dev, int N, int C, int skipna,
+                             double min_valid, double* sums_dev, long long* counts_dev, float* resid_dev);
+
 /* ---------------------------------------------------------------- data parallelism (RCCL over xGMI)
  * replaces Horovod: hvd.init/rank/size (base.py:97-107), DistributedOptimizer / DistributedGradientTape
  * gradient averaging (supervised.py:365; cgan.py:608-611), broadcast of variables + optimiser slots from
