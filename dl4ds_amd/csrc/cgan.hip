@@ -195,7 +195,15 @@ void cgan_step(CganTrainer& t, const float* const* gen_inputs, int n_gen_inputs,
             if (std::string(op->kind) == "norm") ok = false;
             bool reads = false;
             for (int tid : op->in_tids) reads = reads || (tid >= 0 && D.tensors[tid].is_input && D.tensors[tid].requires_grad);
-            if (reads) { ok = ok && op->out_tid >= 0; t.ratio_ops.push_back((int)i); }
+            if (reads) {
+                ok = ok && op->out_tid >= 0;
+                // a reader whose other operand descends from that input (the fused add of another reader's output): running its
+                // backward again would add its output gradient to that operand's a second time, before or after the operand's own
+                // rescaling -- not a graph this route can serve
+                for (int tid : op->in_tids)
+                    if (tid >= 0 && !(D.tensors[tid].is_input && D.tensors[tid].requires_grad) && D.tensors[tid].dep_grad_input) ok = false;
+                t.ratio_ops.push_back((int)i);
+            }
         }
         t.ratio_plan = (ok && !t.ratio_ops.empty()) ? 1 : 0;
     }
@@ -217,19 +225,24 @@ void cgan_step(CganTrainer& t, const float* const* gen_inputs, int n_gen_inputs,
             if (!to.grad_written) continue;
             TView gv = D.view(op->out_tid, 2 * B, true);
             const size_t per_img = (size_t)gv.H * gv.W * gv.C, total = per_img * gv.N;
-            DL4DS_LAUNCH(scale_samples_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, gv, t.ratio,
-                               per_img, to.nmul, total);
-            HIP_CHECK(hipGetLastError());
+            {
+                ProfScope ps(s, "cgan_scale_samples", (double)total, 2.0 * total * sizeof(float));     // (one scope per reader: the tests count them)
+                DL4DS_LAUNCH(scale_samples_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, gv, t.ratio,
+                                   per_img, to.nmul, total);
+                HIP_CHECK(hipGetLastError());
+            }
             op->backward(D, cr);
         }
     } else if (partial) {
         BwdCtx c2{2 * B, B, B, false, true};
+        ProfScope ps(s, "cgan_pass2_partial", 0.0, 0.0);
         D.backward(c2);
     } else {
         // ConvLSTM2D / channel attention back-propagate whole batches only: run the full batch with a zero output
         // gradient on the real half (samples are independent in D, so the fake half's input gradient is unchanged)
         fill(s, dout.grad, (size_t)B, 0.f);
         BwdCtx c2{2 * B, 0, 2 * B, false, true};
+        ProfScope ps(s, "cgan_pass2_zero_filled", 0.0, 0.0);
         D.backward(c2);
     }
     // ---- generator backward: lambda * dpx/dgen + dgan/dgen
