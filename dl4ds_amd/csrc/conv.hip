@@ -1531,6 +1531,7 @@ void conv2d_forward(hipStream_t s, const TView& in, const float* w, int KS, cons
         case ConvFwdFamily::Direct: return conv2d_direct_forward(s, in, w, out, ep);      // a handful of channels: HBM-bound stencil
         case ConvFwdFamily::NarrowPair: return conv2d_narrow_forward(s, in, w, out, ep, true);
         case ConvFwdFamily::Narrow: return conv2d_narrow_forward(s, in, w, out, ep, false);
+        case ConvFwdFamily::Pointwise: return conv2d_pointwise_forward(s, in, w, out, ep);      // 1x1, <= 48 channels: HBM stream
         case ConvFwdFamily::Rest: break;      // the try-and-launch families, in this order:
     }
     if (KS == 3 && conv2d_split_forward(s, in, w, out, ep)) return; // 40 / 48-channel 3x3 layers: fp32 products as six bf16 MFMA terms

@@ -31,6 +31,25 @@ inline bool narrow_wgrad_eligible(const TView& x, const TView& dz, int KS) {
     if (KS != 3 || x.C > 8 || dz.C > 16 || x.d2s > 1 || dz.d2s > 1 || !dz.vec) return false;    // x may be unaligned / Cin % 4 != 0
     return (long)cdiv(x.W, NTW) * cdiv(x.H, NTH) * x.N < (1l << 20);                   // fast_div range
 }
+// conv_pointwise.hip: 1x1 layers as a stream over the flattened pixels.  Channel counts that are multiples of four, up to 48; every
+// operand a float4-able view whose pixels form one flat array (any pitch ld >= C: a channel slice of a wider buffer; no
+// depth_to_space, no frame pick, no channel affine); the epilogue one of the built forms -- bias with {nothing, ReLU, residual,
+// residual + ReLU, ReLU mask, accumulate, mask + accumulate}.  Everything else keeps the kernels behind the route
+// (conv_point_kernel: channel counts that are not multiples of four).  DL4DS_NO_POINTWISE=1 (a test hook: the A/B comparison of
+// tests/test_gpu_conv_pointwise.py; any value in an experiments build) switches the family off, and DL4DS_STREAM_FORCE_WS, which
+// forces conv_stream_ws_kernel onto small grids, forces it past this family too.
+inline bool pointwise_view_ok(const TView& v) {
+    return v.p && v.vec && v.d2s <= 1 && !v.sc && v.ld >= v.C && v.nstride == (size_t)v.H * v.W * v.ld;
+}
+inline bool pointwise_ok(const TView& in, const TView& out, int KS, const ConvEpilogue& ep) {
+    if (KS != 1 || test_env("DL4DS_NO_POINTWISE") || test_env("DL4DS_STREAM_FORCE_WS")) return false;
+    if ((in.C & 3) || (out.C & 3) || in.C < 4 || out.C < 4 || in.C > 48 || out.C > 48) return false;
+    if (!pointwise_view_ok(in) || !pointwise_view_ok(out) || ep.pool || ((((uintptr_t)ep.bias) & 15) != 0)) return false;
+    if (ep.add.p && (!pointwise_view_ok(ep.add) || ep.add.C != out.C)) return false;
+    if (ep.mask.p && (!pointwise_view_ok(ep.mask) || ep.mask.C != out.C)) return false;
+    const int form = (ep.add.p ? 1 : 0) | (ep.relu ? 2 : 0) | (ep.mask.p ? 4 : 0) | (ep.accumulate ? 8 : 0);
+    return form == 0 || form == 1 || form == 2 || form == 3 || form == 4 || form == 8 || form == 12;
+}
 // channels [c0, c1) of the same pixels: a plain view at the tensor's pitch
 inline TView channel_slice(const TView& x, int c0, int c1) {
     TView v = x;
@@ -40,9 +59,9 @@ inline TView channel_slice(const TView& x, int c0, int c1) {
 }
 }  // namespace conv_route
 
-// ---- forward / dgrad.  Direct: conv_direct.hip; NarrowPair: the pair kernel; Narrow: the other kernels of conv_narrow.hip; Rest:
-// conv2d_forward's chain split -> wino -> gemm -> stream -> point -> gemm -> general, whose choices read the device and per-stream state.
-enum class ConvFwdFamily { Direct, NarrowPair, Narrow, Rest };
+// ---- forward / dgrad.  Direct: conv_direct.hip; NarrowPair: the pair kernel; Narrow: the other kernels of conv_narrow.hip; Pointwise:
+// conv_pointwise.hip (1x1); Rest: conv2d_forward's chain split -> wino -> gemm -> stream -> point -> gemm -> general, whose choices read the device and per-stream state.
+enum class ConvFwdFamily { Direct, NarrowPair, Narrow, Pointwise, Rest };
 struct ConvFwdRoute { ConvFwdFamily family; const char* refusal; };      // refusal: null, or what conv2d_forward throws for the call
 
 inline ConvFwdRoute conv2d_forward_route(const TView& in, const TView& out, int KS, const ConvEpilogue& ep) {
@@ -53,6 +72,8 @@ inline ConvFwdRoute conv2d_forward_route(const TView& in, const TView& out, int 
         // (a residual or mask operand in depth_to_space layout: the stencil kernels step aside)
         if (!(ep.add.p && ep.add.d2s > 1) && !(ep.mask.p && ep.mask.d2s > 1)) return {ConvFwdFamily::Direct, nullptr};
     }
+    // 1x1 with float4-able channel counts up to 48 on flat views: HBM stream over the flattened pixels
+    if (pointwise_ok(in, out, KS, ep)) return {ConvFwdFamily::Pointwise, nullptr};
     if (!exp_env("DL4DS_NO_NARROW") && KS == 3 && in.C <= 16 && out.C <= 16 && in.d2s <= 1) {
         const bool pair = narrow_pair_ok(in, out, KS, ep);
         // 9..16 input channels that are not a multiple of four (the 13-channel ConvBlock behind TransitionLast 26 -> 13): the halo

@@ -46,6 +46,9 @@ void conv2d_wgrad(hipStream_t s, const TView& x, const TView& dz, int KS, float*
 void conv2d_direct_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
 // 3x3, Cin <= 16, Cout <= 16: register-resident filter, persistent MFMA kernel (conv_narrow.hip); pair_ok: the route is NarrowPair
 void conv2d_narrow_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep, bool pair_ok);
+// 1x1 layers with channel counts that are multiples of four, up to 48, on flat views (conv_pointwise.hip): register-direct loads,
+// MFMA, float4 stores, no LDS; the route is Pointwise
+void conv2d_pointwise_forward(hipStream_t s, const TView& in, const float* w, const TView& out, const ConvEpilogue& ep);
 // 1x1 layers whose channel counts are not multiples of four (conv_point.hip): contiguous staging + MFMA + contiguous store
 bool conv2d_point_forward(hipStream_t s, const TView& in, const float* w, int KS, const TView& out, const ConvEpilogue& ep);
 int conv2d_narrow_pair_tiles_per_image(int H, int W);

@@ -52,6 +52,7 @@ static const char* name_of(ConvFwdFamily f) {
         case ConvFwdFamily::Direct: return "Direct";
         case ConvFwdFamily::NarrowPair: return "NarrowPair";
         case ConvFwdFamily::Narrow: return "Narrow";
+        case ConvFwdFamily::Pointwise: return "Pointwise";
         default: return "Rest";
     }
 }
